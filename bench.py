@@ -21,6 +21,14 @@ NOT a scaling measurement.  Rank 0 prints ONE JSON line.
 Secondary lines (never the default): --mode train_bf16 | vrig | fullhd | eval, --bf16 (or BENCH_BF16=1) for the bfloat16
 NeRF-MLP mode of vrig / fullhd / eval, --rays-per-gpu N (e.g. 128 = one GPU's share of the north star's 1024-ray global batch
 on 8 GPUs: the strong-scaling point), --graph (the whole step replayed from one hipGraph).
+
+A plain run does only what the headline figure needs: set-up, burn-in, W warm-up steps, K timed steps, the result line.
+--full adds everything else the line used to carry: clock / power sampling, the per-kernel HIP-event profile and roofline, the
+replica checks and all-reduce timings of N>1, the strong-scaling record, the CPU baseline and, on the default one-GPU line, the
+sustained run, the config-E parity record and the secondary lines.  --dump-outputs DIR writes what the last timed step returned
+(train: parameters, Adam moments, gradient, step statistics; eval: the rendered chunk) as DIR/<name>.npy.  The train steps run
+at learning rate 0 (BENCH_LR) and start from the same Adam state and key whatever the burn-in did, so every run gives the last
+step the same inputs and its outputs agree to rounding: two builds can be compared output for output.
 """
 import argparse
 import json
@@ -191,6 +199,12 @@ class CfgEvalWarp(CfgEval):   # BASELINE.md config E as nerfies renders it (eval
   use_warp, num_warp_freqs, num_warp_features, warp_field_type = True, 8, 8, 'se3'
 
 
+# Learning rate of the benchmarked train steps.  0: every step starts from the same seeded parameters, so what a step computes is
+# the same from run to run up to rounding.  With a positive rate it is not: the fine level's float atomics sum in a different order
+# on every run, and Adam's normalised update turns those rounding differences into lr-sized parameter moves that grow step after
+# step.  The cost of a step does not depend on the rate: Adam still reads and writes every parameter and both moments.
+BENCH_LR = 0.0
+
 # training workloads: rays per GPU, model config, regularisers, warp alpha, the gin shape they stand for
 NUM_FRAMES = int(os.environ.get('BENCH_FRAMES', 256))   # frames of the synthetic capture: warp / appearance ids per frame
 
@@ -213,6 +227,45 @@ BF16_NOTE_MLP = (' [opt-in bf16 mode, NeRF MLPs only: bfloat16 NeRF-MLP operands
                  'SE3 warp field and its regularisers, compositing, loss, all-reduce, Adam]')
 BF16_NOTE_ALL = (' [opt-in bf16 mode: bfloat16 operands and activation / dY stash of the NeRF MLPs and of the SE3 trunk; fp32 master '
                  'weights, posenc, exp_se3 / Jacobian algebra / regularisers, GLO tables, compositing, loss, all-reduce, Adam]')
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _leaves(tree, prefix=''):
+  """(dotted name, tensor) of every tensor in a nested dict; '/' in a key (the stats' 'loss/rgb') becomes '_'."""
+  for k, v in tree.items():
+    name = prefix + str(k).replace('/', '_')
+    if isinstance(v, dict):
+      yield from _leaves(v, name + '.')
+    elif torch.is_tensor(v):
+      yield name, v
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+  """--dump-outputs: every {name: tensor} as <path>/<name>.npy, float64 kept, everything else as float32.  If the arrays
+  together exceed `limit` bytes, each array above an even share of it is replaced by a fixed sample of its flattened elements
+  (positions drawn by a generator seeded from the name, sorted, written as <name>.index.npy), so two runs write the same
+  positions.  Returns {name: number of elements written}."""
+  import zlib
+  import numpy as np
+  os.makedirs(path, exist_ok=True)
+  arrs = {}
+  for name, t in arrays.items():
+    a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    arrs[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+  share = limit // max(len(arrs), 1)
+  sampled = sum(a.nbytes for a in arrs.values()) > limit
+  written = {}
+  for name, a in arrs.items():
+    if sampled and a.nbytes > share:
+      k = share // (a.itemsize + 8)   # the float64 index costs 8 bytes per element
+      idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, k, replace=False))
+      np.save(os.path.join(path, name + '.index.npy'), idx.astype(np.float64))
+      a = a.reshape(-1)[idx]
+    np.save(os.path.join(path, name + '.npy'), a)
+    written[name] = int(a.size)
+  return written
 
 
 def synthetic_batch(n, seed, device):
@@ -573,10 +626,11 @@ def rccl_version():
     return f'unavailable ({type(e).__name__})'
 
 
-def eval_mode(args, world, rank, dev, bf16, emit=True):
+def eval_mode(args, world, rank, dev, bf16, emit=True, dump=None):
   """BASELINE configs[4]: the video-render forward, 8192-ray chunks x (128+128), hipGraph replay.  --warp: with the SE3 field
   (the path eval.py actually renders, models.py:251-267: 526.1 MFLOP/ray); --frame: additionally times evaluation.render_image
-  on a whole 960x540 frame (chunk scheduling, tail padding, the copy of every chunk into the frame buffer included)."""
+  on a whole 960x540 frame (chunk scheduling, tail padding, the copy of every chunk into the frame buffer included).
+  `dump`: directory for the rendered chunk of the last timed replay (rank 0)."""
   from nerfies_amd import evaluation, models, training
   n = 8192
   cfg = CfgEvalWarp if args.warp else CfgEval
@@ -588,7 +642,10 @@ def eval_mode(args, world, rank, dev, bf16, emit=True):
     rays['metadata'] = {'warp': torch.full((n, 1), 3 + rank, dtype=torch.int32, device=dev)}
     extra = {'alpha': 8.0}
   fn = evaluation.GraphedChunkRenderer(model, bf16=bf16)
-  step = lambda: fn.call_static(0, 1, fp, rays, extra)
+  box = {}
+
+  def step():
+    box['out'] = fn.call_static(0, 1, fp, rays, extra)
   prof_step = lambda: model.apply({'params': fp}, rays, extra, bf16=bf16)   # HIP events cannot be recorded inside a graph replay
 
   def barrier():
@@ -600,18 +657,20 @@ def eval_mode(args, world, rank, dev, bf16, emit=True):
   for _ in range(args.warmup):
     step()
   barrier()
-  sampler = ClockSampler((dev.index or 0) if world > 1 else 0)
-  sampler.start()
+  sampler = ClockSampler((dev.index or 0) if world > 1 else 0) if args.full else None
+  if sampler:
+    sampler.start()
   t0 = time.perf_counter()
   for _ in range(args.steps):
     step()
   barrier()
   elapsed = time.perf_counter() - t0
-  clocks = sampler.stop()
+  clocks = sampler.stop() if sampler else None
   if world > 1:
     t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = t.item()
+  dumped = dump_outputs(dump, dict(_leaves(box['out']))) if dump and rank == 0 else None
   frame = None
   if args.frame:
     # one 960 x 540 frame (the quarter-HD capture of the README) through render_image: 64 chunks of 8192 rays, the last one
@@ -635,19 +694,15 @@ def eval_mode(args, world, rank, dev, bf16, emit=True):
     frame = {'size': [w, h], 'chunks': nchunks, 'frame_ms': frame_ms, 'sum_of_chunk_replays_ms': nchunks * chunk_ms,
              'overhead_frac': frame_ms / (nchunks * chunk_ms) - 1.0 if world == 1 else None,
              'frames_per_s': 1e3 / frame_ms}
-  model.profile_enable(True)
-  for _ in range(5):
-    prof_step()
-  torch.cuda.synchronize()
-  prof = model.profile_read()
-  model.profile_enable(False)
+  prof = None
+  if args.full:
+    model.profile_enable(True)
+    for _ in range(5):
+      prof_step()
+    torch.cuda.synchronize()
+    prof = model.profile_read()
+    model.profile_enable(False)
   if rank == 0:
-    roofline, peak = roofline_of(prof, bf16, ('eval_warp' if args.warp else 'eval') + ('_x3' if bf16 in ('x3', 'x3mlp') else '_bf16' if bf16 else ''), n, cfg)
-    if bf16 in ('x3', 'x3mlp'):
-      roofline['peak_note'] = ('dense bf16 MFMA peak / 3: every algorithmic multiply-add is three bf16 MFMAs (hi.hi + lo.hi + hi.lo, fp32 accumulate); '
-                               'the float32 chains it emulates are priced against 157.3 TFLOP/s')
-    at_clock(roofline, clocks)
-    step_flops = sum(e['flops_per_launch'] * e['launches'] for e in prof) / 5
     ms = 1e3 * elapsed / args.steps
     warp_txt = 'SE3 warp F_w=8 G=8 (one warp id per chunk)' if args.warp else 'warp off'
     line = {
@@ -658,10 +713,17 @@ def eval_mode(args, world, rank, dev, bf16, emit=True):
         'dtype': ('bf16x3 (fp32-emulating) NeRF MLPs + f32 warp field' if (args.warp and bf16 == 'x3mlp') else 'bf16x3 (fp32-emulating)') if bf16 in ('x3', 'x3mlp') else
                  ('bf16 NeRF MLPs + f32 warp field' if (args.warp and bf16 == 'mlp') else 'bf16') if bf16 else 'f32', 'data': 'synthetic',
         'config': {'workload': f'gpu eval/video shape: 8192-ray chunk x (128+128) samples, F_p=8, {warp_txt}, deterministic, forward only',
-                   'rays_per_gpu': n, 'parallelism': f'ray-shard dp{world}'},
-        'roofline': roofline, 'step_tflops': step_flops / (ms * 1e-3) / 1e12, 'kernels': kernel_table(prof, 5),
-        'frame': frame, 'steady_state': {'burn_in_s': args.burn_in_s, 'timed_window_s': elapsed, 'during_timed_window': clocks},
-        'csrc_sha16': kernel_source_sha()}
+                   'rays_per_gpu': n, 'parallelism': f'ray-shard dp{world}'}}
+    if prof is not None:
+      roofline, peak = roofline_of(prof, bf16, ('eval_warp' if args.warp else 'eval') + ('_x3' if bf16 in ('x3', 'x3mlp') else '_bf16' if bf16 else ''), n, cfg)
+      if bf16 in ('x3', 'x3mlp'):
+        roofline['peak_note'] = ('dense bf16 MFMA peak / 3: every algorithmic multiply-add is three bf16 MFMAs (hi.hi + lo.hi + hi.lo, fp32 accumulate); '
+                                 'the float32 chains it emulates are priced against 157.3 TFLOP/s')
+      at_clock(roofline, clocks)
+      step_flops = sum(e['flops_per_launch'] * e['launches'] for e in prof) / 5
+      line.update({'roofline': roofline, 'step_tflops': step_flops / (ms * 1e-3) / 1e12, 'kernels': kernel_table(prof, 5)})
+    line.update({'frame': frame, 'steady_state': {'burn_in_s': args.burn_in_s, 'timed_window_s': elapsed, 'during_timed_window': clocks},
+                 'csrc_sha16': kernel_source_sha(), 'full': bool(args.full), 'dumped_outputs': dumped})
     if emit:
       print(json.dumps(line))
     return line
@@ -702,10 +764,11 @@ def self_launch(args, argv):
   return subprocess.run(cmd, env=env).returncode
 
 
-def train_workload(args, M, cfg, rays_per_gpu, bf16, graph, ctx, profile=True):
+def train_workload(args, M, cfg, rays_per_gpu, bf16, graph, ctx, profile=True, dump=None):
   """One training workload measured as the contract says: burn-in, W warm-up steps, K timed steps between barrier +
-  synchronize, MAX over ranks; then the self-checks (replica checksums, the collective on its own, the step without the
-  collective) and the per-kernel HIP-event profile.  Returns a dict of measurements (every rank; rank 0 prints)."""
+  synchronize, MAX over ranks; with --full then the self-checks (replica checksums, the collective on its own, the step without
+  the collective) and the per-kernel HIP-event profile.  `dump`: directory for what the last timed step returned (rank 0).
+  Returns a dict of measurements (every rank; rank 0 prints)."""
   from nerfies_amd import models, training
   world, rank, dev, dist_on = ctx['world'], ctx['rank'], ctx['dev'], ctx['dist_on']
   # metadata ids as a capture has them: one warp / appearance id per FRAME (a vrig capture has a few hundred frames and a batch
@@ -718,7 +781,7 @@ def train_workload(args, M, cfg, rays_per_gpu, bf16, graph, ctx, profile=True):
   batch = synthetic_batch(rays_per_gpu, seed=100 + rank, device=dev)   # each rank: its own ray shard
   kw = {}
   if M['reg']:
-    sp = training.ScalarParams(learning_rate=1e-3, background_loss_weight=1.0, elastic_loss_weight=M['elastic_w'])
+    sp = training.ScalarParams(learning_rate=BENCH_LR, background_loss_weight=1.0, elastic_loss_weight=M['elastic_w'])
     g = torch.Generator().manual_seed(rank)
     md = {'warp': torch.randint(0, NUM_FRAMES, (rays_per_gpu, 1), generator=g).to(dev)}
     if getattr(cfg, 'use_camera_metadata', False):
@@ -730,7 +793,7 @@ def train_workload(args, M, cfg, rays_per_gpu, bf16, graph, ctx, profile=True):
     batch['background_points'] = ((torch.rand(16384, 3, generator=g) - 0.5) * 0.8).to(dev)
     kw = dict(use_elastic_loss=True, elastic_reduce_method='weight', use_background_loss=True)
   else:
-    sp = training.ScalarParams(learning_rate=1e-3)
+    sp = training.ScalarParams(learning_rate=BENCH_LR)
   key = 12345 + rank
 
   def barrier():
@@ -764,22 +827,38 @@ def train_workload(args, M, cfg, rays_per_gpu, bf16, graph, ctx, profile=True):
 
   # untimed burn-in at the same workload (>= --burn-in-s seconds) so the short timed window below sits at steady-state
   # clocks and power; the sampler keeps running through the timed region
-  sampler = ClockSampler(ctx['local_rank'] if world > 1 else 0)
+  sampler = ClockSampler(ctx['local_rank'] if world > 1 else 0) if args.full else None
   burn_steps = burn_in(step, args.burn_in_s, world, dev) if args.burn_in_s > 0 else 0
+  if burn_steps:
+    # the burn-in runs for a time, not for a number of steps: the warm-up and timed steps start again from the initial Adam
+    # state and key (the parameters stay the seeded ones at BENCH_LR = 0), so what the last timed step is given does not depend
+    # on how many burn-in steps ran
+    opt = state.optimizer
+    opt.m.zero_()
+    opt.v.zero_()
+    opt.step = 0
+    box['key'] = key
   for _ in range(args.warmup):
     step()
   barrier()
-  sampler.start()
+  if sampler:
+    sampler.start()
   elapsed = timed(args.steps)
-  clocks = sampler.stop()
+  clocks = sampler.stop() if sampler else None
   state, stats, key = box['state'], box['stats'], box['key']
+  dumped = None
+  if dump and rank == 0:
+    opt = state.optimizer
+    dumped = dump_outputs(dump, dict([('params', opt.target.flat), ('adam_m', opt.m), ('adam_v', opt.v), ('grad', opt.grad)] +
+                                     [('stats.' + k, v) for k, v in _leaves(stats)]))
   loss = stats['fine']['loss/rgb'].item()
   # every rank applied the same all-reduced gradient to the same initial parameters: the replicas must be BIT-identical.
-  # Checked on a checksum of the parameter bits (the per-rank losses are reported too: the step's statistics are pmean'ed over the
-  # ranks, training.py:267, so they agree as well)
+  # Checked on a checksum of the bits of the parameters and of Adam's first moment, which every step's gradient enters also at
+  # BENCH_LR = 0 (the per-rank losses are reported too: the step's statistics are pmean'ed over the ranks, training.py:267, so
+  # they agree as well)
   per_rank_loss, replicas_agree = [loss], True
-  if dist_on:
-    flat = state.optimizer.target.flat
+  if dist_on and args.full:
+    flat = torch.cat([state.optimizer.target.flat, state.optimizer.m])
     mine = torch.stack([flat.view(torch.int32).to(torch.int64).sum(), (flat.view(torch.int32).to(torch.int64) * 31 % 1000003).sum()])
     both = torch.cat([mine.to(torch.float64), torch.tensor([loss], device=dev, dtype=torch.float64)])
     allr = [torch.empty_like(both) for _ in range(dist.get_world_size())]
@@ -791,7 +870,7 @@ def train_workload(args, M, cfg, rays_per_gpu, bf16, graph, ctx, profile=True):
 
   # ---- the gradient all-reduce on its own (outside the timed region): the fused [grad | stats] buffer, 20 calls ----
   allreduce_us = exposed_us = None
-  if dist_on:
+  if dist_on and args.full:
     buf = torch.zeros_like(state.optimizer._gs)
     for _ in range(5):
       dist.all_reduce(buf)
@@ -818,7 +897,7 @@ def train_workload(args, M, cfg, rays_per_gpu, bf16, graph, ctx, profile=True):
       exposed_us = 1e6 * (elapsed - nocomm) / args.steps
 
   prof, prof_steps = None, 0
-  if profile:
+  if profile and args.full:
     # per-kernel timing of the SAME step with HIP events on the launch stream (eager: events cannot be recorded inside a
     # graph replay)
     model.profile_enable(True)
@@ -831,7 +910,7 @@ def train_workload(args, M, cfg, rays_per_gpu, bf16, graph, ctx, profile=True):
   return {'elapsed': elapsed, 'ms_per_step': 1e3 * elapsed / args.steps, 'value': world * rays_per_gpu * args.steps / elapsed,
           'loss': loss, 'per_rank_loss': per_rank_loss, 'replicas_agree': replicas_agree, 'allreduce_us': allreduce_us,
           'allreduce_exposed_us': exposed_us, 'allreduce_bytes': 4 * state.optimizer._gs.numel(), 'burn_steps': burn_steps,
-          'clocks': clocks, 'prof': prof, 'prof_steps': prof_steps}
+          'clocks': clocks, 'prof': prof, 'prof_steps': prof_steps, 'dumped': dumped}
 
 
 def main(argv=None):
@@ -840,9 +919,15 @@ def main(argv=None):
   ap.add_argument('--gpus', type=int, default=1)
   ap.add_argument('--steps', type=int, default=30)
   ap.add_argument('--warmup', type=int, default=5)
-  ap.add_argument('--no-cpu-baseline', action='store_true')
+  ap.add_argument('--full', action='store_true',
+                  help='measure and check everything beyond the headline figure: clock / power sampling, per-kernel profile and '
+                       'roofline, replica checks, all-reduce timings and strong scaling (N>1), the CPU baseline and, on the default '
+                       'one-GPU line, the sustained run, eval_parity and the secondary lines')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)')
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
   ap.add_argument('--no-extras', action='store_true',
-                  help='headline line only: skip eval_parity (config-E HIP vs float64 oracle), the secondary lines (vrig fp32, '
+                  help='--full, headline line only: skip eval_parity (config-E HIP vs float64 oracle), the secondary lines (vrig fp32, '
                        'fullhd bf16, eval with the warp) and the sustained run that the default one-GPU line carries')
   ap.add_argument('--sustained-s', type=float, default=5.0, help='seconds of the sustained headline run of the default line')
   ap.add_argument('--burn-in-s', type=float, default=3.0,
@@ -906,7 +991,7 @@ def main(argv=None):
     if torch.cuda.device_count() >= world and not os.environ.get('BENCH_SAME_DEVICE') and backend != 'nccl':
       raise SystemExit(f'{torch.cuda.device_count()} devices for {world} ranks but BENCH_DIST_BACKEND={backend}: the scaling run must '
                        'use nccl (RCCL)')
-    rccl_log = rccl_preflight_begin(rank) if backend == 'nccl' else None
+    rccl_log = rccl_preflight_begin(rank) if backend == 'nccl' and args.full else None
     if backend == 'nccl':
       dist.init_process_group('nccl', device_id=torch.device('cuda', local_rank), **kw)
     else:
@@ -926,7 +1011,7 @@ def main(argv=None):
       raise SystemExit('--split-bf16 is an inference mode (--mode eval) of its own, not combined with --bf16')
     bf16 = 'x3mlp' if args.warp_f32 else 'x3'   # --warp-f32: the SE3 trunk stays on the float32 kernels
   if args.mode == 'eval':
-    eval_mode(args, world, rank, dev, bf16)
+    eval_mode(args, world, rank, dev, bf16, dump=args.dump_outputs)
     if dist_on:
       dist.destroy_process_group()
     return
@@ -936,13 +1021,13 @@ def main(argv=None):
   BF16_NOTE = BF16_NOTE_MLP if bf16 == 'mlp' else BF16_NOTE_ALL
   cfg = M['cfg']
   rays_per_gpu = args.rays_per_gpu or M['rays']
-  r = train_workload(args, M, cfg, rays_per_gpu, bf16, args.graph, ctx)
+  r = train_workload(args, M, cfg, rays_per_gpu, bf16, args.graph, ctx, dump=args.dump_outputs)
 
   # ---- N>1: the north star's other curve in the same run.  "1024-ray batches at 1, 2, 4, 8": the GLOBAL batch stays 1024
   #      rays, every GPU gets 1024/N of them (training.py:266 pmean over the same global batch) -- eager, and with the whole
   #      step replayed from one hipGraph (what a ~1 ms step needs) ----
   strong = None
-  if world > 1 and not args.no_strong and not args.rays_per_gpu and RAYS_PER_GPU % world == 0:
+  if world > 1 and args.full and not args.no_strong and not args.rays_per_gpu and RAYS_PER_GPU % world == 0:
     per = RAYS_PER_GPU // world
     strong = {'global_batch': RAYS_PER_GPU, 'rays_per_gpu': per, 'scaling': 'strong', 'unit': 'rays/s'}
     sargs = argparse.Namespace(**dict(vars(args), burn_in_s=min(args.burn_in_s, 1.0)))
@@ -960,15 +1045,26 @@ def main(argv=None):
   if rank == 0:
     prof, prof_steps, elapsed, clocks = r['prof'], r['prof_steps'], r['elapsed'], r['clocks']
     ms_per_step = r['ms_per_step']
-    step_flops = sum(e['flops_per_launch'] * e['launches'] for e in prof) / prof_steps
-    mode_key = args.mode + ('_bf16' if bf16 and not M.get('force_bf16') else '')
-    roofline, peak_tf = roofline_of(prof, bf16, mode_key, rays_per_gpu, cfg)
-    at_clock(roofline, clocks)
-    kernels = kernel_table(prof, prof_steps)
-    ksum_ms = sum(v['ms'] * v['launches_per_step'] for v in kernels.values())
     mixed = bf16 == 'mlp' and getattr(cfg, 'use_warp', False)   # bf16 NeRF MLPs next to a float32 SE3 trunk
-    # the step's flops are priced against the bf16 peak only when every MFMA kernel of it runs in bf16 (warp off)
-    step_peak = PEAK_BF16_MFMA_TFLOPS if (bf16 and not mixed) else PEAK_FP32_MFMA_TFLOPS
+    profiled = {}
+    if prof is not None:
+      step_flops = sum(e['flops_per_launch'] * e['launches'] for e in prof) / prof_steps
+      mode_key = args.mode + ('_bf16' if bf16 and not M.get('force_bf16') else '')
+      roofline, peak_tf = roofline_of(prof, bf16, mode_key, rays_per_gpu, cfg)
+      at_clock(roofline, clocks)
+      kernels = kernel_table(prof, prof_steps)
+      ksum_ms = sum(v['ms'] * v['launches_per_step'] for v in kernels.values())
+      # the step's flops are priced against the bf16 peak only when every MFMA kernel of it runs in bf16 (warp off)
+      step_peak = PEAK_BF16_MFMA_TFLOPS if (bf16 and not mixed) else PEAK_FP32_MFMA_TFLOPS
+      profiled = {
+          'roofline': roofline,
+          'step_tflops': step_flops / (ms_per_step * 1e-3) / 1e12,
+          ('step_frac_of_bf16_mfma_peak' if step_peak == PEAK_BF16_MFMA_TFLOPS else 'step_frac_of_fp32_mfma_peak'):
+              None if mixed else step_flops / (ms_per_step * 1e-3) / 1e12 / step_peak,
+          'kernels': kernels, 'sum_of_kernels_ms': ksum_ms, 'step_over_sum_of_kernels': ms_per_step / ksum_ms if ksum_ms else None}
+    checked = {}
+    if args.full:
+      checked = {'per_rank_final_loss_fine': r['per_rank_loss'], 'replica_param_checksums_agree': r['replicas_agree']}
     over = os.environ.get('BENCH_OVERSUBSCRIBED')
     out = {
         'metric': M['metric'], 'value': r['value'], 'unit': 'rays/s', 'n_gpus': world,
@@ -978,31 +1074,26 @@ def main(argv=None):
         'config': {'workload': M['workload'].format(rays=rays_per_gpu) + (BF16_NOTE if bf16 else '') +
                                (' [whole step replayed from one hipGraph]' if args.graph else ''),
                    'rays_per_gpu': rays_per_gpu, 'global_batch': world * rays_per_gpu, 'parallelism': f'ray-shard dp{world}',
-                   'metadata_frames': NUM_FRAMES if M['reg'] else None},
-        'roofline': roofline,
-        'step_tflops': step_flops / (ms_per_step * 1e-3) / 1e12,
-        ('step_frac_of_bf16_mfma_peak' if step_peak == PEAK_BF16_MFMA_TFLOPS else 'step_frac_of_fp32_mfma_peak'):
-            None if mixed else step_flops / (ms_per_step * 1e-3) / 1e12 / step_peak,
-        'kernels': kernels, 'sum_of_kernels_ms': ksum_ms, 'step_over_sum_of_kernels': ms_per_step / ksum_ms if ksum_ms else None,
-        'final_loss_fine': r['loss'], 'per_rank_final_loss_fine': r['per_rank_loss'],
-        'replica_param_checksums_agree': r['replicas_agree'],
+                   'metadata_frames': NUM_FRAMES if M['reg'] else None, 'learning_rate': BENCH_LR},
+        **profiled,
+        'final_loss_fine': r['loss'], **checked,
         'steady_state': {'burn_in_steps': r['burn_steps'], 'burn_in_s': args.burn_in_s, 'timed_window_s': elapsed,
                          'during_timed_window': clocks},
         'graph_replay': bool(args.graph),
         'rccl_ranks': dist.get_world_size() if dist_on else 1, 'dist_backend': backend if dist_on else None,
-        'rccl_version': rccl_version() if dist_on and backend == 'nccl' else None,
-        'rccl_preflight': rccl_preflight_summary(rccl_log) if dist_on and backend == 'nccl' else None,
+        'rccl_version': rccl_version() if dist_on and backend == 'nccl' and args.full else None,
+        'rccl_preflight': rccl_preflight_summary(rccl_log) if dist_on and backend == 'nccl' and args.full else None,
         'grad_allreduce_us': r['allreduce_us'], 'grad_allreduce_bytes': r['allreduce_bytes'],
         'grad_allreduce_exposed_us': r['allreduce_exposed_us'],
         'grad_allreduce_exposed_frac': (r['allreduce_exposed_us'] / (1e3 * ms_per_step)) if r['allreduce_exposed_us'] is not None else None,
         'strong_scaling': strong,
         'oversubscribed': over,
         'chain_tile_rows': args.chain_rows or 'auto', 'bf16_wgrad_merge': 'default (1)' if args.bf16_wgrad_merge is None else args.bf16_wgrad_merge,
-        'csrc_sha16': kernel_source_sha(),
+        'csrc_sha16': kernel_source_sha(), 'full': bool(args.full), 'dumped_outputs': r['dumped'],
     }
     if over:
       out['config']['workload'] += f' [OVERSUBSCRIBED: {over}, transport {backend} -- code-path check, not a scaling measurement]'
-    default_line = (world == 1 and args.mode == 'train' and not force_dist and not args.graph and not args.rays_per_gpu and
+    default_line = (args.full and world == 1 and args.mode == 'train' and not force_dist and not args.graph and not args.rays_per_gpu and
                     not bf16 and not args.no_extras)
     if default_line:
       # ---- what makes the ONE driver-run line certify more than the headline's 0.14 s window (all outside the timed region):
@@ -1031,7 +1122,7 @@ def main(argv=None):
                          for k in ('mode', 'dtype', 'value', 'ms_per_step', 'roofline_frac', 'error') if k == 'roofline_frac' or k in x}
                         for x in sec],
           'sustained': {k: sus.get(k) for k in ('seconds', 'value', 'error') if k in sus}}
-    if world == 1 and args.mode == 'train' and not args.no_cpu_baseline and not force_dist:
+    if args.full and world == 1 and args.mode == 'train' and not args.no_cpu_baseline and not force_dist:
       out['cpu_baseline'] = cpu_baseline()
     # the per-kernel table is the longest object of the line: it goes LAST but for the certificates, which a tail-only reader
     # of the line (the driver keeps the last ~2 KB of stdout) must still see

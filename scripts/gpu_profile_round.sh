@@ -44,7 +44,7 @@ for mode in $MODES; do
   # LIGHT="mode ..." (environment): bench line only for those workloads (when the GPU budget does not cover every pass)
   case " $LIGHT " in *" $mode "*) PMC=0; TRACE=0 ;; esac
   NOCPU="--no-cpu-baseline"; [ "$mode" = train ] && NOCPU=""
-  timeout 900 python bench.py $ARGS --steps $STEPS --warmup 5 $NOCPU > $O/${TAG}_bench${SUF}.json 2> $O/${TAG}_bench${SUF}.err
+  timeout 900 python bench.py --full $ARGS --steps $STEPS --warmup 5 $NOCPU > $O/${TAG}_bench${SUF}.json 2> $O/${TAG}_bench${SUF}.err
   head -c 300 $O/${TAG}_bench${SUF}.json; echo
   [ $TRACE = 0 ] && continue
   rm -rf $O/prof_${TAG}${SUF} $O/pmc1_${TAG}${SUF} $O/pmc2_${TAG}${SUF} $O/pmc3_${TAG}${SUF}
@@ -52,21 +52,21 @@ for mode in $MODES; do
   # ... and the headline workload ALONE: since round 6 the default line also runs the secondary workloads, whose launches of the same
   # kernel symbols (other shapes) would be averaged into the per-launch times and bytes of the config-A kernels
   [ "$mode" = train ] && PARGS="$PARGS --no-extras"
-  timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_${TAG}${SUF} -o kt -- python bench.py $PARGS --steps 10 --warmup 2 --burn-in-s 0 --no-cpu-baseline > $O/prof_${TAG}${SUF}.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_${TAG}${SUF} -o kt -- python bench.py --full $PARGS --steps 10 --warmup 2 --burn-in-s 0 --no-cpu-baseline > $O/prof_${TAG}${SUF}.log 2>&1
   summ $O/prof_${TAG}${SUF} $O/${TAG}${SUF}_kernel_stats.md
-  timeout 300 rocprofv3 --pmc $SQ -d $O/pmc1_${TAG}${SUF} -o pmc -- python bench.py $PARGS --steps 3 --warmup 1 --burn-in-s 0 --no-cpu-baseline > $O/pmc1_${TAG}${SUF}.log 2>&1
+  timeout 300 rocprofv3 --pmc $SQ -d $O/pmc1_${TAG}${SUF} -o pmc -- python bench.py --full $PARGS --steps 3 --warmup 1 --burn-in-s 0 --no-cpu-baseline > $O/pmc1_${TAG}${SUF}.log 2>&1
   summ $O/pmc1_${TAG}${SUF} $O/${TAG}${SUF}_pmc_sq.md
   case $mode in train|train_bf16|eval_bf16)   # instruction fetch: the unrolled bf16 chains are ~100 KiB of code (cold start of every launch)
-    timeout 300 rocprofv3 --pmc $ICC -d $O/pmc5_${TAG}${SUF} -o pmc -- python bench.py $PARGS --steps 3 --warmup 1 --burn-in-s 0 --no-cpu-baseline > $O/pmc5_${TAG}${SUF}.log 2>&1
+    timeout 300 rocprofv3 --pmc $ICC -d $O/pmc5_${TAG}${SUF} -o pmc -- python bench.py --full $PARGS --steps 3 --warmup 1 --burn-in-s 0 --no-cpu-baseline > $O/pmc5_${TAG}${SUF}.log 2>&1
     summ $O/pmc5_${TAG}${SUF} $O/${TAG}${SUF}_pmc_icache.md; clean $O/pmc5_${TAG}${SUF} ;;
   esac
   case $mode in *bf16*|*x3*)
-    timeout 300 rocprofv3 --pmc $LDSC -d $O/pmc4_${TAG}${SUF} -o pmc -- python bench.py $PARGS --steps 3 --warmup 1 --burn-in-s 0 --no-cpu-baseline > $O/pmc4_${TAG}${SUF}.log 2>&1
+    timeout 300 rocprofv3 --pmc $LDSC -d $O/pmc4_${TAG}${SUF} -o pmc -- python bench.py --full $PARGS --steps 3 --warmup 1 --burn-in-s 0 --no-cpu-baseline > $O/pmc4_${TAG}${SUF}.log 2>&1
     summ $O/pmc4_${TAG}${SUF} $O/${TAG}${SUF}_pmc_lds.md; clean $O/pmc4_${TAG}${SUF} ;;
   esac
   if [ $PMC = 1 ]; then
-    timeout 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc2_${TAG}${SUF} -o pmc -- python bench.py $PARGS --steps 3 --warmup 1 --burn-in-s 0 --no-cpu-baseline > $O/pmc2_${TAG}${SUF}.log 2>&1
-    timeout 300 rocprofv3 --pmc WRITE_SIZE -d $O/pmc3_${TAG}${SUF} -o pmc -- python bench.py $PARGS --steps 3 --warmup 1 --burn-in-s 0 --no-cpu-baseline > $O/pmc3_${TAG}${SUF}.log 2>&1
+    timeout 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc2_${TAG}${SUF} -o pmc -- python bench.py --full $PARGS --steps 3 --warmup 1 --burn-in-s 0 --no-cpu-baseline > $O/pmc2_${TAG}${SUF}.log 2>&1
+    timeout 300 rocprofv3 --pmc WRITE_SIZE -d $O/pmc3_${TAG}${SUF} -o pmc -- python bench.py --full $PARGS --steps 3 --warmup 1 --burn-in-s 0 --no-cpu-baseline > $O/pmc3_${TAG}${SUF}.log 2>&1
     summ $O/pmc2_${TAG}${SUF} $O/${TAG}${SUF}_pmc_fetch.md
     summ $O/pmc3_${TAG}${SUF} $O/${TAG}${SUF}_pmc_write.md
     fdb=$(find $O/pmc2_${TAG}${SUF} -name '*.db' | head -1); wdb=$(find $O/pmc3_${TAG}${SUF} -name '*.db' | head -1)

@@ -3,9 +3,9 @@
 # ceiling under the power limit (scripts/micro/mfma_bf16_ceiling.hip) with hwmon power / clock sampled alongside.
 O=gpurun_out/r5a; mkdir -p $O
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-( timeout 600 python bench.py --gpus 2 --steps 5 --warmup 2 --burn-in-s 0.5 > $O/bench_gpus2.json 2> $O/bench_gpus2.err; echo "rc=$?" >> $O/bench_gpus2.err )
-timeout 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
-timeout 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --rays-per-gpu 128 > $O/bench_128.json 2> $O/bench_128.err
+( timeout 600 python bench.py --full --gpus 2 --steps 5 --warmup 2 --burn-in-s 0.5 > $O/bench_gpus2.json 2> $O/bench_gpus2.err; echo "rc=$?" >> $O/bench_gpus2.err )
+timeout 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+timeout 300 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --rays-per-gpu 128 > $O/bench_128.json 2> $O/bench_128.err
 # power / clock sampler: every hwmon card, 20 Hz, while the microbenchmark runs
 ( while true; do for h in /sys/class/drm/card*/device/hwmon/hwmon*; do
     p=$(cat $h/power1_average 2>/dev/null || cat $h/power1_input 2>/dev/null); f=$(cat $h/freq1_input 2>/dev/null)

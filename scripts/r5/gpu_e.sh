@@ -4,9 +4,9 @@
 O=gpurun_out/r5e; mkdir -p $O
 export HSA_ENABLE_IPC_MODE_LEGACY=0 TMPDIR=/tmp
 for X in 0 6 10 16 24 32; do
-  NRF_LIB_PATH=nerfies_amd/_lib/variants/libnerfies_amd_exp.so NRF_BCOST_MERGED=$X timeout 200 python bench.py --mode train_bf16 --steps 40 --warmup 5 --burn-in-s 1 --no-cpu-baseline > $O/sweep_$X.json 2> $O/sweep_$X.err
+  NRF_LIB_PATH=nerfies_amd/_lib/variants/libnerfies_amd_exp.so NRF_BCOST_MERGED=$X timeout 200 python bench.py --full --mode train_bf16 --steps 40 --warmup 5 --burn-in-s 1 --no-cpu-baseline > $O/sweep_$X.json 2> $O/sweep_$X.err
 done
-timeout 200 python bench.py --mode fullhd --bf16 --steps 40 --warmup 5 --burn-in-s 1 --no-cpu-baseline > $O/fullhd_bf16.json 2> $O/fullhd_bf16.err
+timeout 200 python bench.py --full --mode fullhd --bf16 --steps 40 --warmup 5 --burn-in-s 1 --no-cpu-baseline > $O/fullhd_bf16.json 2> $O/fullhd_bf16.err
 python - <<'P'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/r5e/*.json')):

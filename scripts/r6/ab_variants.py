@@ -10,7 +10,7 @@ for name in names:
   env = dict(os.environ)
   if name != 'product':
     env['NRF_LIB_PATH'] = os.path.join(ROOT, 'nerfies_amd', '_lib', 'variants', f'libnerfies_amd_{name}.so')
-  r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + mode + ['--steps', '30', '--warmup', '5', '--no-cpu-baseline', '--burn-in-s', '1'],
+  r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full'] + mode + ['--steps', '30', '--warmup', '5', '--no-cpu-baseline', '--burn-in-s', '1'],
                      env=env, capture_output=True, text=True, cwd=ROOT)
   try:
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])

@@ -18,7 +18,7 @@ for st in SETTINGS:
   row = {'chunk': ch, 'merged': mg, 'quad': qd, 'seg': sg, 'narrow': nr}
   for m in MODES:
     env = dict(os.environ, NRF_LIB_PATH=LIB, NRF_BCOST_CHUNK=str(ch), NRF_BCOST_MERGED=str(mg), NRF_BCOST_QUAD=str(qd), NRF_BCOST_SEG=str(sg), NRF_BCOST_CHUNK_NARROW=str(nr))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + m + ['--steps', '30', '--warmup', '5', '--no-cpu-baseline', '--burn-in-s', '1'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full'] + m + ['--steps', '30', '--warmup', '5', '--no-cpu-baseline', '--burn-in-s', '1'],
                        env=env, capture_output=True, text=True, cwd=ROOT)
     try:
       d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])

@@ -9,8 +9,8 @@ timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/r6f/smoke.tx
 bash scripts/gpu_profile_round.sh r06a > $O/r6f/profile_round.log 2>&1
 tail -5 $O/r6f/profile_round.log
 for R in 128 256 512; do
-  timeout 200 python bench.py --mode train_bf16 --rays-per-gpu $R --steps 200 --warmup 10 --burn-in-s 2 --no-cpu-baseline > $O/r06a_bench_train_bf16_$R.json 2>/dev/null
-  timeout 200 python bench.py --mode train_bf16 --rays-per-gpu $R --steps 200 --warmup 10 --burn-in-s 2 --no-cpu-baseline --graph > $O/r06a_bench_train_bf16_${R}_graph.json 2>/dev/null
+  timeout 200 python bench.py --full --mode train_bf16 --rays-per-gpu $R --steps 200 --warmup 10 --burn-in-s 2 --no-cpu-baseline > $O/r06a_bench_train_bf16_$R.json 2>/dev/null
+  timeout 200 python bench.py --full --mode train_bf16 --rays-per-gpu $R --steps 200 --warmup 10 --burn-in-s 2 --no-cpu-baseline --graph > $O/r06a_bench_train_bf16_${R}_graph.json 2>/dev/null
 done
 scripts/micro/_bin/elastic_bench > $O/r6f/elastic_bench.txt 2>&1
 scripts/micro/_bin/wgrad_bf16_bench > $O/r6f/wgrad_bf16_bench.txt 2>&1

@@ -13,7 +13,7 @@ from nerfies_amd import lib as L
 
 mode = sys.argv[1] if len(sys.argv) > 1 else 'vrig'
 extra = sys.argv[2:]
-sys.argv = ['bench.py', '--mode', mode, '--steps', '6', '--warmup', '3', '--burn-in-s', '0', '--no-cpu-baseline'] + extra
+sys.argv = ['bench.py', '--full', '--mode', mode, '--steps', '6', '--warmup', '3', '--burn-in-s', '0', '--no-cpu-baseline'] + extra
 with contextlib.redirect_stdout(io.StringIO()):
   bench.main()
 lib = L.load_library()

@@ -144,3 +144,33 @@ def test_cpu_baseline_reports_every_candidate(monkeypatch):
   assert r['kind'] == 'port' and r['unit'] == 'rays/s' and r['value'] > 0 and r['cores'] == r['cores_used'] <= r['cores_available']
   assert set(r['candidates']) == {'microbatch_grad_accumulation', 'full_batch_one_graph'}
   assert r['value'] == max(c['rays_per_s'] for c in r['candidates'].values()) and r['variant'] in r['candidates']
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+  """--dump-outputs: float32 (float64 kept), one .npy per name; over the size limit the large arrays become a fixed sample whose
+  positions are written next to it, the same positions in every run."""
+  import numpy as np
+  import torch
+  arrays = {'big': torch.arange(1000, dtype=torch.float32), 'half': torch.ones(10, dtype=torch.float16),
+            'f64': torch.zeros(3, dtype=torch.float64), 'stats.fine.loss_rgb': torch.tensor(0.5)}
+  w = bench.dump_outputs(str(tmp_path / 'small'), arrays)
+  assert w == {'big': 1000, 'half': 10, 'f64': 3, 'stats.fine.loss_rgb': 1}
+  assert sorted(os.listdir(tmp_path / 'small')) == ['big.npy', 'f64.npy', 'half.npy', 'stats.fine.loss_rgb.npy']
+  assert np.load(tmp_path / 'small' / 'half.npy').dtype == np.float32 and np.load(tmp_path / 'small' / 'f64.npy').dtype == np.float64
+  assert np.load(tmp_path / 'small' / 'stats.fine.loss_rgb.npy').shape == ()
+  for run in ('a', 'b'):
+    w = bench.dump_outputs(str(tmp_path / run), arrays, limit=2000)
+    assert w['big'] == 2000 // 4 // 12 and w['half'] == 10
+  files = [tmp_path / run for run in ('a', 'b')]
+  names = os.listdir(files[0])
+  assert sum(os.path.getsize(files[0] / n) for n in names) <= 2000 + 128 * len(names)   # + the .npy headers
+  idx = np.load(files[0] / 'big.index.npy')
+  assert idx.dtype == np.float64 and (np.diff(idx) > 0).all() and np.array_equal(idx, np.load(files[1] / 'big.index.npy'))
+  assert np.array_equal(np.load(files[0] / 'big.npy'), idx.astype(np.float32))   # arange: each value is its position
+
+
+def test_leaves_names_nested_stats():
+  import torch
+  t = torch.zeros(())
+  assert dict(bench._leaves({'coarse': {'loss/rgb': t}, 'fine': {'metric/psnr': t}, 'n': 3})) == {
+      'coarse.loss_rgb': t, 'fine.metric_psnr': t}

@@ -1,9 +1,11 @@
 """The gin subset (nerfies_amd/gin_lite.py) and the config dataclasses (nerfies_amd/configs.py).  gin-config is a
 third-party dependency of the reference and is not installed here, so these tests encode the semantics the presets
 rely on: includes, lazy macros, later-wins bindings, @configurable references, REQUIRED,
-skip_unknown, explicit kwargs beat bindings, operative config round trip.  When the reference tree is present (build
-container only) every preset under /root/reference/configs is also parsed and turned into schedules."""
+skip_unknown, explicit kwargs beat bindings, operative config round trip.  Every preset of the reference's configs/ is
+checked through the configuration its include chain resolves to, recorded in tests/golden/reference_presets.json
+(tests/golden/make_reference_presets.py)."""
 import dataclasses
+import json
 import os
 
 import pytest
@@ -155,9 +157,9 @@ def test_model_config_defaults_match_reference_dataclass():
   assert configs.EvalConfig().chunk == 8192 and configs.ExperimentConfig().random_seed == 12345
 
 
-REF_CONFIGS = '/root/reference/configs'
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIPPED = os.path.join(REPO, 'configs')
+REF_PRESETS = os.path.join(REPO, 'tests', 'golden', 'reference_presets.json')
 RUNNABLE = ('gpu_fullhd.gin', 'gpu_quarterhd.gin', 'gpu_quarterhd_4gpu.gin', 'gpu_vrig_paper.gin', 'test_local.gin', 'test_vrig.gin')
 
 
@@ -200,23 +202,26 @@ def test_every_shipped_preset_parses():
     _check_preset(f, m, t)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONFIGS), reason='reference tree only exists in the build container')
+def _reference_presets():
+  with open(REF_PRESETS) as fp:
+    return json.load(fp)
+
+
 def test_shipped_presets_equal_the_reference_presets():
   """Each shipped (flattened) preset resolves to EXACTLY the configuration the reference's include chain resolves to."""
+  ref_all = _reference_presets()
+  assert sorted(ref_all) == sorted(RUNNABLE)
   for f in RUNNABLE:
-    ours = _effective(os.path.join(SHIPPED, f), REPO)
-    ref = _effective(os.path.join('configs', f), '/root/reference')
+    ours = json.loads(json.dumps(_effective(os.path.join(SHIPPED, f), REPO)))   # tuples -> lists, as the record holds them
+    ref = ref_all[f]
     assert ours == ref, (f, {c: {k: (ours[c][k], ref[c][k]) for k in ours[c] if ours[c][k] != ref[c][k]} for c in ours})
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONFIGS), reason='reference tree only exists in the build container')
-def test_every_reference_preset_parses(monkeypatch):
-  monkeypatch.chdir('/root/reference')        # presets include both 'warp_defaults.gin' and 'configs/warp_defaults.gin'
-  for f in sorted(os.listdir(REF_CONFIGS)):
-    if f in ('defaults.gin', 'warp_defaults.gin'):      # "Do not run this directly": macros left for the includer
-      continue
+def test_every_reference_preset_parses():
+  """Every runnable preset of the reference (its configs/ without defaults.gin / warp_defaults.gin, which are only included)
+  as recorded: the config dataclasses accept it and it passes the preset checks."""
+  for f, rec in sorted(_reference_presets().items()):
     gin.clear_config()
-    gin.parse_config_files_and_bindings([os.path.join('configs', f)], None, skip_unknown=True)
-    m, t = configs.ModelConfig(), configs.TrainConfig()
-    configs.EvalConfig(), configs.ExperimentConfig()
+    m, t = configs.ModelConfig(**rec['ModelConfig']), configs.TrainConfig(**rec['TrainConfig'])
+    configs.EvalConfig(**rec['EvalConfig']), configs.ExperimentConfig(**rec['ExperimentConfig'])
     _check_preset(f, m, t)

@@ -130,7 +130,7 @@ def test_bench_line_through_rccl(tmp_path):
   env = dict(os.environ, BENCH_FORCE_DIST='1', MASTER_PORT='29519', HSA_ENABLE_IPC_MODE_LEGACY='0')
   for k in ('NCCL_DEBUG', 'NCCL_DEBUG_FILE', 'NCCL_DEBUG_SUBSYS'):   # an inherited console log would be left alone by the bench (no capture)
     env.pop(k, None)
-  r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--burn-in-s', '0',
+  r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '3', '--warmup', '1', '--burn-in-s', '0',
                       '--no-cpu-baseline', '--rays-per-gpu', '128'], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
   assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
   d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
@@ -149,7 +149,7 @@ def test_bench_gpus_2_launches_itself_and_checks_itself():
   env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
   for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'BENCH_FORCE_DIST', 'BENCH_DIST_BACKEND', 'BENCH_SAME_DEVICE'):
     env.pop(k, None)
-  r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--burn-in-s', '0'],
+  r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--steps', '3', '--warmup', '1', '--burn-in-s', '0'],
                      env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
   assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
   lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -172,13 +172,13 @@ def test_bench_gpus_2_launches_itself_and_checks_itself():
 
 
 def test_default_bench_line_carries_its_certificates():
-  """`python bench.py` as the driver runs it (fewer steps, no CPU baseline here): the ONE line carries the config-E parity record
+  """`python bench.py --full` (fewer steps, no CPU baseline here): the ONE line carries the config-E parity record
   (HIP vs float64 oracle, within the north star's 1e-3), the secondary lines of the other BASELINE configs and the sustained run,
   top-level and as a compact copy inside `config` (the driver's record keeps `config` whole)."""
   env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
   for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'BENCH_FORCE_DIST', 'BENCH_DIST_BACKEND', 'BENCH_SAME_DEVICE'):
     env.pop(k, None)
-  r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '5', '--warmup', '2', '--burn-in-s', '0.5', '--no-cpu-baseline',
+  r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '5', '--warmup', '2', '--burn-in-s', '0.5', '--no-cpu-baseline',
                       '--sustained-s', '1.0'], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
   assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
   d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
