@@ -382,6 +382,12 @@ int nrf_debug_wgrad_segments(nrf_handle h, const void* workspace, double* out, i
  * feature wave * 32 * NCB + 32 * cb + (lane & 31)  (NCB = 2 for the 256-wide trunk, 1 otherwise). */
 int nrf_debug_ws_offset(nrf_handle h, const char* name, int32_t level, int64_t* float_offset);
 
+/* Test aid: 64-bit FNV-1a digest of the last planned workspace layout -- every sub-buffer offset, the descriptor tables
+ * (pack, bf16 pack, wgrad groups and stream-K segments of both wgrad kernels, reduce) and their byte offsets, the tile
+ * counts and the launch sizes the plan decides.  Equal digests = the same plan.  Runs without a GPU (nrf_workspace_bytes*
+ * plans with the handle's default CU count then).  NRF_E_STATE before the handle's first plan. */
+int nrf_debug_plan_digest(nrf_handle h, uint64_t* digest);
+
 /* Tuning options of a handle (no reference counterpart: XLA picks its own tilings).  Must be set before the first
  * nrf_workspace_bytes / nrf_forward call that uses the handle with a given batch size, or between steps (the next call
  * re-plans; a stashed forward cannot be differentiated across a change: NRF_E_STATE).  Unknown option / value:

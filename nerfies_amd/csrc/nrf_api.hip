@@ -304,17 +304,7 @@ int nrf_warp_points(nrf_handle h, const float* params, const float* points, cons
   const WarpParamOffsets& wo = padded ? h->wpo : h->xwpo;   // else the caller's buffer: external offsets
   if (h->wp_pack.empty() || h->wp_pack_base != (int64_t)q.wpk_f) {
     h->wp_pack.clear();
-    const WarpParamOffsets& w = wo;
-    const WarpPackOffsets& wk = h->wpk;
-    auto addw = [&](int64_t src, int dst, int row0, int kvalid, int K) {
-      PackDesc d;
-      d.src_off = src; d.dst_off = (int64_t)q.wpk_f + dst; d.src_ld = WARP_W; d.src_row0 = row0; d.kvalid = kvalid; d.K = K;
-      d.ncb = 1; d.transposed = 0; d.nwaves = 4; d.nvalid = 1 << 30;
-      h->wp_pack.push_back(d);
-    };
-    addw(w.trunk_k[0], wk.fwd_L[0], 0, h->Win, h->PKw);
-    for (int l = 1; l < WARP_DEPTH; ++l) addw(w.trunk_k[l], wk.fwd_L[l], 0, WARP_W, WARP_W);
-    addw(w.trunk_k[WARP_SKIP], wk.fwd_L4b, WARP_W, h->Win, h->PKw);
+    warp_pack_descs(h, wo, (int64_t)q.wpk_f, false, h->wp_pack);
     h->wp_pack_base = (int64_t)q.wpk_f;
   }
   hipError_t e = hipMemcpyAsync(ws + q.desc_f, h->wp_pack.data(), h->wp_pack.size() * sizeof(PackDesc), hipMemcpyHostToDevice, st);
@@ -344,7 +334,6 @@ int nrf_set_option(nrf_handle h, int32_t option, int64_t value) {
     if (h->chain_rows_opt != (int)value) {
       h->chain_rows_opt = (int)value;
       h->stashed_ws = nullptr;   // a stash written under the old plan is not differentiated under the new one
-      h->uploaded_ws = nullptr;  // ... and the next call uploads the re-planned tables
     }
     return NRF_OK;
   }
@@ -353,7 +342,6 @@ int nrf_set_option(nrf_handle h, int32_t option, int64_t value) {
     if (h->bf16_wgrad_merge != (int)value) {
       h->bf16_wgrad_merge = (int)value;
       h->stashed_ws = nullptr;
-      h->uploaded_ws = nullptr;
     }
     return NRF_OK;
   }
@@ -387,7 +375,7 @@ int nrf_profile_read(nrf_handle h, nrf_profile_entry* out, int32_t* n) {
 
 int nrf_debug_ws_offset(nrf_handle h, const char* name, int32_t level, int64_t* float_offset) {
   if (!h || !name || !float_offset) return fail(NRF_E_NULL, "null");
-  if (level < 0 || level > 3 || h->plan.B < 0) return fail(NRF_E_STATE, "no workspace plan yet / bad level");
+  if (level < 0 || level > 3 || h->plan.key.B < 0) return fail(NRF_E_STATE, "no workspace plan yet / bad level");
   const LevelWs& L = h->plan.L[level];
   const struct { const char* n; size_t v; } tab[] = {
       {"st_pe", L.st_pe}, {"st_h", L.st_h}, {"st_bn", L.st_bn}, {"st_rgbh", L.st_rgbh}, {"dy_trunk", L.dy_trunk},
@@ -404,6 +392,48 @@ int nrf_debug_ws_offset(nrf_handle h, const char* name, int32_t level, int64_t* 
   for (const auto& t : tab)
     if (!strcmp(t.n, name)) { *float_offset = (int64_t)t.v; return NRF_OK; }
   return fail(NRF_E_SHAPE, "unknown workspace buffer name");
+}
+
+// FNV-1a over everything of the plan that reaches the device or a launch, field by field (LevelWs has padding; serial and the
+// host-side bf_stream_ok guard stay out)
+int nrf_debug_plan_digest(nrf_handle h, uint64_t* digest) {
+  if (!h || !digest) return fail(NRF_E_NULL, "null");
+  const WsPlan& p = h->plan;
+  if (p.key.B < 0) return fail(NRF_E_STATE, "no workspace plan yet");
+  uint64_t x = 0xcbf29ce484222325ull;
+  auto bytes = [&](const void* v, size_t n) {
+    for (size_t i = 0; i < n; ++i) x = (x ^ static_cast<const unsigned char*>(v)[i]) * 0x100000001b3ull;
+  };
+  auto put = [&](auto v) { bytes(&v, sizeof(v)); };
+  auto vec = [&](const auto& v) { put((uint64_t)v.size()); bytes(v.data(), v.size() * sizeof(v[0])); };
+  put(p.key.B); put(p.key.flags); put(p.key.bgN); put(p.key.elastic); put(p.key.chain_rows_opt); put(p.key.bf16_wgrad_merge);
+  put(p.total_floats);
+  for (int i = 0; i < 4; ++i) { put(p.S[i]); put(p.rows[i]); put(p.ntiles[i]); }
+  put(p.bwd32); put(p.bfw); put(p.tg_tiles_per); put(p.wgrad_nwg); put(p.bwgrad_nwg);
+  for (int i = 0; i < 4; ++i) put(p.nreduce_pass[i]);
+  for (size_t v : {p.tables, p.bf_desc, p.bfw_wpk, p.bfw_wpkT, p.iparams, p.igrad, p.cond, p.mse, p.zero_rgb, p.warp_wpk, p.bg_loss,
+                   p.bg_points, p.bg_ids, p.el_sums, p.el_coef, p.wr_sums, p.t_codes, p.t_dcodes, p.t_in, p.t_h, p.t_dpre, p.counters,
+                   p.timeline, p.seg_clock})
+    put(v);
+  for (const LevelWs& L : p.L) {
+    for (size_t v : {L.wpk, L.z, L.out4, L.rgb, L.depth, L.med, L.acc, L.weights, L.condterm, L.alpha_ct, L.dsig_ray, L.bf_wpk,
+                     L.bf_wpkT, L.b_pe, L.b_h, L.b_bn, L.b_rgbh, L.b_bits, L.b_dy, L.b_dbn, L.b_drgbh, L.b_dsmall})
+      put(v);
+    put(L.b_ngroups);
+    for (size_t v : {L.bw_in, L.bw_h, L.bw_bits, L.bw_dy, L.bw_dhead}) put(v);
+    put(L.bw_ngroups);
+    for (size_t v : {L.st_pe, L.st_h, L.st_bn, L.st_rgbh, L.bits_trunk, L.bits_rgbh, L.d_raw4, L.dy_trunk, L.dy_bn, L.dy_rgbh, L.dray,
+                     L.small_part, L.cond_grad, L.wpoints, L.points_raw, L.d_points, L.el_dw4, L.el_dv4, L.w_st_win, L.w_st_h,
+                     L.w_st_wv, L.w_bits, L.w_dy, L.w_dw4, L.w_dv4, L.w_small_part})
+      put(v);
+  }
+  for (size_t v : {p.pack_off_b, p.groups_off_b, p.reduce_off_b, p.segs_off_b, p.segbegin_off_b, p.emb_off_b, p.bgroups_off_b,
+                   p.bsegs_off_b, p.bsegbegin_off_b})
+    put(v);
+  vec(p.pack); vec(p.bfpack); vec(p.groups); vec(p.bgroups); vec(p.segs); vec(p.seg_begin); vec(p.bsegs); vec(p.bseg_begin);
+  vec(p.reduce);
+  *digest = x;
+  return NRF_OK;
 }
 
 int nrf_debug_wgrad_segments(nrf_handle h, const void* workspace, double* out, int32_t* n) {

@@ -61,9 +61,21 @@ struct LevelWs {   // float offsets from the workspace base, per level (0 = coar
   size_t w_st_win, w_st_h, w_st_wv, w_bits, w_dy, w_dw4, w_dv4, w_small_part;
 };
 
+// What a workspace plan is built for: a handle re-plans (and re-uploads the tables) when any of it changes
+struct PlanKey {
+  int B = -1;                   // rays
+  uint32_t flags = 0;           // plan_flags() of the call
+  int bgN = 0;                  // background points
+  int elastic = 0;              // the elastic regulariser's buffers
+  int chain_rows_opt = 0, bf16_wgrad_merge = 0;   // the handle's options
+  bool operator==(const PlanKey& o) const {
+    return B == o.B && flags == o.flags && bgN == o.bgN && elastic == o.elastic && chain_rows_opt == o.chain_rows_opt &&
+           bf16_wgrad_merge == o.bf16_wgrad_merge;
+  }
+};
+
 struct WsPlan {
-  int B = -1;
-  uint32_t flags = 0;
+  PlanKey key;
   uint64_t serial = 0;   // identity of this layout: a stash written under one plan must not be differentiated under another
   int S[4], rows[4], ntiles[4];
   size_t tables;        // byte region at the start: PackDesc[], WgradGroup[], ReduceDesc[]
@@ -83,7 +95,7 @@ struct WsPlan {
   std::vector<int> bseg_begin;
   size_t bgroups_off_b = 0, bsegs_off_b = 0, bsegbegin_off_b = 0;
   int bwgrad_nwg = 0;
-  size_t cond, mse, zero_rgb, slabs;
+  size_t cond, mse, zero_rgb;
   size_t warp_wpk;      // packed SE3 trunk weights (shared by both levels)
   size_t bg_loss;       // [64] background-loss accumulator
   size_t bg_points = 0, bg_ids = 0;   // [bgN][3] noised points / [bgN] ids drawn by the library
@@ -98,18 +110,13 @@ struct WsPlan {
                                      // (background batch), 3 (Jacobian tangents) add into leaves shared with earlier passes
   LevelWs L[4];          // 0 coarse, 1 fine, 2 background points (SE3 field only, training.py:117-135),
                          // 3 tangent pass of the coarse warp Jacobian (elastic regulariser, 3 x coarse tiles)
-  int elastic = 0;       // plan built with the elastic regulariser's buffers
   bool bwd32 = false;    // training plan: the fp32 NeRF reverse chain runs on 32-row tiles (mlp_chain32.hip); decides the
                          // number of bias partials the reduce table sums
-  int chain_rows_opt = 0;   // the handle's options the plan was built under
-  int bf16_wgrad_merge = 0;
   int tg_tiles_per = 0;  // primal tiles one tangent pass covers (elastic: coarse level; Jacobian output: the larger level)
-  int bgN = 0;           // number of background points the plan was built for
   size_t total_floats;
   std::vector<PackDesc> pack;
   std::vector<WgradGroup> groups;
   std::vector<ReduceDesc> reduce;
-  int ntasks = 0;
 };
 
 
@@ -200,13 +207,10 @@ struct nrf_handle_s {
   nrf::api::WsPlan plan;
   // identity of the tables last uploaded to a workspace, and of the last stashed forward
   void* uploaded_ws = nullptr;
+  nrf::api::PlanKey uploaded_key;
   int xdepth = nrf::TRUNK_DEPTH, xskip = nrf::SKIP_LAYER;   // the caller's trunk (<= 8 layers; its skip index or -1): nrf_create
   int emap[nrf::TRUNK_DEPTH];                          // internal trunk layer -> the caller's layer, or -1 (identity layer)
   int wxdepth = nrf::WARP_DEPTH, wxwidth = nrf::WARP_W;     // the caller's warp trunk (warp_kwargs trunk_depth / trunk_width)
-  int uploaded_B = -1;
-  uint32_t uploaded_flags = 0;
-  int uploaded_bgN = 0;
-  int uploaded_elastic = 0;
   void* stashed_ws = nullptr;
   uint64_t stashed_plan = 0;   // WsPlan::serial of the stashed forward
   int stashed_B = -1;
@@ -227,6 +231,7 @@ int* tile_counter_or_null(float* base, int idx);
 uint32_t plan_flags(uint32_t flags);
 bool chain32_for(const nrf_handle_s* h, int ntiles, bool reverse = false);
 void build_plan(nrf_handle h, int B, uint32_t flags, int bgN = 0, int elastic = 0);
+void warp_pack_descs(const nrf_handle_s* h, const WarpParamOffsets& w, int64_t base, bool transposed, std::vector<PackDesc>& out);
 int upload_tables(nrf_handle h, float* ws, hipStream_t stream);
 void query_device(nrf_handle h);
 

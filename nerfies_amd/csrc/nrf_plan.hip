@@ -172,7 +172,6 @@ void build_pack_offsets(nrf_handle h) {
   }
 }
 
-// Lays out the workspace for B rays and (re)builds the descriptor tables.
 // Measured (r01): pulling tiles from a global counter is 4-6 % SLOWER than the static round-robin split for the
 // chain kernels (fine forward 1.99 vs 1.87 ms) although it removes the tail where the younger workgroup of a CU
 // runs alone -- so static is the default and NRF_DYNAMIC_TILES=1 keeps the other path testable.
@@ -223,34 +222,271 @@ bool chain32_for(const nrf_handle_s* h, int ntiles, bool reverse) {
   return !reverse && ntiles < AUTO32_FWD_BELOW_TILES_PER_CU * h->num_cus;
 }
 
-void build_plan(nrf_handle h, int B, uint32_t flags, int bgN, int elastic) {
+// fp32 fragment images of the SE3 trunk (warp_chain.hip), packed from the leaves at `w` to base + h->wpk: the forward layers and,
+// with `transposed`, the reverse chain's W^T of layers 1..5
+void warp_pack_descs(const nrf_handle_s* h, const WarpParamOffsets& w, int64_t base, bool transposed, std::vector<PackDesc>& out) {
+  const WarpPackOffsets& wk = h->wpk;
+  auto add = [&](int64_t src, int dst, int row0, int kvalid, int K, int tr) {
+    PackDesc q;
+    q.src_off = src; q.dst_off = base + dst; q.src_ld = WARP_W; q.src_row0 = row0; q.kvalid = kvalid; q.K = K; q.ncb = 1;
+    q.transposed = tr; q.nwaves = 4; q.nvalid = 1 << 30;
+    out.push_back(q);
+  };
+  add(w.trunk_k[0], wk.fwd_L[0], 0, h->Win, h->PKw, 0);
+  for (int l = 1; l < WARP_DEPTH; ++l) add(w.trunk_k[l], wk.fwd_L[l], 0, WARP_W, WARP_W, 0);
+  add(w.trunk_k[WARP_SKIP], wk.fwd_L4b, WARP_W, h->Win, h->PKw, 0);
+  for (int l = 1; l < WARP_DEPTH && transposed; ++l) add(w.trunk_k[l], wk.bwd_LT[l], 0, WARP_W, WARP_W, 1);
+}
+
+namespace {
+
+// calibration overrides of the wgrad cost models (scripts/wgrad_calib.py, scripts/r6/cost_sweep.py): experiment builds only
+double env_cost(const char* name, double dflt) {
+#ifdef NRF_EXPERIMENT
+  if (const char* e = getenv(name)) return atof(e);
+#endif
+  (void)name;
+  return dflt;
+}
+
+// An operand of an fp32 wgrad group (wgrad.hip): a stash of the level at *off + add (read once the layout is known), SRC_*
+// layout, 32-feature blocks and floats per 64-row tile.  {} = none: the vector-column groups have no dY.
+struct Operand { int kind; size_t* off; size_t add; int blocks, stride; };
+Operand frag256(size_t* off, size_t add = 0) { return {SRC_FRAG256, off, add, 8, FRAG_TILE_256}; }
+Operand frag128(size_t* off, size_t add = 0) { return {SRC_FRAG128, off, add, 4, FRAG_TILE_128}; }
+Operand plain(size_t* off, int K) { return {SRC_PLAIN, off, 0, (K + 31) / 32, (K + 31) / 32 * 32 * TILE_ROWS}; }   // whole 32-feature blocks
+
+// fp32 wgrad group: leaf [kvalid][cols] (+)= X^T dY over the tiles of level lv, or -- vec > 0, the narrow heads on the VALU --
+// X^T v, v = .w (vec 1) / .xyz (vec 3) of the vec4 rows at vecoff (nullptr: the level's d_raw4); vecoff2 / dst2: a second
+// vector column set against the same X
+struct GroupSpec {
+  int lv, accumulate;
+  Operand x, dy;
+  int kvalid, cols, vec;
+  int64_t dst;
+  size_t* vecoff;
+  size_t* vecoff2;
+  int64_t dst2;
+};
+
+// Cost of one 64-row tile of an fp32 group, in units of a full 256x256 layer tile; the narrow groups are staging/latency bound,
+// so they are charged more than their MFMA share.
+// measured with scripts/wgrad_calib.py / wgrad_calib_vrig.py (per-segment wall clocks, least squares), relative to a
+// 256x256 tile; round 3 (asm LDS-DMA + 160 KiB ring: the narrow groups are no longer latency-bound): 8x8 = 14.8 us; round 6 (SGPR piece
+// tables, refill behind the MFMAs): re-fitted on config A and the vrig shape (gpurun_out/r6h: every narrow type ~6 % cheaper relative
+// to 8x8, a segment 0.4-0.5 tiles; the two-vector SE3 heads 0.155: the fit's Kb = 4, Nb = 0 row mixes them with the rgb logits)
+double tile_cost(const GroupSpec& sp) {
+  const double c_vec256 = env_cost("NRF_COST_VEC256", 0.106), c_vec128 = env_cost("NRF_COST_VEC128", 0.094),
+               c_vec128x2 = env_cost("NRF_COST_VEC128X2", 0.155),   // SE3 heads: two vectors against one pass over h6
+               c_pe = env_cost("NRF_COST_PE", 0.270),               // 2 x 8 blocks: posenc rows of the NeRF trunk
+               c_rgbh = env_cost("NRF_COST_RGBH", 0.516),           // 8 x 4
+               c_44 = env_cost("NRF_COST_44", 0.266),               // 4 x 4: SE3 trunk layers
+               c_pe128 = env_cost("NRF_COST_PE128", 0.141);         // 2 x 4: SE3 trunk input rows
+  const int Kb = sp.x.blocks, Nb = sp.dy.blocks;
+  if (Nb == 0) return Kb == 8 ? c_vec256 : sp.vecoff2 ? c_vec128x2 : c_vec128;   // vector columns only (VALU + HBM stream)
+  if (Nb == 8) return Kb >= 5 ? 1.0 : c_pe;
+  return Kb >= 5 ? c_rgbh : Kb >= 3 ? c_44 : c_pe128;
+}
+
+// A source of a bf16 wgrad operand (wgrad_bf16.hip): a bf16 stash at *off + add dwords, `blocks` blocks of it per 32-sample group.
+// A second source (BSpec x2 / dy2) supplies the operand's last blocks out of a buffer of `stride` blocks per group.
+struct BfSrc { size_t* off; size_t add; int blocks; int stride = 0; };
+// A leaf out of a group's slab: leaf [rows][cols] <- slab[0:rows][col0:col0 + cols]; a bias leaf: column sums [col0:col0 + cols] of dY
+struct Leaf { int64_t off; int cols, col0; };
+
+// bf16 wgrad group over the 32-sample groups of level lv (ngroups: 0 = the MLP level's), added in reduce pass `accu`
+struct BSpec {
+  int lv, accu, ngroups;
+  BfSrc x, dy, x2, dy2;   // X = [x | x2], dY = [dy | dy2]
+  int rows;               // valid rows of X
+  Leaf w[2], b[2];        // weight and bias leaves, off < 0: none
+};
+
+// Cost of one 32-sample group of a bf16 group: HBM-bound, cost = blocks streamed.
+// A chunk costs (Kb + Nb) + a fixed term, in block units (2 KiB streamed).  Round 2 measured + 12 on config A (the per-chunk
+// barrier and HBM latency worth 24 KiB of streaming: wgrad 0.87 ms with a pure byte model, 0.61 ms with that one).  Round 6,
+// after the copies moved to per-segment SGPR tables (wgrad_bf16.hip): ALONE every shape streams 5.6-6.4 TB/s, i.e. cost ~ bytes
+// (scripts/micro/wgrad_bf16_bench.hip), but IN the mixed launch a byte-proportional model is 3-10 % slower than + 12, and the
+// narrow shapes (Kb + Nb <= 8: the SE3 trunk's 16 / 12 KiB chunks) are best charged + 8: swept on config D / vrig / A (bf16) at
+// narrow = 12 / 8 / 5 / 2: 1.19 / 1.13 / 1.18 / 1.38 ms, 0.92 / 0.84 / 0.90 / 1.03 ms, 0.456 / 0.460 / 0.495 / 0.618 ms
+// (profiles/r06_experiments.md section 3)
+double bcost(const BSpec& sp) {
+  const double bc_chunk = env_cost("NRF_BCOST_CHUNK", 12.0);   // per-chunk fixed cost (barrier + issue), in block units
+  // the two merged shapes (10 x 8, 8 x 9: ten accumulator blocks per wave, five copies per wave and chunk) cost more per chunk
+  // than their bytes: with a byte-proportional cost the kernel was 10 % SLOWER although it fetched 10 % less (the workgroups
+  // inside the merged groups ran ~1.35 x their quota); swept on the GPU at +0 / 6 / 10 / 16 / 24 / 32 units: 0.555 / 0.508 /
+  // 0.500 / 0.520 / 0.527 / 0.543 ms
+  const double bc_merged = env_cost("NRF_BCOST_MERGED", 10.0);
+  const double bc_chunk_narrow = env_cost("NRF_BCOST_CHUNK_NARROW", 8.0);   // ... of the 4 x 4 / 2 x 4 shapes (SE3 trunk: 16 / 12 KiB chunks)
+  const double bc_quad = env_cost("NRF_BCOST_QUAD", 0.0);   // per accumulator block (Kb x Nb): the MFMA / operand-read side of a chunk
+  const int Kb = sp.x.blocks + sp.x2.blocks, Nb = sp.dy.blocks + sp.dy2.blocks;   // the second sources' blocks included
+  return (double)(Kb + Nb) + (Kb + Nb <= 8 ? bc_chunk_narrow : bc_chunk) + bc_quad * Kb * Nb + ((sp.x2.blocks || sp.dy2.blocks) ? bc_merged : 0.0);
+}
+
+// Stream-K partition of the wgrad work: equal cost per workgroup, one workgroup per CU.  Group gi is ntiles[gi] tiles of cost[gi];
+// every workgroup and every group boundary opens a segment, at cost `seg`.  Fills segs / seg_begin (workgroup w runs segments
+// [seg_begin[w], seg_begin[w + 1])) and returns the number of segments (slab partials) of each group.
+std::vector<int> stream_k(const std::vector<double>& cost, const std::vector<int>& ntiles, double seg, int nwg,
+                          std::vector<WgradSegment>& segs, std::vector<int>& seg_begin) {
+  std::vector<int> nsplit(cost.size(), 0);
+  double total = 0;
+  for (size_t gi = 0; gi < cost.size(); ++gi) total += cost[gi] * ntiles[gi];
+  total += seg * (nwg + (double)cost.size());
+  const double quota = total / nwg;
+  seg_begin.assign(1, 0);
+  int w = 0;
+  double room = quota;
+  for (size_t gi = 0; gi < cost.size(); ++gi) {
+    const double c = cost[gi];
+    const int nt = ntiles[gi];
+    for (int t0 = 0; t0 < nt;) {
+      int take_n = (int)floor((room - seg) / c + 1e-9);
+      if (take_n <= 0 && w < nwg - 1) {   // this workgroup is full: move on
+        seg_begin.push_back((int)segs.size());
+        ++w; room += quota;
+        continue;
+      }
+      if (take_n <= 0 || w == nwg - 1 || take_n > nt - t0) take_n = nt - t0;   // the last workgroup absorbs rounding leftovers
+      segs.push_back({(int)gi, t0, t0 + take_n, nsplit[gi]++});
+      t0 += take_n;
+      room -= seg + take_n * c;
+    }
+  }
+  while ((int)seg_begin.size() < nwg + 1) seg_begin.push_back((int)segs.size());
+  return nsplit;
+}
+
+// The chunk table of one bf16 weight stream (mlp_bf16.hip / warp_bf16.hip; x3: mlp_bf16x3.hip / warp_bf16x3.hip) from float offset
+// `base`.  One GEMM = nblocks / pb panels; a panel (chunk) = [row][block of the panel][lane] x 16 B, rows = [bias row,] then the
+// k-step rows of each input part.  x3: the same GEMM sequence with every k-step row of a forward stream doubled (W_hi, W_lo); the
+// kernel cuts a panel's rows into chunks itself.
+struct Stream {
+  size_t base, at;   // stream base, floats emitted so far
+  int tr;            // 1: a reverse (dgrad) stream, A = W as stored, [m = the layer's input feature][k = its output feature]
+  bool x3;
+  std::vector<RcPackDesc>& out;
+  // an input part: leaf, ld, first row, valid K, input blocks; leaf2 / split: the second of two leaves side by side (SE3 heads w | v)
+  struct Part { int64_t leaf; int ld, row0, krows, nin; int64_t leaf2 = -1; int split = 0; };
+  // bias: the bias row's leaf, -1 none, -2 a zero row where the kernel runs a bias-style k-step this model does not use;
+  // bias2 / bsplit: as leaf2 / split
+  void gemm(int pb, int nblocks, int ncols, int64_t bias, std::initializer_list<Part> parts, int64_t bias2 = -1, int bsplit = 0) {
+    for (int pn = 0; pn < nblocks / pb; ++pn) {
+      int row = 0;
+      auto emit = [&](int kind, int64_t src, int64_t src2, int split, int ld, int row0, int krows, int nrows) {
+        RcPackDesc e;
+        memset(&e, 0, sizeof(e));
+        e.src_off = src; e.dst_off = (long long)(base + at + (size_t)row * pb * 256); e.kind = kind; e.src_ld = ld; e.row0 = row0;
+        e.krows = krows; e.ncols = ncols; e.ngroups = nrows; e.nout = pb; e.nout_panel = pb; e.o0 = 0; e.transposed = tr;
+        e.oblk0 = pn * pb; e.src_off2 = src2 >= 0 ? src2 : 0; e.split = src2 >= 0 ? split : 0; e.x3 = x3 && !tr;
+        out.push_back(e);
+        row += nrows;
+      };
+      if (bias >= 0) emit(1, bias, bias2, bsplit, 0, 0, 0, 1);
+      else if (bias == -2) emit(2, 0, -1, 0, 0, 0, 0, 1);
+      for (const Part& q : parts) emit(0, q.leaf, q.leaf2, q.split, q.ld, q.row0, q.krows, (x3 && !tr ? 2 : 1) * 2 * q.nin);
+      at += (size_t)row * pb * 256;
+    }
+  }
+};
+
+ReduceDesc reduce_desc(int64_t dst, int dst_ld, int rows, int cols, int64_t src, int src_ld, int64_t part_stride, int nparts,
+                       int accumulate = 0) {
+  ReduceDesc r;
+  memset(&r, 0, sizeof(r));
+  r.dst_off = dst; r.dst_ld = dst_ld; r.rows = rows; r.cols = cols; r.accumulate = accumulate;
+  r.src_off = src; r.src_ld = src_ld; r.part_stride = part_stride; r.nparts = nparts;
+  return r;
+}
+
+// The descriptor tables at ws + plan.tables in layout order, each sized from what was built (round 2 reserved 64 pack / 192
+// reduce descriptors without a check) plus its slack: one spare element, or 256 bytes (wgrad groups and segments).  The embed
+// table is the handle's, uploaded only for a model that runs on its padded image.
+struct Table {
+  size_t* off_b;
+  const void* data;
+  size_t bytes, slack;
+  const char* what;
+  bool upload;
+};
+template <class T> Table table(size_t* off_b, const std::vector<T>& v, bool spare, const char* what, bool upload = true) {
+  return {off_b, v.data(), v.size() * sizeof(T), spare ? sizeof(T) : 256, what, upload};
+}
+std::vector<Table> tables_of(nrf_handle h) {
   WsPlan& p = h->plan;
-  flags = plan_flags(flags);
-  if (p.B == B && p.flags == flags && p.bgN == bgN && p.elastic == elastic && p.chain_rows_opt == h->chain_rows_opt &&
-      p.bf16_wgrad_merge == h->bf16_wgrad_merge) return;
-  const nrf_model_desc& d = h->d;
-  const bool train = flags & NRF_FLAG_TRAIN;
-  const bool bft = train && (flags & NRF_FLAG_BF16);   // bf16 training: the NeRF MLPs stash / differentiate in bfloat16
-  const bool x3 = !train && (flags & NRF_FLAG_BF16X3);  // split-bf16 inference chains (mlp_bf16x3.hip)
-  const bool jac = (flags & NRF_FLAG_WARP_JACOBIAN) && h->warp;   // tangent pass in an inference plan
-  const bool bfw = bft && h->warp && !(flags & NRF_FLAG_WARP_F32);   // ... and so does the SE3 trunk (warp_bf16.hip)
-  const bool wstash = (train && !bfw) || jac;                      // the fp32 warp kernels keep their input / sign-bit stash
-  static std::atomic<uint64_t> next_serial{1};   // handles may be planned from several host threads
-  p = WsPlan();
-  p.serial = next_serial++;
-  p.B = B;
-  p.flags = flags;
-  p.bgN = bgN;
+  return {table(&p.pack_off_b, p.pack, true, "upload pack table"), table(&p.groups_off_b, p.groups, false, "upload wgrad table"),
+          table(&p.reduce_off_b, p.reduce, true, "upload reduce table"), table(&p.segs_off_b, p.segs, false, "upload wgrad segments"),
+          table(&p.segbegin_off_b, p.seg_begin, true, "upload wgrad segment index"),
+          table(&p.emb_off_b, h->emb, true, "upload embed table", h->embed),
+          table(&p.bgroups_off_b, p.bgroups, false, "upload bf16 wgrad table"),
+          table(&p.bsegs_off_b, p.bsegs, false, "upload bf16 wgrad segments"),
+          table(&p.bsegbegin_off_b, p.bseg_begin, true, "upload bf16 wgrad segment index")};
+}
+
+// build_plan's stages and what they hand on
+struct Planner {
+  nrf_handle h;
+  WsPlan& p;
+  const nrf_model_desc& d;
+  const bool train;
+  const bool bft;      // bf16 training: the NeRF MLPs stash / differentiate in bfloat16
+  const bool x3;       // split-bf16 inference chains (mlp_bf16x3.hip)
+  const bool jac;      // tangent pass in an inference plan
+  const bool bfw;      // ... and so does the SE3 trunk (warp_bf16.hip)
+  const bool wstash;   // the fp32 warp kernels keep their input / sign-bit stash
+  const int G;
+  std::vector<GroupSpec> specs;         // fp32 wgrad groups
+  std::vector<BSpec> bspecs;            // bf16 wgrad groups
+  std::vector<int> nsplit, bnsplit;     // segments of each group
+  std::vector<ReduceDesc> by_pass[4];   // reduce descriptors by pass (ReduceDesc::accumulate)
+  size_t o = 0;                         // floats laid out
+
+  Planner(nrf_handle h_, uint32_t flags)
+      : h(h_), p(h_->plan), d(h_->d), train(flags & NRF_FLAG_TRAIN), bft(train && (flags & NRF_FLAG_BF16)),
+        x3(!train && (flags & NRF_FLAG_BF16X3)), jac((flags & NRF_FLAG_WARP_JACOBIAN) && h_->warp),
+        bfw(bft && h_->warp && !(flags & NRF_FLAG_WARP_F32)), wstash((train && !bfw) || jac), G(h_->num_cus) {}
+  size_t take(size_t n) { size_t r = o; o = align_up(o + n, ALIGN_F); return r; }
+  void add_reduce(const ReduceDesc& r) { by_pass[r.accumulate].push_back(r); }
+  // fp32 groups: leaf [kvalid][cols] <- X^T dY; the narrow heads: leaf [kvalid][vec] <- X^T v
+  void gemm(int lv, int accu, Operand x, int kvalid, Operand dy, int64_t dst, int cols) {
+    specs.push_back({lv, accu, x, dy, kvalid, cols, 0, dst, nullptr, nullptr, -1});
+  }
+  void heads(int lv, int accu, Operand x, int kvalid, int vec, int64_t dst, size_t* vecoff = nullptr, size_t* vecoff2 = nullptr,
+             int64_t dst2 = -1) {
+    specs.push_back({lv, accu, x, Operand{}, kvalid, vec, vec, dst, vecoff, vecoff2, dst2});
+  }
+  // bf16 groups: leaf [rows][cols] <- (X^T dY)[:, col0:], bias leaf (-1: none) <- column sums of dY
+  BSpec& bgemm(int lv, BfSrc x, BfSrc dy, int64_t leaf, int rows, int cols, int64_t bias, int col0 = 0) {
+    bspecs.push_back({lv, 0, 0, x, dy, {}, {}, rows, {{leaf, cols, col0}, {-1, 0, 0}}, {{bias, cols, 0}, {-1, 0, 0}}});
+    return bspecs.back();
+  }
+
+  void shapes();
+  void wgrad_specs();
+  void fp32_specs(int lv);
+  void warp_specs(int lv, int accu);
+  void bf16_specs(int lv);
+  void bf16_warp_specs(int lv, int accu, bool tangent);
+  void cut_wgrad();
+  void weight_streams();
+  void buffers();
+  void alloc_warp(LevelWs& L, size_t nt);
+  void pack_descs();
+  void fp32_groups();
+  void bf16_groups();
+  void bias_reduces();
+  void chain_reduces();
+  void tables();
+};
+
+void Planner::shapes() {
+  const PlanKey& k = p.key;
   p.bfw = bfw;
-  p.elastic = elastic;
-  p.chain_rows_opt = h->chain_rows_opt;
-  p.bf16_wgrad_merge = h->bf16_wgrad_merge;
   p.S[0] = d.num_coarse_samples;
   p.S[1] = d.num_coarse_samples + d.num_fine_samples;
   p.S[BG] = 1;
   p.S[TG] = 1;
   for (int lv = 0; lv < 3; ++lv) {
-    p.rows[lv] = lv == BG ? bgN : B * p.S[lv];
+    p.rows[lv] = lv == BG ? k.bgN : k.B * p.S[lv];
     p.ntiles[lv] = (p.rows[lv] + TILE_ROWS - 1) / TILE_ROWS;
   }
   {   // the reverse chain's tiling is part of the plan (the reduce table sums one bias partial per workgroup of that launch);
@@ -259,428 +495,239 @@ void build_plan(nrf_handle h, int B, uint32_t flags, int bgN, int elastic) {
     for (int q = 0; q < h->nlevels; ++q) nt_mlp += p.ntiles[q];
     p.bwd32 = train && !bft && !h->warp && chain32_for(h, nt_mlp, true);
   }
-  p.tg_tiles_per = jac ? p.ntiles[h->nlevels - 1] : elastic ? p.ntiles[0] : 0;   // Jacobian output: levels run one after the other
+  p.tg_tiles_per = jac ? p.ntiles[h->nlevels - 1] : k.elastic ? p.ntiles[0] : 0;   // Jacobian output: levels run one after the other
   p.ntiles[TG] = 3 * p.tg_tiles_per;
   p.rows[TG] = p.ntiles[TG] * TILE_ROWS;
-  const int G = h->num_cus;
+}
 
-  // ---- wgrad groups (training) ----
-  struct GroupSpec { int lv; int xk; size_t* xoff; int xstride; int kvalid; int Kb; int yk; size_t* yoff; int ystride; int Nb;
-                     int vec; int64_t dst; int dst_ld; int rows; int cols; int units; size_t xadd, yadd;
-                     size_t* vecoff = nullptr; int accumulate = 0;
-                     size_t* vecoff2 = nullptr; int64_t dst2 = -1; };   // second vector column set against the same X
-  std::vector<GroupSpec> specs;
-  const int Kb_pe = (h->PK + 31) / 32;          // posenc stash tiles hold whole 32-feature blocks
-  const int PKS = Kb_pe * 32;
-  // SE3 trunk + heads of level `lv` (coarse / fine samples, or the background-point batch)
-  auto add_warp_groups = [&](int lv, int accu) {
-    LevelWs& L = p.L[lv];
-    const WarpParamOffsets& w = h->wpo;
-    const size_t wl = (size_t)p.ntiles[lv] * FRAG_TILE_128;
-    const int Kb_in = (h->PKw + 31) / 32;
-    auto push = [&](GroupSpec g) { g.accumulate = accu; specs.push_back(g); };
-    for (int l = 0; l < WARP_DEPTH; ++l) {
-      if (l == 0) {
-        push({lv, SRC_PLAIN, &L.w_st_win, Kb_in * 32 * TILE_ROWS, h->Win, Kb_in, SRC_FRAG128, &L.w_dy, FRAG_TILE_128, 4, 0,
-              w.trunk_k[0], WARP_W, h->Win, WARP_W, Kb_in * 4, 0, 0});
-      } else {
-        push({lv, SRC_FRAG128, &L.w_st_h, FRAG_TILE_128, WARP_W, 4, SRC_FRAG128, &L.w_dy, FRAG_TILE_128, 4, 0,
-              w.trunk_k[l], WARP_W, WARP_W, WARP_W, 16, (size_t)(l - 1) * wl, (size_t)l * wl});
-        if (l == WARP_SKIP)
-          push({lv, SRC_PLAIN, &L.w_st_win, Kb_in * 32 * TILE_ROWS, h->Win, Kb_in, SRC_FRAG128, &L.w_dy, FRAG_TILE_128, 4, 0,
-                w.trunk_k[l] + (int64_t)WARP_W * WARP_W, WARP_W, h->Win, WARP_W, Kb_in * 4, 0, (size_t)l * wl});
-      }
-    }
-    GroupSpec gw = {lv, SRC_FRAG128, &L.w_st_h, FRAG_TILE_128, WARP_W, 4, 0, nullptr, 0, 0, 3,
-                    w.w_k, 3, WARP_W, 3, 6, (size_t)(WARP_DEPTH - 1) * wl, 0};
-    gw.vecoff = &L.w_dw4;
-    gw.vecoff2 = &L.w_dv4; gw.dst2 = w.v_k;   // both heads read h6: one pass over its stash
-    push(gw);
-  };
-  // bf16 training: the NeRF MLP groups go to the bf16 wgrad kernel (X / dY = bf16 stash buffers of Kb / Nb blocks per
-  // 32-sample group); bias = the group also owns the bias gradient (column sums of its dY)
-  struct BSpec { int lv; size_t* xoff; size_t xadd; int Kb; size_t* yoff; size_t yadd; int Nb;
-                 int64_t dst; int dst_ld, rows, cols, col0;          // weight leaf <- slab[0:rows][col0:col0+cols]
-                 int64_t bias_dst; int bias_cols;                     // bias leaf <- column sums [0:bias_cols], or -1
-                 int64_t bias2_dst; int bias2_col0;                   // a second bias leaf (alpha: column 3; SE3 v head: columns 3..5), or -1
-                 int bias2_cols = 1; int accu = 0; int ngroups = 0;   // reduce pass the leaf is added in; groups (0: the MLP level's)
-                 int64_t dst2 = -1; int col20 = 0;                    // a second weight leaf from the same slab (SE3 v head), or -1
-                 int dst2_ld = 0, dst2_cols = 0;                      // ... of its own width (0: as the first leaf)
-                 // an operand assembled from two stash buffers (WgradGroup x2_off / dy2_off): the last Kb2 / Nb2 blocks
-                 size_t* x2off = nullptr; int Kb2 = 0, x2_blocks = 0; size_t* y2off = nullptr; int Nb2 = 0, y2_blocks = 0; };
-  std::vector<BSpec> bspecs;
-  if (bft) {
-    for (int lv = 0; lv < h->nlevels; ++lv) {
-      LevelWs& L = p.L[lv];
-      const MlpParamOffsets& po = h->po[lv];
-      L.b_ngroups = (p.rows[lv] + 255) / 256 * 8;
-      const size_t layer = (size_t)L.b_ngroups * 8 * BF_BLOCK_DW;
-      auto bpush = [&](size_t* xoff, size_t xadd, int Kb, size_t* yoff, size_t yadd, int Nb, int64_t dst, int dst_ld, int rows, int cols,
-                       int col0, int64_t bias_dst, int bias_cols, int64_t bias2_dst = -1, int bias2_col0 = 0) {
-        bspecs.push_back({lv, xoff, xadd, Kb, yoff, yadd, Nb, dst, dst_ld, rows, cols, col0, bias_dst, bias_cols, bias2_dst, bias2_col0});
-      };
-      for (int l = 0; l < TRUNK_DEPTH; ++l) {
-        if (l == 0) {
-          bpush(&L.b_pe, 0, 2, &L.b_dy, 0, 8, po.trunk_k[0], 256, h->P, 256, 0, po.trunk_b[0], 256);
-        } else {
-          if (l == d.nerf_skip_layer && h->bf16_wgrad_merge) {
-            // (NRF_OPT_BF16_WGRAD_MERGE) the skip layer's kernel is [256 + P, 256]: rows 0..255 multiply h4, rows 256.. the posenc (modules.py:47-48).  ONE group,
-            // X = [h4 (8 blocks) | posenc (2 blocks)] against dpre_4, so dpre_4 is streamed once (rounds 2-4: two groups, twice)
-            bpush(&L.b_h, (size_t)(l - 1) * layer, 10, &L.b_dy, (size_t)l * layer, 8, po.trunk_k[l], 256, 256 + h->P, 256, 0, po.trunk_b[l], 256);
-            bspecs.back().x2off = &L.b_pe; bspecs.back().Kb2 = 2; bspecs.back().x2_blocks = 2;
-          } else {
-            bpush(&L.b_h, (size_t)(l - 1) * layer, 8, &L.b_dy, (size_t)l * layer, 8, po.trunk_k[l], 256, 256, 256, 0, po.trunk_b[l], 256);
-            if (l == d.nerf_skip_layer)   // merge off: the posenc rows of the skip layer as a group of their own (dpre_4 read twice)
-              bpush(&L.b_pe, 0, 2, &L.b_dy, (size_t)l * layer, 8, po.trunk_k[l] + 256 * 256, 256, h->P, 256, 0, -1, 0);
-          }
-        }
-      }
-      const bool merge_alpha = h->bf16_wgrad_merge && h->A == 0;
-      if (!merge_alpha) {
-        bpush(&L.b_h, (size_t)7 * layer, 8, &L.b_dbn, 0, 8, po.bn_k, 256, 256, 256, 0, po.bn_b, 256);
-      } else {
-        // the bottleneck AND the alpha head read h8 (modules.py:149-157): ONE group, dY = [d bottleneck (8 blocks) | d raw (block 0 of
-        // the small stash)], h8 streamed once; slab column 256 + 3 (d raw sigma) is the alpha kernel's gradient
-        bpush(&L.b_h, (size_t)7 * layer, 8, &L.b_dbn, 0, 9, po.bn_k, 256, 256, 256, 0, po.bn_b, 256);
-        BSpec& m = bspecs.back();
-        m.y2off = &L.b_dsmall; m.Nb2 = 1; m.y2_blocks = 2;
-        m.dst2 = po.alpha_k; m.col20 = 256 + 3; m.dst2_ld = 1; m.dst2_cols = 1;
-      }
-      bpush(&L.b_bn, 0, 8, &L.b_drgbh, 0, 4, po.rgbh_k, 128, 256, 128, 0, po.rgbh_b, 128);
-      // narrow heads against the "small" dY block: columns 0..2 = d rgb logits (X = rgb hidden), column 3 = d raw sigma (X = h8)
-      bpush(&L.b_rgbh, 0, 4, &L.b_dsmall, 0, 2, po.logit_k, 3, 128, 3, 0, po.logit_b, 3, po.alpha_b, 3);
-      if (h->A > 0) bpush(&L.b_bn, 0, 8, &L.b_dsmall, 0, 2, po.alpha_k, 1, 256, 1, 3, -1, 0);   // use_alpha_condition: X = the bottleneck
-      else if (!merge_alpha) bpush(&L.b_h, (size_t)7 * layer, 8, &L.b_dsmall, 0, 2, po.alpha_k, 1, 256, 1, 3, -1, 0);
-      // (merged: the alpha head rides in the bottleneck's group above)
-    }
+// ---- wgrad groups (training): what each multiplies, which leaves it feeds ----
+void Planner::wgrad_specs() {
+  if (!train) return;
+  for (int lv = 0; lv < h->nlevels; ++lv) {
+    if (bft) bf16_specs(lv);
+    else fp32_specs(lv);
+    if (h->warp && !bfw) warp_specs(lv, lv > 0 ? 1 : 0);   // the field is shared by both passes: level 1 accumulates
   }
+  if (h->warp && !bfw && p.key.bgN > 0) warp_specs(BG, 2);
+  if (h->warp && !bfw && p.key.elastic) warp_specs(TG, 3);   // tangent activations x tangent adjoints, same leaves
   // bf16 SE3 trunk: every pass through the field (coarse / fine samples, background points, the 3 tangents per coarse sample)
   // leaves its own X / dY stash; all of them add into the same leaves (reduce passes 0..3).  The tangent pass carries no bias.
   if (bfw) {
-    const WarpParamOffsets& w = h->wpo;
-    auto add_bf_warp = [&](int lv, int accu, bool tangent) {
-      LevelWs& L = p.L[lv];
-      const int rows = tangent ? p.rows[0] : p.rows[lv];
-      L.bw_ngroups = (tangent ? 3 : 1) * ((rows + 255) / 256 * 8);
-      const size_t layer = (size_t)L.bw_ngroups * 4 * BF_BLOCK_DW;
-      auto wpush = [&](size_t* xoff, size_t xadd, int Kb, size_t* yoff, size_t yadd, int Nb, int64_t dst, int dst_ld, int rws, int cols,
-                       int64_t bias_dst, int bias_cols) {
-        BSpec b = {lv, xoff, xadd, Kb, yoff, yadd, Nb, dst, dst_ld, rws, cols, 0, tangent ? -1 : bias_dst, bias_cols, -1, 0};
-        b.accu = accu; b.ngroups = L.bw_ngroups;
-        bspecs.push_back(b);
-      };
-      for (int l = 0; l < WARP_DEPTH; ++l) {
-        if (l == 0) {
-          wpush(&L.bw_in, 0, 2, &L.bw_dy, 0, 4, w.trunk_k[0], WARP_W, h->Win, WARP_W, w.trunk_b[0], WARP_W);
-        } else {
-          wpush(&L.bw_h, (size_t)(l - 1) * layer, 4, &L.bw_dy, (size_t)l * layer, 4, w.trunk_k[l], WARP_W, WARP_W, WARP_W, w.trunk_b[l], WARP_W);
-          if (l == WARP_SKIP)
-            wpush(&L.bw_in, 0, 2, &L.bw_dy, (size_t)l * layer, 4, w.trunk_k[l] + (int64_t)WARP_W * WARP_W, WARP_W, h->Win, WARP_W, -1, 0);
-        }
-      }
-      // both heads read h6 against the "small" dY block: columns 0..2 = dL/dw, 3..5 = dL/dv
-      BSpec hd = {lv, &L.bw_h, (size_t)(WARP_DEPTH - 1) * layer, 4, &L.bw_dhead, 0, 2, w.w_k, 3, WARP_W, 3, 0,
-                  tangent ? -1 : w.w_b, 3, tangent ? -1 : w.v_b, 3};
-      hd.bias2_cols = 3; hd.accu = accu; hd.ngroups = L.bw_ngroups; hd.dst2 = w.v_k; hd.col20 = 3;
-      bspecs.push_back(hd);
-    };
-    for (int lv = 0; lv < h->nlevels; ++lv) add_bf_warp(lv, lv > 0 ? 1 : 0, false);
-    if (bgN > 0) add_bf_warp(BG, 2, false);
-    if (elastic) add_bf_warp(TG, 3, true);
+    for (int lv = 0; lv < h->nlevels; ++lv) bf16_warp_specs(lv, lv > 0 ? 1 : 0, false);
+    if (p.key.bgN > 0) bf16_warp_specs(BG, 2, false);
+    if (p.key.elastic) bf16_warp_specs(TG, 3, true);
   }
-  if (train) {
-    for (int lv = 0; lv < h->nlevels; ++lv) {
-      LevelWs& L = p.L[lv];
-      const MlpParamOffsets& po = h->po[lv];
-      const size_t layer = (size_t)p.ntiles[lv] * FRAG_TILE_256;
-      for (int l = 0; l < TRUNK_DEPTH && !bft; ++l) {
-        if (l == 0) {
-          specs.push_back({lv, SRC_PLAIN, &L.st_pe, PKS * TILE_ROWS, h->P, Kb_pe, SRC_FRAG256, &L.dy_trunk, FRAG_TILE_256, 8, 0,
-                           po.trunk_k[0], 256, h->P, 256, Kb_pe * 8, 0, 0});
-        } else {
-          specs.push_back({lv, SRC_FRAG256, &L.st_h, FRAG_TILE_256, 256, 8, SRC_FRAG256, &L.dy_trunk, FRAG_TILE_256, 8, 0,
-                           po.trunk_k[l], 256, 256, 256, 64, (size_t)(l - 1) * layer, (size_t)l * layer});
-          if (l == d.nerf_skip_layer)
-            specs.push_back({lv, SRC_PLAIN, &L.st_pe, PKS * TILE_ROWS, h->P, Kb_pe, SRC_FRAG256, &L.dy_trunk, FRAG_TILE_256, 8, 0,
-                             po.trunk_k[l] + 256 * 256, 256, h->P, 256, Kb_pe * 8, 0, (size_t)l * layer});
-        }
-      }
-      if (!bft) {
-      specs.push_back({lv, SRC_FRAG256, &L.st_h, FRAG_TILE_256, 256, 8, SRC_FRAG256, &L.dy_bn, FRAG_TILE_256, 8, 0,
-                       po.bn_k, 256, 256, 256, 64, (size_t)7 * layer, 0});
-      specs.push_back({lv, SRC_FRAG256, &L.st_bn, FRAG_TILE_256, 256, 8, SRC_FRAG128, &L.dy_rgbh, FRAG_TILE_128, 4, 0,
-                       po.rgbh_k, 128, 256, 128, 32, 0, 0});
-      // narrow heads on the VALU: alpha (X = h8, vec.w) and rgb logits (X = rgb hidden, vec.xyz)
-      if (h->A > 0)   // use_alpha_condition: the alpha head reads the bottleneck
-        specs.push_back({lv, SRC_FRAG256, &L.st_bn, FRAG_TILE_256, 256, 8, 0, nullptr, 0, 0, 1, po.alpha_k, 1, 256, 1, 12, 0, 0});
-      else
-        specs.push_back({lv, SRC_FRAG256, &L.st_h, FRAG_TILE_256, 256, 8, 0, nullptr, 0, 0, 1,
-                         po.alpha_k, 1, 256, 1, 12, (size_t)7 * layer, 0});
-      specs.push_back({lv, SRC_FRAG128, &L.st_rgbh, FRAG_TILE_128, 128, 4, 0, nullptr, 0, 0, 3,
-                       po.logit_k, 3, 128, 3, 6, 0, 0});
-      }
-      if (h->warp && !bfw) add_warp_groups(lv, lv > 0 ? 1 : 0);   // the field is shared by both passes: level 1 accumulates
-    }
-    if (h->warp && !bfw && bgN > 0) add_warp_groups(BG, 2);
-    if (h->warp && !bfw && elastic) add_warp_groups(TG, 3);   // tangent activations x tangent adjoints, same leaves
-  }
+}
 
-  // ---- float layout ----
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t r = o; o = align_up(o + n, ALIGN_F); return r; };
-  // ---- stream-K partition of the wgrad work: equal cost per workgroup, one workgroup per CU ----
-  // cost of one 64-row tile of a group, in units of a full 256x256 layer tile; the narrow groups
-  // are staging/latency bound, so they are charged more than their MFMA share.
-  auto env_cost = [](const char* name, double dflt) {   // calibration overrides (scripts/wgrad_calib.py): experiment builds only
-#ifdef NRF_EXPERIMENT
-    if (const char* e = getenv(name)) return atof(e);
-#endif
-    (void)name;
-    return dflt;
-  };
-  // measured with scripts/wgrad_calib.py / wgrad_calib_vrig.py (per-segment wall clocks, least squares), relative to a
-  // 256x256 tile; round 3 (asm LDS-DMA + 160 KiB ring: the narrow groups are no longer latency-bound): 8x8 = 14.8 us; round 6 (SGPR piece
-  // tables, refill behind the MFMAs): re-fitted on config A and the vrig shape (gpurun_out/r6h: every narrow type ~6 % cheaper relative
-  // to 8x8, a segment 0.4-0.5 tiles; the two-vector SE3 heads 0.155: the fit's Kb = 4, Nb = 0 row mixes them with the rgb logits)
-  const double c_vec256 = env_cost("NRF_COST_VEC256", 0.106), c_vec128 = env_cost("NRF_COST_VEC128", 0.094),
-               c_vec128x2 = env_cost("NRF_COST_VEC128X2", 0.155),   // SE3 heads: two vectors against one pass over h6
-               c_pe = env_cost("NRF_COST_PE", 0.270),               // 2 x 8 blocks: posenc rows of the NeRF trunk
-               c_rgbh = env_cost("NRF_COST_RGBH", 0.516),           // 8 x 4
-               c_44 = env_cost("NRF_COST_44", 0.266),               // 4 x 4: SE3 trunk layers
-               c_pe128 = env_cost("NRF_COST_PE128", 0.141),         // 2 x 4: SE3 trunk input rows
-               c_seg = env_cost("NRF_COST_SEG", 0.5);   // fixed cost of opening a segment (pipeline fill + slab flush), in tiles
-  auto tile_cost = [&](const GroupSpec& sp) -> double {
-    if (sp.Nb == 0) return sp.Kb == 8 ? c_vec256 : sp.vecoff2 ? c_vec128x2 : c_vec128;   // vector columns only (VALU + HBM stream)
-    if (sp.Nb == 8) return sp.Kb >= 5 ? 1.0 : c_pe;
-    return sp.Kb >= 5 ? c_rgbh : sp.Kb >= 3 ? c_44 : c_pe128;
-  };
-  std::vector<int> nsplit(specs.size(), 0);
+void Planner::fp32_specs(int lv) {
+  LevelWs& L = p.L[lv];
+  const MlpParamOffsets& po = h->po[lv];
+  const size_t layer = (size_t)p.ntiles[lv] * FRAG_TILE_256;
+  for (int l = 0; l < TRUNK_DEPTH; ++l) {
+    const Operand dy = frag256(&L.dy_trunk, (size_t)l * layer);
+    if (l > 0) gemm(lv, 0, frag256(&L.st_h, (size_t)(l - 1) * layer), 256, dy, po.trunk_k[l], 256);
+    if (l == 0 || l == d.nerf_skip_layer) gemm(lv, 0, plain(&L.st_pe, h->PK), h->P, dy, po.trunk_k[l] + (l > 0 ? 256 * 256 : 0), 256);
+  }
+  gemm(lv, 0, frag256(&L.st_h, (size_t)7 * layer), 256, frag256(&L.dy_bn), po.bn_k, 256);
+  gemm(lv, 0, frag256(&L.st_bn), 256, frag128(&L.dy_rgbh), po.rgbh_k, 128);
+  // narrow heads on the VALU: alpha (X = h8, or the bottleneck under use_alpha_condition; vec.w) and rgb logits (X = rgb hidden, vec.xyz)
+  heads(lv, 0, h->A > 0 ? frag256(&L.st_bn) : frag256(&L.st_h, (size_t)7 * layer), 256, 1, po.alpha_k);
+  heads(lv, 0, frag128(&L.st_rgbh), 128, 3, po.logit_k);
+}
+
+// SE3 trunk + heads of level `lv` (coarse / fine samples, or the background-point batch, or the tangents)
+void Planner::warp_specs(int lv, int accu) {
+  LevelWs& L = p.L[lv];
+  const WarpParamOffsets& w = h->wpo;
+  const size_t wl = (size_t)p.ntiles[lv] * FRAG_TILE_128;
+  for (int l = 0; l < WARP_DEPTH; ++l) {
+    const Operand dy = frag128(&L.w_dy, (size_t)l * wl);
+    if (l > 0) gemm(lv, accu, frag128(&L.w_st_h, (size_t)(l - 1) * wl), WARP_W, dy, w.trunk_k[l], WARP_W);
+    if (l == 0 || l == WARP_SKIP)
+      gemm(lv, accu, plain(&L.w_st_win, h->PKw), h->Win, dy, w.trunk_k[l] + (l > 0 ? (int64_t)WARP_W * WARP_W : 0), WARP_W);
+  }
+  // both heads read h6: one pass over its stash
+  heads(lv, accu, frag128(&L.w_st_h, (size_t)(WARP_DEPTH - 1) * wl), WARP_W, 3, w.w_k, &L.w_dw4, &L.w_dv4, w.v_k);
+}
+
+// bf16 training: the NeRF MLP groups go to the bf16 wgrad kernel (X / dY = bf16 stash buffers of Kb / Nb blocks per 32-sample
+// group); a group may also own bias gradients (column sums of its dY)
+void Planner::bf16_specs(int lv) {
+  LevelWs& L = p.L[lv];
+  const MlpParamOffsets& po = h->po[lv];
+  L.b_ngroups = (p.rows[lv] + 255) / 256 * 8;
+  const size_t layer = (size_t)L.b_ngroups * 8 * BF_BLOCK_DW;
+  for (int l = 0; l < TRUNK_DEPTH; ++l) {
+    const BfSrc dy{&L.b_dy, (size_t)l * layer, 8};
+    if (l == 0) {
+      bgemm(lv, {&L.b_pe, 0, 2}, dy, po.trunk_k[0], h->P, 256, po.trunk_b[0]);
+    } else if (l == d.nerf_skip_layer && h->bf16_wgrad_merge) {
+      // (NRF_OPT_BF16_WGRAD_MERGE) the skip layer's kernel is [256 + P, 256]: rows 0..255 multiply h4, rows 256.. the posenc (modules.py:47-48).  ONE group,
+      // X = [h4 (8 blocks) | posenc (2 blocks)] against dpre_4, so dpre_4 is streamed once (rounds 2-4: two groups, twice)
+      bgemm(lv, {&L.b_h, (size_t)(l - 1) * layer, 8}, dy, po.trunk_k[l], 256 + h->P, 256, po.trunk_b[l]).x2 = {&L.b_pe, 0, 2, 2};
+    } else {
+      bgemm(lv, {&L.b_h, (size_t)(l - 1) * layer, 8}, dy, po.trunk_k[l], 256, 256, po.trunk_b[l]);
+      if (l == d.nerf_skip_layer)   // merge off: the posenc rows of the skip layer as a group of their own (dpre_4 read twice)
+        bgemm(lv, {&L.b_pe, 0, 2}, dy, po.trunk_k[l] + 256 * 256, h->P, 256, -1);
+    }
+  }
+  const BfSrc h8{&L.b_h, (size_t)7 * layer, 8}, dsmall{&L.b_dsmall, 0, 2};
+  const bool merge_alpha = h->bf16_wgrad_merge && h->A == 0;
+  BSpec& bn = bgemm(lv, h8, {&L.b_dbn, 0, 8}, po.bn_k, 256, 256, po.bn_b);
+  if (merge_alpha) {
+    // the bottleneck AND the alpha head read h8 (modules.py:149-157): ONE group, dY = [d bottleneck (8 blocks) | d raw (block 0 of
+    // the small stash)], h8 streamed once; slab column 256 + 3 (d raw sigma) is the alpha kernel's gradient
+    bn.dy2 = {&L.b_dsmall, 0, 1, 2};
+    bn.w[1] = {po.alpha_k, 1, 256 + 3};
+  }
+  bgemm(lv, {&L.b_bn, 0, 8}, {&L.b_drgbh, 0, 4}, po.rgbh_k, 256, 128, po.rgbh_b);
+  // narrow heads against the "small" dY block: columns 0..2 = d rgb logits (X = rgb hidden), column 3 = d raw sigma (X = h8)
+  bgemm(lv, {&L.b_rgbh, 0, 4}, dsmall, po.logit_k, 128, 3, po.logit_b).b[1] = {po.alpha_b, 1, 3};
+  if (h->A > 0) bgemm(lv, {&L.b_bn, 0, 8}, dsmall, po.alpha_k, 256, 1, -1, 3);   // use_alpha_condition: X = the bottleneck
+  else if (!merge_alpha) bgemm(lv, h8, dsmall, po.alpha_k, 256, 1, -1, 3);
+  // (merged: the alpha head rides in the bottleneck's group above)
+}
+
+void Planner::bf16_warp_specs(int lv, int accu, bool tangent) {
+  LevelWs& L = p.L[lv];
+  const WarpParamOffsets& w = h->wpo;
+  const int rows = tangent ? p.rows[0] : p.rows[lv];
+  L.bw_ngroups = (tangent ? 3 : 1) * ((rows + 255) / 256 * 8);
+  const size_t layer = (size_t)L.bw_ngroups * 4 * BF_BLOCK_DW;
+  const size_t first = bspecs.size();
+  auto bias = [&](int64_t b) { return tangent ? -1 : b; };
+  for (int l = 0; l < WARP_DEPTH; ++l) {
+    const BfSrc dy{&L.bw_dy, (size_t)l * layer, 4};
+    if (l == 0) {
+      bgemm(lv, {&L.bw_in, 0, 2}, dy, w.trunk_k[0], h->Win, WARP_W, bias(w.trunk_b[0]));
+    } else {
+      bgemm(lv, {&L.bw_h, (size_t)(l - 1) * layer, 4}, dy, w.trunk_k[l], WARP_W, WARP_W, bias(w.trunk_b[l]));
+      if (l == WARP_SKIP) bgemm(lv, {&L.bw_in, 0, 2}, dy, w.trunk_k[l] + (int64_t)WARP_W * WARP_W, h->Win, WARP_W, -1);
+    }
+  }
+  // both heads read h6 against the "small" dY block: columns 0..2 = dL/dw, 3..5 = dL/dv
+  BSpec& hd = bgemm(lv, {&L.bw_h, (size_t)(WARP_DEPTH - 1) * layer, 4}, {&L.bw_dhead, 0, 2}, w.w_k, WARP_W, 3, bias(w.w_b));
+  hd.w[1] = {w.v_k, 3, 3};
+  hd.b[1] = {bias(w.v_b), 3, 3};
+  for (size_t i = first; i < bspecs.size(); ++i) { bspecs[i].accu = accu; bspecs[i].ngroups = L.bw_ngroups; }
+}
+
+// ---- stream-K cut of both wgrad kernels' work ----
+void Planner::cut_wgrad() {
   if (!specs.empty()) {
-    double total = 0;
-    for (auto& sp : specs) total += tile_cost(sp) * p.ntiles[sp.lv];
-    const int nwg = G;
-    total += c_seg * (nwg + (double)specs.size());   // every workgroup and every group boundary opens a segment
-    const double quota = total / nwg;
-    p.seg_begin.assign(1, 0);
-    int w = 0;
-    double room = quota;
-    for (size_t gi = 0; gi < specs.size(); ++gi) {
-      const double c = tile_cost(specs[gi]);
-      int t0 = 0;
-      const int nt = p.ntiles[specs[gi].lv];
-      while (t0 < nt) {
-        int take_n = (int)floor((room - c_seg) / c + 1e-9);
-        if (take_n <= 0 && w < nwg - 1) {            // this workgroup is full: move on
-          p.seg_begin.push_back((int)p.segs.size());
-          ++w; room += quota;
-          continue;
-        }
-        if (take_n <= 0) take_n = nt - t0;           // last workgroup absorbs rounding leftovers
-        if (w == nwg - 1) take_n = nt - t0;
-        if (take_n > nt - t0) take_n = nt - t0;
-        p.segs.push_back({(int)gi, t0, t0 + take_n, nsplit[gi]});
-        nsplit[gi] += 1;
-        t0 += take_n;
-        room -= c_seg + take_n * c;
-      }
-    }
-    while ((int)p.seg_begin.size() < nwg + 1) p.seg_begin.push_back((int)p.segs.size());
-    p.wgrad_nwg = nwg;
+    std::vector<double> cost;
+    std::vector<int> nt;
+    for (const GroupSpec& s : specs) { cost.push_back(tile_cost(s)); nt.push_back(p.ntiles[s.lv]); }
+    // fixed cost of opening a segment (pipeline fill + slab flush), in tiles
+    nsplit = stream_k(cost, nt, env_cost("NRF_COST_SEG", 0.5), G, p.segs, p.seg_begin);
+    p.wgrad_nwg = G;
   }
-  // ---- the same stream-K cut for the bf16 groups: HBM-bound, cost = blocks streamed per 32-sample group ----
-  std::vector<int> bnsplit(bspecs.size(), 0);
-  if (!bspecs.empty()) {
-    // a chunk costs (Kb + Nb) + a fixed term, in block units (2 KiB streamed).  Round 2 measured + 12 on config A (the per-chunk
-    // barrier and HBM latency worth 24 KiB of streaming: wgrad 0.87 ms with a pure byte model, 0.61 ms with that one).  Round 6,
-    // after the copies moved to per-segment SGPR tables (wgrad_bf16.hip): ALONE every shape streams 5.6-6.4 TB/s, i.e. cost ~ bytes
-    // (scripts/micro/wgrad_bf16_bench.hip), but IN the mixed launch a byte-proportional model is 3-10 % slower than + 12, and the
-    // narrow shapes (Kb + Nb <= 8: the SE3 trunk's 16 / 12 KiB chunks) are best charged + 8: swept on config D / vrig / A (bf16) at
-    // narrow = 12 / 8 / 5 / 2: 1.19 / 1.13 / 1.18 / 1.38 ms, 0.92 / 0.84 / 0.90 / 1.03 ms, 0.456 / 0.460 / 0.495 / 0.618 ms
-    // (profiles/r06_experiments.md section 3)
-    const double bc_seg = env_cost("NRF_BCOST_SEG", 16.0);   // opening a segment (pipeline fill + 256 KiB slab flush), in block units
-    const double bc_chunk = env_cost("NRF_BCOST_CHUNK", 12.0);   // per-chunk fixed cost (barrier + issue), in block units
-    // the two merged shapes (10 x 8, 8 x 9: ten accumulator blocks per wave, five copies per wave and chunk) cost more per chunk
-    // than their bytes: with a byte-proportional cost the kernel was 10 % SLOWER although it fetched 10 % less (the workgroups
-    // inside the merged groups ran ~1.35 x their quota); swept on the GPU at +0 / 6 / 10 / 16 / 24 / 32 units: 0.555 / 0.508 /
-    // 0.500 / 0.520 / 0.527 / 0.543 ms
-    const double bc_merged = env_cost("NRF_BCOST_MERGED", 10.0);
-    const double bc_chunk_narrow = env_cost("NRF_BCOST_CHUNK_NARROW", 8.0);   // ... of the 4 x 4 / 2 x 4 shapes (SE3 trunk: 16 / 12 KiB chunks)
-    const double bc_quad = env_cost("NRF_BCOST_QUAD", 0.0);   // per accumulator block (Kb x Nb): the MFMA / operand-read side of a chunk
-    auto bcost = [&](const BSpec& sp) {
-      // Kb / Nb include the second source's blocks
-      return (double)(sp.Kb + sp.Nb) + (sp.Kb + sp.Nb <= 8 ? bc_chunk_narrow : bc_chunk) + bc_quad * sp.Kb * sp.Nb + ((sp.Kb2 || sp.Nb2) ? bc_merged : 0.0);
-    };
-    double total = 0;
-    auto bng = [&](const BSpec& sp) { return sp.ngroups ? sp.ngroups : p.L[sp.lv].b_ngroups; };
-    for (auto& sp : bspecs) total += bcost(sp) * bng(sp);
-    const int nwg = G;
-    total += bc_seg * (nwg + (double)bspecs.size());
-    const double quota = total / nwg;
-    p.bseg_begin.assign(1, 0);
-    int w = 0;
-    double room = quota;
-    for (size_t gi = 0; gi < bspecs.size(); ++gi) {
-      const double c = bcost(bspecs[gi]);
-      int t0 = 0;
-      const int nt = bng(bspecs[gi]);
-      while (t0 < nt) {
-        int take_n = (int)floor((room - bc_seg) / c + 1e-9);
-        if (take_n <= 0 && w < nwg - 1) {
-          p.bseg_begin.push_back((int)p.bsegs.size());
-          ++w; room += quota;
-          continue;
-        }
-        if (take_n <= 0 || w == nwg - 1 || take_n > nt - t0) take_n = nt - t0;
-        p.bsegs.push_back({(int)gi, t0, t0 + take_n, bnsplit[gi]});
-        bnsplit[gi] += 1;
-        t0 += take_n;
-        room -= bc_seg + take_n * c;
-      }
-    }
-    while ((int)p.bseg_begin.size() < nwg + 1) p.bseg_begin.push_back((int)p.bsegs.size());
-    p.bwgrad_nwg = nwg;
+  if (!bspecs.empty()) {   // "tile" = 32-sample group
+    std::vector<double> cost;
+    std::vector<int> nt;
+    for (const BSpec& s : bspecs) { cost.push_back(bcost(s)); nt.push_back(s.ngroups ? s.ngroups : p.L[s.lv].b_ngroups); }
+    // opening a segment (pipeline fill + 256 KiB slab flush), in block units
+    bnsplit = stream_k(cost, nt, env_cost("NRF_BCOST_SEG", 16.0), G, p.bsegs, p.bseg_begin);
+    p.bwgrad_nwg = G;
   }
-  p.ntasks = (int)p.segs.size();
-  if (h->embed) {
-    p.iparams = take((size_t)h->nparams);
-    if (train) p.igrad = take((size_t)h->nparams);
-  }
-  p.bfpack.clear();
-  if (!train || bft) {   // weight streams of the bf16 chains (mlp_bf16.hip): chunks (panels) in execution order
-    for (int lv = 0; lv < h->nlevels; ++lv) {
-      const MlpParamOffsets& po = h->po[lv];
-      // x3: the same GEMM sequence with every k-step row doubled (W_hi, W_lo); the kernel cuts a panel's rows into chunks itself
-      const size_t fwd_kb = x3 ? BF_X3_STREAM_KB : BF_FWD_STREAM_KB;
-      p.L[lv].bf_wpk = take(fwd_kb * 256);   // KiB -> floats
-      size_t at = 0;   // floats from the level's stream base
-      size_t base = p.L[lv].bf_wpk;
-      int tr = 0;
-      // One GEMM = nblocks / pb panels; a panel (chunk) = [row][block of the panel][lane] x 16 B, rows = [bias row,] then the
-      // k-step rows of each input part (leaf, ld, row0, valid K, input blocks)
-      struct Part { int64_t leaf; int ld, row0, krows, nin; };
-      auto gemm = [&](int pb, int nblocks, int ncols, int64_t bias, std::initializer_list<Part> parts) {
-        for (int pn = 0; pn < nblocks / pb; ++pn) {
-          int row = 0;
-          auto emit = [&](int kind, int64_t src, int ld, int row0, int krows, int nrows) {
-            RcPackDesc e;
-            memset(&e, 0, sizeof(e));
-            e.src_off = src; e.dst_off = (long long)(base + at + (size_t)row * pb * 256); e.kind = kind; e.src_ld = ld; e.row0 = row0;
-            e.krows = krows; e.ncols = ncols; e.ngroups = nrows; e.nout = pb; e.nout_panel = pb; e.o0 = 0; e.transposed = tr;
-            e.oblk0 = pn * pb; e.x3 = x3 && !tr;
-            p.bfpack.push_back(e);
-            row += nrows;
-          };
-          if (bias >= 0) emit(1, bias, 0, 0, 0, 1);
-          else if (bias == -2) emit(2, 0, 0, 0, 0, 1);   // a zero row where the kernel runs a bias-style k-step this model does not use
-          for (const Part& q : parts) emit(0, q.leaf, q.ld, q.row0, q.krows, (x3 && !tr ? 2 : 1) * 2 * q.nin);
-          at += (size_t)row * pb * 256;
-        }
-      };
-      gemm(2, 8, TRUNK_W, po.trunk_b[0], {{po.trunk_k[0], TRUNK_W, 0, h->P, 2}});
-      for (int l = 1; l < TRUNK_DEPTH; ++l) {
-        if (l == SKIP_LAYER) gemm(2, 8, TRUNK_W, po.trunk_b[l], {{po.trunk_k[l], TRUNK_W, 0, TRUNK_W, 8}, {po.trunk_k[l], TRUNK_W, TRUNK_W, h->P, 2}});
-        else gemm(2, 8, TRUNK_W, po.trunk_b[l], {{po.trunk_k[l], TRUNK_W, 0, TRUNK_W, 8}});
-      }
-      gemm(2, 8, TRUNK_W, po.bn_b, {{po.bn_k, TRUNK_W, 0, TRUNK_W, 8}});        // bottleneck
-      gemm(1, 1, 1, po.alpha_b, {{po.alpha_k, 1, 0, TRUNK_W, 8}});               // alpha head: one block, column 0
-      gemm(2, 4, RGB_W, -1, {{po.rgbh_k, RGB_W, 0, TRUNK_W, 8}});                // rgb hidden (bias: the fp32 per-ray term)
-      gemm(1, 1, 3, po.logit_b, {{po.logit_k, 3, 0, RGB_W, 4}});                 // rgb logits: one block, columns 0..2
-      p.bf_stream_ok = at == fwd_kb * 256;
-      if (bft) {
-        // dgrad stream (nerf_mlp_bwd_bf16_kernel): A = W as stored, [m = the layer's input feature][k = its output feature];
-        // ncols = valid M, Part.krows = valid K
-        p.L[lv].bf_wpkT = take((size_t)(h->warp ? BF_BWD_STREAM_DPTS_KB : BF_BWD_STREAM_KB) * 256);
-        base = p.L[lv].bf_wpkT; at = 0; tr = 1;
-        gemm(4, 4, RGB_W, -1, {{po.logit_k, 3, 0, 3, 1}});                       // G1: one k-step (3 valid) + a zero one, 4 blocks
-        // the alpha head's transpose is ONE bias-style row (w_alpha[0:256], B = d sigma) in the GEMM that produces the gradient of
-        // its input: the trunk output (G3), or -- use_alpha_condition, modules.py:152-157 -- the bottleneck (G2); zeros in the other
-        const int64_t arow = po.alpha_k;
-        gemm(2, 8, TRUNK_W, h->A > 0 ? arow : -2, {{po.rgbh_k, RGB_W, 0, RGB_W, 4}});             // G2: rows 0..255 of [256+R, 128]
-        gemm(2, 8, TRUNK_W, h->A > 0 ? -2 : arow, {{po.bn_k, TRUNK_W, 0, TRUNK_W, 8}});           // G3
-        for (int l = TRUNK_DEPTH - 1; l >= 1; --l) gemm(2, 8, TRUNK_W, -1, {{po.trunk_k[l], TRUNK_W, 0, TRUNK_W, 8}});
-        if (h->warp) {   // d posenc: W0 and the skip layer's posenc rows as A [m = posenc feature (P valid)][k = output feature]
-          gemm(2, 2, h->P, -1, {{po.trunk_k[0], TRUNK_W, 0, TRUNK_W, 8}});
-          gemm(2, 2, h->P, -1, {{po.trunk_k[d.nerf_skip_layer], TRUNK_W, TRUNK_W, TRUNK_W, 8}});
-        }
-        p.bf_stream_ok = p.bf_stream_ok && at == (size_t)(h->warp ? BF_BWD_STREAM_DPTS_KB : BF_BWD_STREAM_KB) * 256;
-      }
-    }
-    if (h->warp) {   // bf16 SE3 trunk (warp_bf16.hip): forward stream (also for bf16 inference), reverse stream (training); x3: its doubled rows (warp_bf16x3.hip)
-      const WarpParamOffsets& w = h->wpo;
-      size_t at = 0, base = 0;
-      int tr = 0;
-      struct Part { int64_t leaf; int ld, row0, krows, nin; int64_t leaf2 = -1; int split = 0; };
-      // as the NeRF gemm() above; bias2 / Part.leaf2: the second of two leaves side by side (heads w | v)
-      auto gemm = [&](int pb, int nblocks, int ncols, int64_t bias, int64_t bias2, int bsplit, std::initializer_list<Part> parts) {
-        for (int pn = 0; pn < nblocks / pb; ++pn) {
-          int row = 0;
-          auto emit = [&](int kind, int64_t src, int64_t src2, int split, int ld, int row0, int krows, int nrows) {
-            RcPackDesc e;
-            memset(&e, 0, sizeof(e));
-            e.src_off = src; e.dst_off = (long long)(base + at + (size_t)row * pb * 256); e.kind = kind; e.src_ld = ld; e.row0 = row0;
-            e.krows = krows; e.ncols = ncols; e.ngroups = nrows; e.nout = pb; e.nout_panel = pb; e.o0 = 0; e.transposed = tr;
-            e.oblk0 = pn * pb; e.src_off2 = src2 >= 0 ? src2 : 0; e.split = src2 >= 0 ? split : 0; e.x3 = x3 && !tr;
-            p.bfpack.push_back(e);
-            row += nrows;
-          };
-          if (bias >= 0) emit(1, bias, bias2, bsplit, 0, 0, 0, 1);
-          for (const Part& q : parts) emit(0, q.leaf, q.leaf2, q.split, q.ld, q.row0, q.krows, (x3 && !tr ? 2 : 1) * 2 * q.nin);
-          at += (size_t)row * pb * 256;
-        }
-      };
-      const size_t wfwd_kb = x3 ? BFW_X3_STREAM_KB : BFW_FWD_STREAM_KB;
-      p.bfw_wpk = take(wfwd_kb * 256);
-      base = p.bfw_wpk;
-      gemm(2, 4, WARP_W, w.trunk_b[0], -1, 0, {{w.trunk_k[0], WARP_W, 0, h->Win, 2}});
-      for (int l = 1; l < WARP_DEPTH; ++l) {
-        if (l == WARP_SKIP) gemm(2, 4, WARP_W, w.trunk_b[l], -1, 0, {{w.trunk_k[l], WARP_W, 0, WARP_W, 4}, {w.trunk_k[l], WARP_W, WARP_W, h->Win, 2}});
-        else gemm(2, 4, WARP_W, w.trunk_b[l], -1, 0, {{w.trunk_k[l], WARP_W, 0, WARP_W, 4}});
-      }
-      gemm(1, 1, 6, w.w_b, w.v_b, 3, {{w.w_k, 3, 0, WARP_W, 4, w.v_k, 3}});     // heads: columns 0..2 = w, 3..5 = v
-      p.bf_stream_ok = p.bf_stream_ok && at == wfwd_kb * 256;
-      if (bfw) {
-        // reverse stream: A = W as stored, [m = the layer's input feature][k = its output feature]
-        p.bfw_wpkT = take((size_t)BFW_BWD_STREAM_KB * 256);
-        base = p.bfw_wpkT; at = 0; tr = 1;
-        gemm(4, 4, WARP_W, -1, -1, 0, {{w.w_k, 3, 0, 6, 1, w.v_k, 3}});         // heads^T: K = (w0..2, v0..2) of one k-step + a zero one
-        for (int l = WARP_DEPTH - 1; l >= 1; --l) gemm(2, 4, WARP_W, -1, -1, 0, {{w.trunk_k[l], WARP_W, 0, WARP_W, 4}});
-        gemm(2, 2, h->Win, -1, -1, 0, {{w.trunk_k[0], WARP_W, 0, WARP_W, 4}});                  // C0: d input through layer 0
-        gemm(2, 2, h->Win, -1, -1, 0, {{w.trunk_k[WARP_SKIP], WARP_W, WARP_W, WARP_W, 4}});     // C4: ... through the skip rows
-        p.bf_stream_ok = p.bf_stream_ok && at == (size_t)BFW_BWD_STREAM_KB * 256;
-      }
-    }
-    p.bf_desc = take(p.bfpack.size() * sizeof(RcPackDesc) / 4 + 16);
-  }
+}
 
-  auto alloc_warp = [&](LevelWs& L, size_t nt) {
-    L.wpoints = take(nt * TILE_ROWS * 3);
-    L.points_raw = take(nt * TILE_ROWS * 3);
-    if (wstash) {
-      L.w_st_win = take(nt * ((h->PKw + 31) / 32 * 32) * TILE_ROWS);
-      L.w_st_h = take(nt * FRAG_TILE_128 * WARP_DEPTH);
-      L.w_st_wv = take(nt * TILE_ROWS * 8);
-      L.w_bits = take(nt * 4 * 64 * WARP_DEPTH);
+// ---- weight streams of the bf16 / x3 chains: chunks (panels) in execution order ----
+void Planner::weight_streams() {
+  // the bf16 chains run the skip at a compile-time layer: a model whose skip moved has no bf16 stream (check_flags refuses it)
+  const int skip = SKIP_LAYER;
+  p.bf_stream_ok = d.nerf_skip_layer == skip;
+  for (int lv = 0; lv < h->nlevels; ++lv) {
+    const MlpParamOffsets& po = h->po[lv];
+    const size_t fwd_kb = x3 ? BF_X3_STREAM_KB : BF_FWD_STREAM_KB;
+    p.L[lv].bf_wpk = take(fwd_kb * 256);   // KiB -> floats
+    Stream f{p.L[lv].bf_wpk, 0, 0, x3, p.bfpack};
+    f.gemm(2, 8, TRUNK_W, po.trunk_b[0], {{po.trunk_k[0], TRUNK_W, 0, h->P, 2}});
+    for (int l = 1; l < TRUNK_DEPTH; ++l) {
+      if (l == skip) f.gemm(2, 8, TRUNK_W, po.trunk_b[l], {{po.trunk_k[l], TRUNK_W, 0, TRUNK_W, 8}, {po.trunk_k[l], TRUNK_W, TRUNK_W, h->P, 2}});
+      else f.gemm(2, 8, TRUNK_W, po.trunk_b[l], {{po.trunk_k[l], TRUNK_W, 0, TRUNK_W, 8}});
     }
-    if (train && !bfw) {
-      L.d_points = take(nt * TILE_ROWS * 3);
-      L.w_dy = take(nt * FRAG_TILE_128 * WARP_DEPTH);
-      L.w_dw4 = take(nt * TILE_ROWS * 4);
-      L.w_dv4 = take(nt * TILE_ROWS * 4);
-      L.w_small_part = take((size_t)4 * G * WARP_SMALL_PART);
+    f.gemm(2, 8, TRUNK_W, po.bn_b, {{po.bn_k, TRUNK_W, 0, TRUNK_W, 8}});        // bottleneck
+    f.gemm(1, 1, 1, po.alpha_b, {{po.alpha_k, 1, 0, TRUNK_W, 8}});               // alpha head: one block, column 0
+    f.gemm(2, 4, RGB_W, -1, {{po.rgbh_k, RGB_W, 0, TRUNK_W, 8}});                // rgb hidden (bias: the fp32 per-ray term)
+    f.gemm(1, 1, 3, po.logit_b, {{po.logit_k, 3, 0, RGB_W, 4}});                 // rgb logits: one block, columns 0..2
+    p.bf_stream_ok = p.bf_stream_ok && f.at == fwd_kb * 256;
+    if (!bft) continue;
+    // dgrad stream (nerf_mlp_bwd_bf16_kernel): ncols = valid M, Part.krows = valid K
+    const size_t bwd_kb = h->warp ? BF_BWD_STREAM_DPTS_KB : BF_BWD_STREAM_KB;
+    p.L[lv].bf_wpkT = take(bwd_kb * 256);
+    Stream b{p.L[lv].bf_wpkT, 0, 1, x3, p.bfpack};
+    b.gemm(4, 4, RGB_W, -1, {{po.logit_k, 3, 0, 3, 1}});                       // G1: one k-step (3 valid) + a zero one, 4 blocks
+    // the alpha head's transpose is ONE bias-style row (w_alpha[0:256], B = d sigma) in the GEMM that produces the gradient of
+    // its input: the trunk output (G3), or -- use_alpha_condition, modules.py:152-157 -- the bottleneck (G2); zeros in the other
+    const int64_t arow = po.alpha_k;
+    b.gemm(2, 8, TRUNK_W, h->A > 0 ? arow : -2, {{po.rgbh_k, RGB_W, 0, RGB_W, 4}});             // G2: rows 0..255 of [256+R, 128]
+    b.gemm(2, 8, TRUNK_W, h->A > 0 ? -2 : arow, {{po.bn_k, TRUNK_W, 0, TRUNK_W, 8}});           // G3
+    for (int l = TRUNK_DEPTH - 1; l >= 1; --l) b.gemm(2, 8, TRUNK_W, -1, {{po.trunk_k[l], TRUNK_W, 0, TRUNK_W, 8}});
+    if (h->warp) {   // d posenc: W0 and the skip layer's posenc rows as A [m = posenc feature (P valid)][k = output feature]
+      b.gemm(2, 2, h->P, -1, {{po.trunk_k[0], TRUNK_W, 0, TRUNK_W, 8}});
+      b.gemm(2, 2, h->P, -1, {{po.trunk_k[skip], TRUNK_W, TRUNK_W, TRUNK_W, 8}});
     }
-    if (bfw) {   // bf16 trunk: fp32 rows only for what exp_se3 / the elastic kernel read and write; the rest is the bf16 stash
-      const size_t ng = L.bw_ngroups;
-      L.w_st_wv = take(nt * TILE_ROWS * 8);
-      L.d_points = take(nt * TILE_ROWS * 3);
-      L.w_dw4 = take(nt * TILE_ROWS * 4);
-      L.w_dv4 = take(nt * TILE_ROWS * 4);
-      L.bw_in = take(ng * 2 * BF_BLOCK_DW);
-      L.bw_h = take(ng * 4 * BF_BLOCK_DW * WARP_DEPTH);
-      L.bw_bits = take(ng * 64 * 2 * WARP_DEPTH);
-      L.bw_dy = take(ng * 4 * BF_BLOCK_DW * WARP_DEPTH);
-      L.bw_dhead = take(ng * 2 * BF_BLOCK_DW);
+    p.bf_stream_ok = p.bf_stream_ok && b.at == bwd_kb * 256;
+  }
+  if (h->warp) {   // bf16 SE3 trunk (warp_bf16.hip): forward stream (also for bf16 inference), reverse stream (training); x3: its doubled rows (warp_bf16x3.hip)
+    const WarpParamOffsets& w = h->wpo;
+    const size_t wfwd_kb = x3 ? BFW_X3_STREAM_KB : BFW_FWD_STREAM_KB;
+    p.bfw_wpk = take(wfwd_kb * 256);
+    Stream f{p.bfw_wpk, 0, 0, x3, p.bfpack};
+    f.gemm(2, 4, WARP_W, w.trunk_b[0], {{w.trunk_k[0], WARP_W, 0, h->Win, 2}});
+    for (int l = 1; l < WARP_DEPTH; ++l) {
+      if (l == WARP_SKIP) f.gemm(2, 4, WARP_W, w.trunk_b[l], {{w.trunk_k[l], WARP_W, 0, WARP_W, 4}, {w.trunk_k[l], WARP_W, WARP_W, h->Win, 2}});
+      else f.gemm(2, 4, WARP_W, w.trunk_b[l], {{w.trunk_k[l], WARP_W, 0, WARP_W, 4}});
     }
-  };
+    f.gemm(1, 1, 6, w.w_b, {{w.w_k, 3, 0, WARP_W, 4, w.v_k, 3}}, w.v_b, 3);     // heads: columns 0..2 = w, 3..5 = v
+    p.bf_stream_ok = p.bf_stream_ok && f.at == wfwd_kb * 256;
+    if (bfw) {
+      p.bfw_wpkT = take((size_t)BFW_BWD_STREAM_KB * 256);
+      Stream b{p.bfw_wpkT, 0, 1, x3, p.bfpack};
+      b.gemm(4, 4, WARP_W, -1, {{w.w_k, 3, 0, 6, 1, w.v_k, 3}});         // heads^T: K = (w0..2, v0..2) of one k-step + a zero one
+      for (int l = WARP_DEPTH - 1; l >= 1; --l) b.gemm(2, 4, WARP_W, -1, {{w.trunk_k[l], WARP_W, 0, WARP_W, 4}});
+      b.gemm(2, 2, h->Win, -1, {{w.trunk_k[0], WARP_W, 0, WARP_W, 4}});                  // C0: d input through layer 0
+      b.gemm(2, 2, h->Win, -1, {{w.trunk_k[WARP_SKIP], WARP_W, WARP_W, WARP_W, 4}});     // C4: ... through the skip rows
+      p.bf_stream_ok = p.bf_stream_ok && b.at == (size_t)BFW_BWD_STREAM_KB * 256;
+    }
+  }
+  p.bf_desc = take(p.bfpack.size() * sizeof(RcPackDesc) / 4 + 16);
+}
+
+void Planner::alloc_warp(LevelWs& L, size_t nt) {
+  L.wpoints = take(nt * TILE_ROWS * 3);
+  L.points_raw = take(nt * TILE_ROWS * 3);
+  if (wstash) {
+    L.w_st_win = take(nt * ((h->PKw + 31) / 32 * 32) * TILE_ROWS);
+    L.w_st_h = take(nt * FRAG_TILE_128 * WARP_DEPTH);
+    L.w_st_wv = take(nt * TILE_ROWS * 8);
+    L.w_bits = take(nt * 4 * 64 * WARP_DEPTH);
+  }
+  if (train && !bfw) {
+    L.d_points = take(nt * TILE_ROWS * 3);
+    L.w_dy = take(nt * FRAG_TILE_128 * WARP_DEPTH);
+    L.w_dw4 = take(nt * TILE_ROWS * 4);
+    L.w_dv4 = take(nt * TILE_ROWS * 4);
+    L.w_small_part = take((size_t)4 * G * WARP_SMALL_PART);
+  }
+  if (bfw) {   // bf16 trunk: fp32 rows only for what exp_se3 / the elastic kernel read and write; the rest is the bf16 stash
+    const size_t ng = L.bw_ngroups;
+    L.w_st_wv = take(nt * TILE_ROWS * 8);
+    L.d_points = take(nt * TILE_ROWS * 3);
+    L.w_dw4 = take(nt * TILE_ROWS * 4);
+    L.w_dv4 = take(nt * TILE_ROWS * 4);
+    L.bw_in = take(ng * 2 * BF_BLOCK_DW);
+    L.bw_h = take(ng * 4 * BF_BLOCK_DW * WARP_DEPTH);
+    L.bw_bits = take(ng * 64 * 2 * WARP_DEPTH);
+    L.bw_dy = take(ng * 4 * BF_BLOCK_DW * WARP_DEPTH);
+    L.bw_dhead = take(ng * 2 * BF_BLOCK_DW);
+  }
+}
+
+// ---- per-level and shared buffers ----
+void Planner::buffers() {
+  const int B = p.key.B, bgN = p.key.bgN;
   p.cond = take((size_t)B * (h->R > 0 ? h->R : 1));
   p.mse = take((size_t)2 * B);   // [level][ray] squared error
   p.zero_rgb = take((size_t)B * 3);
@@ -709,11 +756,8 @@ void build_plan(nrf_handle h, int B, uint32_t flags, int bgN, int elastic) {
       L.b_drgbh = take(ng * 4 * BF_BLOCK_DW);
       L.b_dsmall = take(ng * 2 * BF_BLOCK_DW);
       L.d_raw4 = take(nt * TILE_ROWS * 4);
-      L.dray = take((size_t)B * RGB_W);
-      L.small_part = take((size_t)4 * G * SMALL_PART);   // up to four workgroups per CU (32-row reverse chain)
-      L.cond_grad = take((size_t)(h->R > 0 ? h->R : 1) * RGB_W);
     } else if (train) {
-      L.st_pe = take(nt * PKS * TILE_ROWS);
+      L.st_pe = take(nt * ((h->PK + 31) / 32 * 32) * TILE_ROWS);
       L.st_h = take(nt * FRAG_TILE_256 * TRUNK_DEPTH);
       L.st_bn = take(nt * FRAG_TILE_256);
       L.st_rgbh = take(nt * FRAG_TILE_128);
@@ -723,6 +767,8 @@ void build_plan(nrf_handle h, int B, uint32_t flags, int bgN, int elastic) {
       L.dy_trunk = take(nt * FRAG_TILE_256 * TRUNK_DEPTH);
       L.dy_bn = take(nt * FRAG_TILE_256);
       L.dy_rgbh = take(nt * FRAG_TILE_128);
+    }
+    if (train) {
       L.dray = take((size_t)B * RGB_W);
       L.small_part = take((size_t)4 * G * SMALL_PART);   // up to four workgroups per CU (32-row reverse chain)
       L.cond_grad = take((size_t)(h->R > 0 ? h->R : 1) * RGB_W);
@@ -746,7 +792,7 @@ void build_plan(nrf_handle h, int B, uint32_t flags, int bgN, int elastic) {
   }
   if (jac && !train) alloc_warp(p.L[TG], p.ntiles[TG]);
   if (h->warp && train) p.wr_sums = take(64);
-  if (h->warp && elastic && train) {
+  if (h->warp && p.key.elastic && train) {
     alloc_warp(p.L[TG], p.ntiles[TG]);
     p.L[0].el_dw4 = take((size_t)p.ntiles[0] * TILE_ROWS * 4);
     p.L[0].el_dv4 = take((size_t)p.ntiles[0] * TILE_ROWS * 4);
@@ -757,9 +803,11 @@ void build_plan(nrf_handle h, int B, uint32_t flags, int bgN, int elastic) {
   p.seg_clock = take(2 * (p.segs.size() + 1));
   p.counters = take(64);
   p.timeline = take(2 * (2 * 4 * 64 + 1024 + 4 * 4096));
+}
 
-  // ---- pack descriptors (both levels, forward and transposed streams); a bf16 TRAINING plan reads only the bf16 images of the
-  //      NeRF MLPs (bfpack), so their fp32 fragment images are not rebuilt every step ----
+// ---- pack descriptors (both levels, forward and transposed streams); a bf16 TRAINING plan reads only the bf16 images of the
+//      NeRF MLPs (bfpack), so their fp32 fragment images are not rebuilt every step ----
+void Planner::pack_descs() {
   for (int lv = 0; lv < (bft ? 0 : h->nlevels); ++lv) {
     const MlpParamOffsets& po = h->po[lv];
     const int64_t base = (int64_t)p.L[lv].wpk;
@@ -784,255 +832,199 @@ void build_plan(nrf_handle h, int B, uint32_t flags, int bgN, int elastic) {
       add(po.trunk_k[d.nerf_skip_layer], pk.bwd_L4bT, 256, 256, 256, 256, 2, 1, 1, h->P);
     }
   }
-  if (h->warp && !bfw) {   // fp32 fragment images of the SE3 trunk (a bf16-trunk training plan reads only its bf16 streams)
-    const WarpParamOffsets& w = h->wpo;
-    const WarpPackOffsets& wk = h->wpk;
-    const int64_t base = (int64_t)p.warp_wpk;
-    auto addw = [&](int64_t src, int dst, int row0, int kvalid, int K, int tr) {
-      PackDesc q;
-      q.src_off = src; q.dst_off = base + dst; q.src_ld = WARP_W; q.src_row0 = row0; q.kvalid = kvalid; q.K = K; q.ncb = 1;
-      q.transposed = tr; q.nwaves = 4; q.nvalid = 1 << 30;
-      p.pack.push_back(q);
-    };
-    addw(w.trunk_k[0], wk.fwd_L[0], 0, h->Win, h->PKw, 0);
-    for (int l = 1; l < WARP_DEPTH; ++l) addw(w.trunk_k[l], wk.fwd_L[l], 0, WARP_W, WARP_W, 0);
-    addw(w.trunk_k[WARP_SKIP], wk.fwd_L4b, WARP_W, h->Win, h->PKw, 0);
-    for (int l = 1; l < WARP_DEPTH; ++l) addw(w.trunk_k[l], wk.bwd_LT[l], 0, WARP_W, WARP_W, 1);
-  }
+  // fp32 fragment images of the SE3 trunk (a bf16-trunk training plan reads only its bf16 streams)
+  if (h->warp && !bfw) warp_pack_descs(h, h->wpo, (int64_t)p.warp_wpk, true, p.pack);
+}
 
-  // ---- wgrad groups + slabs + reduce descriptors ----
-  std::vector<ReduceDesc> reduce2, reduce3, reduce4;   // accumulating descriptors (later launches)
-  if (train) {
-    int first = 0;
-    for (size_t i = 0; i < specs.size(); ++i) {
-      const GroupSpec& s = specs[i];
-      WgradGroup g;
-      memset(&g, 0, sizeof(g));
-      g.x_off = (int64_t)(*s.xoff + s.xadd);
-      g.x_kind = s.xk; g.x_tile_stride = s.xstride; g.x_kvalid = s.kvalid; g.Kb = s.Kb;
-      g.dy_off = s.yoff ? (int64_t)(*s.yoff + s.yadd) : 0;
-      g.dy_kind = s.yk; g.dy_tile_stride = s.ystride; g.Nb = s.Nb;
-      g.ntiles = p.ntiles[s.lv];
-      g.nsplit = nsplit[i];
-      g.tiles_per = 0;
-      g.first_task = first;
-      first += g.nsplit;
-      ReduceDesc r;
-      memset(&r, 0, sizeof(r));
-      r.dst_off = s.dst; r.dst_ld = s.dst_ld; r.rows = s.rows; r.cols = s.cols; r.accumulate = s.accumulate;
-      if (s.vec) {
-        g.vec_off = (int64_t)(s.vecoff ? *s.vecoff : p.L[s.lv].d_raw4);
-        g.vslab_off = (int64_t)take((size_t)g.nsplit * 2 * g.Kb * 32 * 4);
-        g.slab_off = 0;
-        r.src_off = g.vslab_off + (s.vec == 1 ? 3 : 0);
-        r.src_ld = 4; r.part_stride = (int64_t)g.Kb * 32 * 4; r.nparts = 2 * g.nsplit;
-        g.vec2_off = -1;
-        if (s.vecoff2) {
-          g.vec2_off = (int64_t)*s.vecoff2;
-          g.vslab2_off = (int64_t)take((size_t)g.nsplit * 2 * g.Kb * 32 * 4);
-          ReduceDesc r2 = r;
-          r2.dst_off = s.dst2; r2.src_off = g.vslab2_off;
-          (r2.accumulate == 0 ? p.reduce : r2.accumulate == 1 ? reduce2 : r2.accumulate == 2 ? reduce3 : reduce4).push_back(r2);
-        }
-      } else {
-        g.vec_off = -1; g.vslab_off = 0; g.vec2_off = -1;
-        g.slab_off = (int64_t)take((size_t)g.nsplit * g.Kb * 32 * g.Nb * 32);
-        r.src_off = g.slab_off; r.src_ld = g.Nb * 32; r.part_stride = (int64_t)g.Kb * 32 * g.Nb * 32; r.nparts = g.nsplit;
+// ---- fp32 wgrad groups: slabs (taken in group order) + reduce descriptors ----
+void Planner::fp32_groups() {
+  int first = 0;
+  for (size_t i = 0; i < specs.size(); ++i) {
+    const GroupSpec& s = specs[i];
+    WgradGroup g;
+    memset(&g, 0, sizeof(g));
+    g.x_off = (int64_t)(*s.x.off + s.x.add); g.x_kind = s.x.kind; g.x_tile_stride = s.x.stride; g.x_kvalid = s.kvalid; g.Kb = s.x.blocks;
+    g.dy_off = s.dy.off ? (int64_t)(*s.dy.off + s.dy.add) : 0; g.dy_kind = s.dy.kind; g.dy_tile_stride = s.dy.stride; g.Nb = s.dy.blocks;
+    g.ntiles = p.ntiles[s.lv];
+    g.nsplit = nsplit[i];
+    g.first_task = first;
+    first += g.nsplit;
+    g.vec_off = g.vec2_off = -1;
+    if (s.vec) {   // two vec4 partial rows per segment
+      const int64_t part = (int64_t)g.Kb * 32 * 4;
+      g.vec_off = (int64_t)(s.vecoff ? *s.vecoff : p.L[s.lv].d_raw4);
+      g.vslab_off = (int64_t)take((size_t)g.nsplit * 2 * g.Kb * 32 * 4);
+      if (s.vecoff2) {
+        g.vec2_off = (int64_t)*s.vecoff2;
+        g.vslab2_off = (int64_t)take((size_t)g.nsplit * 2 * g.Kb * 32 * 4);
+        add_reduce(reduce_desc(s.dst2, s.cols, s.kvalid, s.cols, g.vslab2_off, 4, part, 2 * g.nsplit, s.accumulate));
       }
-      p.groups.push_back(g);
-      (r.accumulate == 0 ? p.reduce : r.accumulate == 1 ? reduce2 : r.accumulate == 2 ? reduce3 : reduce4).push_back(r);
+      add_reduce(reduce_desc(s.dst, s.cols, s.kvalid, s.cols, g.vslab_off + (s.vec == 1 ? 3 : 0), 4, part, 2 * g.nsplit, s.accumulate));
+    } else {
+      g.slab_off = (int64_t)take((size_t)g.nsplit * g.Kb * 32 * g.Nb * 32);
+      add_reduce(reduce_desc(s.dst, s.cols, s.kvalid, s.cols, g.slab_off, g.Nb * 32, (int64_t)g.Kb * 32 * g.Nb * 32, g.nsplit,
+                             s.accumulate));
     }
-    auto warp_bias_descs = [&](int lv, int grid, int accu) {
+    p.groups.push_back(g);
+  }
+}
+
+// ---- bf16 wgrad groups: slab [Kb*32][Nb*32] per segment (+ a bias slab [Nb*32]); each leaf takes a column window of it ----
+void Planner::bf16_groups() {
+  for (size_t i = 0; i < bspecs.size(); ++i) {
+    const BSpec& s = bspecs[i];
+    const int Kb = s.x.blocks + s.x2.blocks, Nb = s.dy.blocks + s.dy2.blocks;
+    WgradGroup g;
+    memset(&g, 0, sizeof(g));
+    g.x_off = (int64_t)(*s.x.off + s.x.add); g.x_tile_stride = s.x.blocks * BF_BLOCK_DW; g.Kb = Kb; g.x_kvalid = s.rows; g.Kb1 = s.x.blocks;
+    g.dy_off = (int64_t)(*s.dy.off + s.dy.add); g.dy_tile_stride = s.dy.blocks * BF_BLOCK_DW; g.Nb = Nb; g.Nb1 = s.dy.blocks;
+    g.x2_off = s.x2.off ? (int64_t)*s.x2.off : g.x_off; g.x2_tile_stride = s.x2.stride * BF_BLOCK_DW;
+    g.dy2_off = s.dy2.off ? (int64_t)*s.dy2.off : g.dy_off; g.dy2_tile_stride = s.dy2.stride * BF_BLOCK_DW;
+    g.ntiles = s.ngroups ? s.ngroups : p.L[s.lv].b_ngroups; g.nsplit = bnsplit[i]; g.vec_off = -1; g.vec2_off = -1;
+    g.slab_off = (int64_t)take((size_t)g.nsplit * Kb * 32 * Nb * 32);
+    g.vslab_off = s.b[0].off >= 0 ? (int64_t)take((size_t)g.nsplit * Nb * 32) : -1;
+    p.bgroups.push_back(g);
+    for (const Leaf& l : s.w)
+      if (l.off >= 0)
+        add_reduce(reduce_desc(l.off, l.cols, s.rows, l.cols, g.slab_off + l.col0, Nb * 32, (int64_t)Kb * 32 * Nb * 32, g.nsplit, s.accu));
+    for (const Leaf& b : s.b)
+      if (b.off >= 0) add_reduce(reduce_desc(b.off, b.cols, 1, b.cols, g.vslab_off + b.col0, Nb * 32, Nb * 32, g.nsplit, s.accu));
+  }
+}
+
+// ---- bias gradients of the fp32 dgrad launches (per-workgroup partials) and the per-ray condition rows ----
+void Planner::bias_reduces() {
+  int nt_mlp = 0;
+  for (int q = 0; q < h->nlevels; ++q) nt_mlp += p.ntiles[q];
+  // ONE dgrad launch over the tiles of all levels: two workgroups per CU on 64-row tiles, four on 32-row half tiles
+  const int grid = p.bwd32 ? (2 * nt_mlp < 4 * G ? 2 * nt_mlp : 4 * G) : (nt_mlp < 2 * G ? nt_mlp : 2 * G);
+  for (int lv = 0; lv < h->nlevels; ++lv) {
+    const MlpParamOffsets& po = h->po[lv];
+    const LevelWs& L = p.L[lv];
+    auto small = [&](int64_t dst, int cols, int sp_off) {
+      if (bft) return;   // the bf16 wgrad kernel sums the bias columns itself
+      add_reduce(reduce_desc(dst, cols, 1, cols, (int64_t)L.small_part + sp_off, cols, SMALL_PART, grid));
+    };
+    for (int l = 0; l < TRUNK_DEPTH; ++l) small(po.trunk_b[l], 256, l * 256);
+    small(po.bn_b, 256, 2048);
+    small(po.rgbh_b, 128, 2304);
+    small(po.logit_b, 3, 2432);
+    small(po.alpha_b, 1, 2435);
+    if (h->R > 0) add_reduce(reduce_desc(po.rgbh_k + 256 * 128, 128, h->R, 128, (int64_t)L.cond_grad, 128, 0, 1));
+    if (h->warp && !bfw && lv == 0) {   // ONE SE3 dgrad launch (coarse + fine + background tiles), one set of bias partials
+      const int nt_w = nt_mlp + (p.key.bgN > 0 ? p.ntiles[BG] : 0);
+      const int wgrid = nt_w < warp_grid_mul() * G ? nt_w : warp_grid_mul() * G;
       const WarpParamOffsets& w = h->wpo;
-      const LevelWs& L = p.L[lv];
       auto wsmall = [&](int64_t dst, int cols, int sp_off) {
-        ReduceDesc r;
-        memset(&r, 0, sizeof(r));
-        r.dst_off = dst; r.dst_ld = cols; r.rows = 1; r.cols = cols; r.accumulate = accu;
-        r.src_off = (int64_t)L.w_small_part + sp_off; r.src_ld = cols; r.part_stride = WARP_SMALL_PART; r.nparts = grid;
-        (r.accumulate == 0 ? p.reduce : r.accumulate == 1 ? reduce2 : r.accumulate == 2 ? reduce3 : reduce4).push_back(r);
+        add_reduce(reduce_desc(dst, cols, 1, cols, (int64_t)L.w_small_part + sp_off, cols, WARP_SMALL_PART, wgrid));
       };
       for (int l = 0; l < WARP_DEPTH; ++l) wsmall(w.trunk_b[l], WARP_W, l * WARP_W);
       wsmall(w.w_b, 3, 768);
       wsmall(w.v_b, 3, 771);
-    };
-    // bf16 groups: slab [Kb*32][Nb*32] per segment (+ a bias slab [Nb*32]); the leaf takes a column window of it
-    for (size_t i = 0; i < bspecs.size(); ++i) {
-      const BSpec& sp = bspecs[i];
-      WgradGroup g;
-      memset(&g, 0, sizeof(g));
-      g.x_off = (int64_t)(*sp.xoff + sp.xadd); g.x_tile_stride = (sp.Kb - sp.Kb2) * BF_BLOCK_DW; g.Kb = sp.Kb; g.x_kvalid = sp.rows;
-      g.dy_off = (int64_t)(*sp.yoff + sp.yadd); g.dy_tile_stride = (sp.Nb - sp.Nb2) * BF_BLOCK_DW; g.Nb = sp.Nb;
-      g.Kb1 = sp.Kb - sp.Kb2; g.Nb1 = sp.Nb - sp.Nb2;
-      g.x2_off = sp.x2off ? (int64_t)*sp.x2off : g.x_off; g.x2_tile_stride = sp.x2off ? sp.x2_blocks * BF_BLOCK_DW : 0;
-      g.dy2_off = sp.y2off ? (int64_t)*sp.y2off : g.dy_off; g.dy2_tile_stride = sp.y2off ? sp.y2_blocks * BF_BLOCK_DW : 0;
-      g.ntiles = sp.ngroups ? sp.ngroups : p.L[sp.lv].b_ngroups; g.nsplit = bnsplit[i]; g.vec_off = -1; g.vec2_off = -1;
-      g.slab_off = (int64_t)take((size_t)g.nsplit * sp.Kb * 32 * sp.Nb * 32);
-      g.vslab_off = sp.bias_dst >= 0 ? (int64_t)take((size_t)g.nsplit * sp.Nb * 32) : -1;
-      p.bgroups.push_back(g);
-      ReduceDesc r;
-      memset(&r, 0, sizeof(r));
-      r.dst_off = sp.dst; r.dst_ld = sp.dst_ld; r.rows = sp.rows; r.cols = sp.cols;
-      r.src_off = g.slab_off + sp.col0; r.src_ld = sp.Nb * 32; r.part_stride = (int64_t)sp.Kb * 32 * sp.Nb * 32; r.nparts = g.nsplit;
-      r.accumulate = sp.accu;
-      auto rpush = [&](const ReduceDesc& q) {
-        (q.accumulate == 0 ? p.reduce : q.accumulate == 1 ? reduce2 : q.accumulate == 2 ? reduce3 : reduce4).push_back(q);
-      };
-      rpush(r);
-      if (sp.dst2 >= 0) {   // a second leaf out of the same slab (column window col20)
-        ReduceDesc r2 = r;
-        r2.dst_off = sp.dst2; r2.src_off = g.slab_off + sp.col20;
-        if (sp.dst2_cols > 0) { r2.dst_ld = sp.dst2_ld; r2.cols = sp.dst2_cols; }
-        rpush(r2);
-      }
-      auto bias = [&](int64_t dst, int cols, int col0) {
-        ReduceDesc b;
-        memset(&b, 0, sizeof(b));
-        b.dst_off = dst; b.dst_ld = cols; b.rows = 1; b.cols = cols; b.accumulate = sp.accu;
-        b.src_off = g.vslab_off + col0; b.src_ld = sp.Nb * 32; b.part_stride = sp.Nb * 32; b.nparts = g.nsplit;
-        rpush(b);
-      };
-      if (sp.bias_dst >= 0) bias(sp.bias_dst, sp.bias_cols, 0);
-      if (sp.bias2_dst >= 0) bias(sp.bias2_dst, sp.bias2_cols, sp.bias2_col0);
-    }
-    // bias gradients and per-ray condition rows
-    for (int lv = 0; lv < h->nlevels; ++lv) {
-      const MlpParamOffsets& po = h->po[lv];
-      const LevelWs& L = p.L[lv];
-      int nt_mlp = 0;
-      for (int q = 0; q < h->nlevels; ++q) nt_mlp += p.ntiles[q];
-      // ONE dgrad launch over the tiles of all levels: two workgroups per CU on 64-row tiles, four on 32-row half tiles
-      const int grid = p.bwd32 ? (2 * nt_mlp < 4 * G ? 2 * nt_mlp : 4 * G) : (nt_mlp < 2 * G ? nt_mlp : 2 * G);
-      auto small = [&](int64_t dst, int cols, int sp_off) {
-        if (bft) return;   // the bf16 wgrad kernel sums the bias columns itself
-        ReduceDesc r;
-        memset(&r, 0, sizeof(r));
-        r.dst_off = dst; r.dst_ld = cols; r.rows = 1; r.cols = cols;
-        r.src_off = (int64_t)L.small_part + sp_off; r.src_ld = cols; r.part_stride = SMALL_PART; r.nparts = grid;
-        p.reduce.push_back(r);
-      };
-      for (int l = 0; l < TRUNK_DEPTH; ++l) small(po.trunk_b[l], 256, l * 256);
-      small(po.bn_b, 256, 2048);
-      small(po.rgbh_b, 128, 2304);
-      small(po.logit_b, 3, 2432);
-      small(po.alpha_b, 1, 2435);
-      if (h->R > 0) {
-        ReduceDesc r;
-        memset(&r, 0, sizeof(r));
-        r.dst_off = po.rgbh_k + 256 * 128; r.dst_ld = 128; r.rows = h->R; r.cols = 128;
-        r.src_off = (int64_t)L.cond_grad; r.src_ld = 128; r.part_stride = 0; r.nparts = 1;
-        p.reduce.push_back(r);
-      }
-      if (h->warp && !bfw && lv == 0) {   // ONE SE3 dgrad launch (coarse + fine + background tiles), one set of bias partials
-        const int nt_w = nt_mlp + (bgN > 0 ? p.ntiles[BG] : 0);
-        warp_bias_descs(0, nt_w < warp_grid_mul() * G ? nt_w : warp_grid_mul() * G, 0);
-      }
     }
   }
-  {
-    // Every pass of a destination in ONE launch: the descriptors that add into a leaf (the SE3 field's: fine level, tangent pass,
-    // background batch) are chained behind the pass-0 descriptor of the same destination window; a workgroup column of reduce_kernel
-    // walks the chain with one element -> thread mapping.  Heads first (the launch's grid), chained descriptors behind them.
-    std::vector<ReduceDesc> all = p.reduce;
-    all.insert(all.end(), reduce2.begin(), reduce2.end());
-    all.insert(all.end(), reduce3.begin(), reduce3.end());
-    all.insert(all.end(), reduce4.begin(), reduce4.end());
-    auto wide_ok = [](const ReduceDesc& d) {
-      return ((d.cols | d.src_ld | d.dst_ld) & 3) == 0 && (d.part_stride & 3) == 0 && (d.src_off & 3) == 0 && (d.dst_off & 3) == 0;
-    };
-    const int n = (int)all.size();
-    std::vector<int> prev(n, -1), nxt(n, -1);
-    for (int i = 0; i < n; ++i) {
-      if (all[i].accumulate == 0) continue;
-      for (int j = i - 1; j >= 0; --j)   // the latest earlier descriptor of the same destination window that is still a chain's tail
-        if (nxt[j] < 0 && all[j].dst_off == all[i].dst_off && all[j].rows == all[i].rows && all[j].cols == all[i].cols &&
-            all[j].dst_ld == all[i].dst_ld && all[j].accumulate < all[i].accumulate) { prev[i] = j; nxt[j] = i; break; }
-    }
-    std::vector<int> order, pos(n, -1);
-    for (int i = 0; i < n; ++i) if (prev[i] < 0 && all[i].accumulate == 0) order.push_back(i);          // heads of pass 0
-    const int nheads0 = (int)order.size();
-    for (int i = 0; i < n; ++i) if (prev[i] >= 0) order.push_back(i);                                    // chained
-    const int nchained_end = (int)order.size();
-    for (int i = 0; i < n; ++i) if (prev[i] < 0 && all[i].accumulate != 0) order.push_back(i);          // no pass-0 partner: a second launch
-    for (int k = 0; k < (int)order.size(); ++k) pos[order[k]] = k;
-    p.reduce.clear();
-    for (int k = 0; k < (int)order.size(); ++k) {
-      ReduceDesc d = all[order[k]];
-      d.next = nxt[order[k]] >= 0 ? pos[nxt[order[k]]] : -1;
-      p.reduce.push_back(d);
-    }
-    for (int k = 0; k < (int)p.reduce.size(); ++k) {   // one mapping per chain, chosen at its head
-      if (k >= nheads0 && k < nchained_end) continue;
-      bool tall = p.reduce[k].rows == 1, wide = true, big = false;
-      for (int q = k; q >= 0; q = p.reduce[q].next) { wide = wide && wide_ok(p.reduce[q]); big = big || p.reduce[q].nparts >= 64; }
-      const int path = (tall && big) ? 2 : wide ? 1 : 0;
-      for (int q = k; q >= 0; q = p.reduce[q].next) p.reduce[q].path = path;
-    }
-    p.nreduce_pass[0] = nheads0;
-    p.nreduce_pass[1] = nchained_end - nheads0;            // reached through `next`, not launched
-    p.nreduce_pass[2] = (int)order.size() - nchained_end;  // launched second (empty in every configuration built so far)
-    p.nreduce_pass[3] = 0;
+}
+
+// Every pass of a destination in ONE launch: the descriptors that add into a leaf (the SE3 field's: fine level, tangent pass,
+// background batch) are chained behind the pass-0 descriptor of the same destination window; a workgroup column of reduce_kernel
+// walks the chain with one element -> thread mapping.  Heads first (the launch's grid), chained descriptors behind them.
+void Planner::chain_reduces() {
+  std::vector<ReduceDesc> all;
+  for (const std::vector<ReduceDesc>& pass : by_pass) all.insert(all.end(), pass.begin(), pass.end());
+  auto wide_ok = [](const ReduceDesc& d) {
+    return ((d.cols | d.src_ld | d.dst_ld) & 3) == 0 && (d.part_stride & 3) == 0 && (d.src_off & 3) == 0 && (d.dst_off & 3) == 0;
+  };
+  const int n = (int)all.size();
+  std::vector<int> prev(n, -1), nxt(n, -1);
+  for (int i = 0; i < n; ++i) {
+    if (all[i].accumulate == 0) continue;
+    for (int j = i - 1; j >= 0; --j)   // the latest earlier descriptor of the same destination window that is still a chain's tail
+      if (nxt[j] < 0 && all[j].dst_off == all[i].dst_off && all[j].rows == all[i].rows && all[j].cols == all[i].cols &&
+          all[j].dst_ld == all[i].dst_ld && all[j].accumulate < all[i].accumulate) { prev[i] = j; nxt[j] = i; break; }
   }
-  // ---- descriptor tables (bytes), sized from what was actually built (round 2 reserved 64 pack / 192 reduce
-  //      descriptors without a check) ----
-  p.pack_off_b = 0;
-  p.groups_off_b = align_up((p.pack.size() + 1) * sizeof(PackDesc), 256);
-  p.reduce_off_b = p.groups_off_b + align_up(specs.size() * sizeof(WgradGroup) + 256, 256);
-  p.segs_off_b = p.reduce_off_b + align_up((p.reduce.size() + 1) * sizeof(ReduceDesc), 256);
-  p.segbegin_off_b = p.segs_off_b + align_up(p.segs.size() * sizeof(WgradSegment) + 256, 256);
-  p.emb_off_b = p.segbegin_off_b + align_up((p.seg_begin.size() + 1) * sizeof(int), 256);
-  p.bgroups_off_b = p.emb_off_b + align_up((h->emb.size() + 1) * sizeof(EmbedDesc), 256);
-  p.bsegs_off_b = p.bgroups_off_b + align_up(bspecs.size() * sizeof(WgradGroup) + 256, 256);
-  p.bsegbegin_off_b = p.bsegs_off_b + align_up(p.bsegs.size() * sizeof(WgradSegment) + 256, 256);
-  const size_t table_bytes = p.bsegbegin_off_b + align_up((p.bseg_begin.size() + 1) * sizeof(int), 256);
-  p.tables = take(table_bytes / 4);
-  p.total_floats = o;
+  std::vector<int> order, pos(n, -1);
+  for (int i = 0; i < n; ++i) if (prev[i] < 0 && all[i].accumulate == 0) order.push_back(i);          // heads of pass 0
+  const int nheads0 = (int)order.size();
+  for (int i = 0; i < n; ++i) if (prev[i] >= 0) order.push_back(i);                                    // chained
+  const int nchained_end = (int)order.size();
+  for (int i = 0; i < n; ++i) if (prev[i] < 0 && all[i].accumulate != 0) order.push_back(i);          // no pass-0 partner: a second launch
+  for (int k = 0; k < (int)order.size(); ++k) pos[order[k]] = k;
+  p.reduce.clear();
+  for (int k = 0; k < (int)order.size(); ++k) {
+    ReduceDesc d = all[order[k]];
+    d.next = nxt[order[k]] >= 0 ? pos[nxt[order[k]]] : -1;
+    p.reduce.push_back(d);
+  }
+  for (int k = 0; k < (int)p.reduce.size(); ++k) {   // one mapping per chain, chosen at its head
+    if (k >= nheads0 && k < nchained_end) continue;
+    bool tall = p.reduce[k].rows == 1, wide = true, big = false;
+    for (int q = k; q >= 0; q = p.reduce[q].next) { wide = wide && wide_ok(p.reduce[q]); big = big || p.reduce[q].nparts >= 64; }
+    const int path = (tall && big) ? 2 : wide ? 1 : 0;
+    for (int q = k; q >= 0; q = p.reduce[q].next) p.reduce[q].path = path;
+  }
+  p.nreduce_pass[0] = nheads0;
+  p.nreduce_pass[1] = nchained_end - nheads0;            // reached through `next`, not launched
+  p.nreduce_pass[2] = (int)order.size() - nchained_end;  // launched second (empty in every configuration built so far)
+  p.nreduce_pass[3] = 0;
+}
+
+// ---- descriptor tables (bytes) ----
+void Planner::tables() {
+  size_t bytes = 0;
+  for (const Table& t : tables_of(h)) {
+    *t.off_b = bytes;
+    bytes += align_up(t.bytes + t.slack, 256);
+  }
+  p.tables = take(bytes / 4);
+}
+
+}  // namespace
+
+// Lays out the workspace for B rays and (re)builds the descriptor tables.  The order of the take() calls is the layout: padded
+// parameter image, bf16 weight streams, per-level buffers (counters and timeline last), wgrad slabs, descriptor tables.
+void build_plan(nrf_handle h, int B, uint32_t flags, int bgN, int elastic) {
+  const PlanKey key{B, plan_flags(flags), bgN, elastic, h->chain_rows_opt, h->bf16_wgrad_merge};
+  if (h->plan.key == key) return;
+  static std::atomic<uint64_t> next_serial{1};   // handles may be planned from several host threads
+  h->plan = WsPlan();
+  h->plan.key = key;
+  h->plan.serial = next_serial++;
+  Planner s(h, key.flags);
+  s.shapes();
+  s.wgrad_specs();
+  s.cut_wgrad();
+  if (h->embed) {
+    h->plan.iparams = s.take((size_t)h->nparams);
+    if (s.train) h->plan.igrad = s.take((size_t)h->nparams);
+  }
+  if (!s.train || s.bft) s.weight_streams();
+  s.buffers();
+  s.pack_descs();
+  if (s.train) {
+    s.fp32_groups();
+    s.bf16_groups();
+    s.bias_reduces();
+  }
+  s.chain_reduces();
+  s.tables();
+  h->plan.total_floats = s.o;
 }
 
 int upload_tables(nrf_handle h, float* ws, hipStream_t stream) {
   WsPlan& p = h->plan;
-  if (h->uploaded_ws == (void*)ws && h->uploaded_B == p.B && h->uploaded_flags == p.flags && h->uploaded_bgN == p.bgN && h->uploaded_elastic == p.elastic) return NRF_OK;
+  if (h->uploaded_ws == (void*)ws && h->uploaded_key == p.key) return NRF_OK;
   char* base = reinterpret_cast<char*>(ws + p.tables);
-  hipError_t e;
-  if (!p.pack.empty()) {
-    e = hipMemcpyAsync(base + p.pack_off_b, p.pack.data(), p.pack.size() * sizeof(PackDesc), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return fail_hip(e, "upload pack table");
+  for (const Table& t : tables_of(h)) {
+    if (!t.upload || !t.bytes) continue;
+    const hipError_t e = hipMemcpyAsync(base + *t.off_b, t.data, t.bytes, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return fail_hip(e, t.what);
   }
-  if (!p.groups.empty()) {
-    e = hipMemcpyAsync(base + p.groups_off_b, p.groups.data(), p.groups.size() * sizeof(WgradGroup), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return fail_hip(e, "upload wgrad table");
-  }
-  if (!p.segs.empty()) {
-    e = hipMemcpyAsync(base + p.segs_off_b, p.segs.data(), p.segs.size() * sizeof(WgradSegment), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return fail_hip(e, "upload wgrad segments");
-    e = hipMemcpyAsync(base + p.segbegin_off_b, p.seg_begin.data(), p.seg_begin.size() * sizeof(int), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return fail_hip(e, "upload wgrad segment index");
-  }
-  if (!p.bfpack.empty()) {
-    e = hipMemcpyAsync(ws + p.bf_desc, p.bfpack.data(), p.bfpack.size() * sizeof(RcPackDesc), hipMemcpyHostToDevice, stream);
+  if (!p.bfpack.empty()) {   // the bf16 pack table has a region of its own
+    const hipError_t e = hipMemcpyAsync(ws + p.bf_desc, p.bfpack.data(), p.bfpack.size() * sizeof(RcPackDesc), hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) return fail_hip(e, "upload bf16 pack table");
   }
-  if (!p.bgroups.empty()) {
-    e = hipMemcpyAsync(base + p.bgroups_off_b, p.bgroups.data(), p.bgroups.size() * sizeof(WgradGroup), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return fail_hip(e, "upload bf16 wgrad table");
-    e = hipMemcpyAsync(base + p.bsegs_off_b, p.bsegs.data(), p.bsegs.size() * sizeof(WgradSegment), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return fail_hip(e, "upload bf16 wgrad segments");
-    e = hipMemcpyAsync(base + p.bsegbegin_off_b, p.bseg_begin.data(), p.bseg_begin.size() * sizeof(int), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return fail_hip(e, "upload bf16 wgrad segment index");
-  }
-  if (h->embed) {
-    e = hipMemcpyAsync(base + p.emb_off_b, h->emb.data(), h->emb.size() * sizeof(EmbedDesc), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return fail_hip(e, "upload embed table");
-  }
-  if (!p.reduce.empty()) {
-    e = hipMemcpyAsync(base + p.reduce_off_b, p.reduce.data(), p.reduce.size() * sizeof(ReduceDesc), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return fail_hip(e, "upload reduce table");
-  }
   h->uploaded_ws = ws;
-  h->uploaded_B = p.B;
-  h->uploaded_flags = p.flags;
-  h->uploaded_bgN = p.bgN;
-  h->uploaded_elastic = p.elastic;
+  h->uploaded_key = p.key;
   return NRF_OK;
 }
 

@@ -54,7 +54,7 @@ ChainFwdArgs fwd_args(nrf_handle h, int lv, const float* params, const nrf_rays*
   a.params = params; a.po = h->po[lv]; a.wpk = ws + L.wpk; a.pk = h->pk;
   a.condterm = ws + L.condterm; a.zvals = ws + L.z; a.origins = rays->origins; a.directions = rays->directions;
   a.points = nullptr; a.out4 = reinterpret_cast<float4*>(ws + L.out4);
-  a.S = p.S[lv]; a.B = p.B; a.rows = p.rows[lv]; a.ntiles = p.ntiles[lv];
+  a.S = p.S[lv]; a.B = p.key.B; a.rows = p.rows[lv]; a.ntiles = p.ntiles[lv];
   a.F = h->d.num_nerf_point_freqs; a.P = h->P; a.PK = h->PK; a.sigma_act = h->d.sigma_activation; a.skip = h->d.nerf_skip_layer;
   a.tile_counter = tile_counter_or_null(ws + p.counters, CT_MLP_FWD + lv);
   a.timeline = knobs().timeline ? reinterpret_cast<unsigned long long*>(ws + p.timeline) + lv * (256 + 512 + 4 * 2048) : nullptr;
@@ -65,7 +65,7 @@ ChainFwdArgs fwd_args(nrf_handle h, int lv, const float* params, const nrf_rays*
     a.noise_seed = rnd ? rnd->seed : 0; a.noise_offset = rnd ? rnd->offset : 0; a.noise_stream = 2u + (unsigned)lv;
     a.dyn = dyn;
   }
-  if (train && (p.flags & NRF_FLAG_BF16)) {
+  if (train && (p.key.flags & NRF_FLAG_BF16)) {
     a.bst = bf_stash(p, lv, ws);
   } else if (train) {
     a.st_pe = ws + L.st_pe; a.st_h = ws + L.st_h; a.st_bn = ws + L.st_bn; a.st_rgbh = ws + L.st_rgbh;
@@ -116,7 +116,7 @@ WarpFwdArgs warp_fwd_args(nrf_handle h, int lv, const float* params, const nrf_r
   a.warp_ids = per_ray ? nullptr : rays->warp_ids;
   a.embed_table = rays->warp_codes ? rays->warp_codes : h->time_enc ? ws + p.t_codes : params + h->wpo.embed;
   a.points_out = ws + L.wpoints; a.points_raw = ws + L.points_raw;
-  a.S = p.S[lv]; a.B = p.B; a.rows = p.rows[lv]; a.ntiles = p.ntiles[lv];
+  a.S = p.S[lv]; a.B = p.key.B; a.rows = p.rows[lv]; a.ntiles = p.ntiles[lv];
   a.F = h->Fw; a.G = h->G; a.Win = h->Win; a.PKw = h->PKw; a.alpha = alpha; a.dyn = sc->dynamic;
   a.tile_counter = tile_counter_or_null(ws + p.counters, CT_WARP_FWD + lv);
   if (train) {   // train: here "keep the stash" (training plan, or an inference plan that returns the Jacobian)
@@ -164,7 +164,8 @@ int forward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, cons
   build_plan(h, B, flags, bgN, elastic);
   WsPlan& p = h->plan;
   if (ws_bytes < p.total_floats * sizeof(float)) return fail(NRF_E_WORKSPACE, "workspace too small (see nrf_workspace_bytes)");
-  if (!p.bf_stream_ok) return fail(NRF_E_STATE, "bf16 weight stream tables do not match the kernels' chunk sequence");
+  if ((flags & (NRF_FLAG_BF16 | NRF_FLAG_BF16X3)) && !p.bf_stream_ok)   // the bf16 / x3 chains' streams (launch_bf16_pack below)
+    return fail(NRF_E_STATE, "bf16 weight stream tables do not match the kernels' chunk sequence");
   const nrf_model_desc& d = h->d;
   const bool train = flags & NRF_FLAG_TRAIN;
   const bool warp_on = h->warp && !(flags & NRF_FLAG_NO_WARP);   // models.py:296 use_warp argument
@@ -217,7 +218,7 @@ int forward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, cons
   const nrf_dynamic_scalars* dyn = scalars ? scalars->dynamic : nullptr;
   launch_sample_coarse(rnd ? rnd->t_rand : nullptr, B, p.S[0], d.near_plane, d.far_plane, d.use_stratified_sampling,
                        d.use_linear_disparity, rnd ? rnd->seed : 0, rnd ? rnd->offset : 0, dyn, ws + p.L[0].z, stream);
-  if (train && bg && p.bgN > 0 && warp_on) draw_background(h, bg, rnd, scalars, ws, stream);
+  if (train && bg && p.key.bgN > 0 && warp_on) draw_background(h, bg, rnd, scalars, ws, stream);
   pf.end(stream);
   if (warp_on && h->time_enc && !rays->warp_codes) {   // modules.TimeEncoder once per ray (warping.py:311-313, models.py:252-254)
     TimeEncArgs ta;
@@ -243,12 +244,12 @@ int forward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, cons
                          : (p.ntiles[lv] < gmul * h->num_cus ? p.ntiles[lv] : gmul * h->num_cus);   // two workgroups per CU
     if (warp_on) {
       // the background-point batch of the fused train step rides in the coarse launch (its 256 tiles under-fill the chip)
-      const bool with_bg = lv == 0 && train && bg && p.bgN > 0;
+      const bool with_bg = lv == 0 && train && bg && p.key.bgN > 0;
       WarpFwdArgs bga;
       if (with_bg) bga = bg_fwd_args(h, params, bg, scalars, ws);
       const int wnt = p.ntiles[lv] + (with_bg ? p.ntiles[BG] : 0);
       const int wgrid = wnt < warp_grid_mul() * h->num_cus ? wnt : warp_grid_mul() * h->num_cus;
-      pf.begin(lv == 0 ? "warp_fwd_coarse" : "warp_fwd_fine", warp_fwd_flops_row(h) * (p.rows[lv] + (with_bg ? p.bgN : 0)), stream);
+      pf.begin(lv == 0 ? "warp_fwd_coarse" : "warp_fwd_fine", warp_fwd_flops_row(h) * (p.rows[lv] + (with_bg ? p.key.bgN : 0)), stream);
       if (x3 && !jac && !(flags & NRF_FLAG_WARP_F32)) {   // SE3 trunk in split-bf16 arithmetic (warp_bf16x3.hip); the Jacobian output keeps the float32 kernels (their input stash)
         WarpFwdArgs wa = warp_fwd_args(h, lv, params, rays, scalars, ws, false);
         wa.bwpk = ws + p.bfw_wpk; wa.rows_pad = p.ntiles[lv] * TILE_ROWS;
@@ -268,7 +269,7 @@ int forward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, cons
       // forward-mode Jacobian of the warp: on the coarse samples for the elastic regulariser (models.py:345), per level
       // as an output (return_warp_jacobian, models.py:345-346, 367-368)
       float* jout = !out ? nullptr : lv == 0 ? out->coarse.warp_jacobian : out->fine.warp_jacobian;
-      if ((lv == 0 && train && p.elastic) || (jac && jout)) launch_tangent_fwd(h, lv, params, rays, scalars, ws, gmul, stream);
+      if ((lv == 0 && train && p.key.elastic) || (jac && jout)) launch_tangent_fwd(h, lv, params, rays, scalars, ws, gmul, stream);
       if (jac && jout) {
         JacobianArgs ja;
         memset(&ja, 0, sizeof(ja));   // x_rows = nullptr: the points come from the fp32 input stash
@@ -337,7 +338,7 @@ WarpFwdArgs bg_fwd_args(nrf_handle h, const float* params, const nrf_background*
   fa.params = params; fa.po = h->wpo; fa.wpk = ws + p.warp_wpk; fa.pk = h->wpk;
   fa.points_in = bg_points_of(p, bg, ws); fa.point_ids = bg_ids_of(p, bg, ws); fa.points_out = ws + L.wpoints;
   fa.embed_table = params + h->wpo.embed;
-  fa.S = 1; fa.B = p.bgN; fa.rows = p.bgN; fa.ntiles = p.ntiles[BG];
+  fa.S = 1; fa.B = p.key.bgN; fa.rows = p.key.bgN; fa.ntiles = p.ntiles[BG];
   fa.F = h->Fw; fa.G = h->G; fa.Win = h->Win; fa.PKw = h->PKw; fa.alpha = sc->warp_alpha; fa.dyn = sc->dynamic;
   fa.st_win = ws + L.w_st_win; fa.st_h = ws + L.w_st_h; fa.st_wv = reinterpret_cast<float4*>(ws + L.w_st_wv);
   fa.bits = reinterpret_cast<uint32_t*>(ws + L.w_bits);
@@ -348,7 +349,7 @@ WarpFwdArgs bg_fwd_args(nrf_handle h, const float* params, const nrf_background*
 void draw_background(nrf_handle h, const nrf_background* bg, const nrf_rand* rnd, const nrf_step_scalars* sc, float* ws, hipStream_t stream) {
   const WsPlan& p = h->plan;
   if (bg->warp_ids) return;
-  launch_background_draw(bg->points, p.bgN, bg->id_choices, bg->num_choices, bg->noise_std, rnd ? rnd->seed : 0, rnd ? rnd->offset : 0,
+  launch_background_draw(bg->points, p.key.bgN, bg->id_choices, bg->num_choices, bg->noise_std, rnd ? rnd->seed : 0, rnd ? rnd->offset : 0,
                          sc ? sc->dynamic : nullptr, ws + p.bg_points, reinterpret_cast<int32_t*>(ws + p.bg_ids), stream);
 }
 
@@ -362,7 +363,7 @@ int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, con
                   bool bg_forward_done) {
   WsPlan& p = h->plan;
   const nrf_model_desc& d = h->d;
-  const int B = p.B;
+  const int B = p.key.B;
   const bool warp_on = h->stashed_warp;
   const char* tables = reinterpret_cast<const char*>(ws + p.tables);
   // narrower model: the stashed forward left the padded parameter image in the workspace; gradients are formed
@@ -372,9 +373,9 @@ int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, con
   if ((reinterpret_cast<uintptr_t>(grad_x) & 15u) != 0) return fail(NRF_E_SHAPE, "grad_params must be 16-byte aligned");
   float* grad = h->embed ? ws + p.igrad : grad_x;
   const bool wr_on = wr && warp_on;
-  const bool bg_on = bg && p.bgN > 0;
-  const bool el_on = el && p.elastic && warp_on;
-  const bool bft = p.flags & NRF_FLAG_BF16;
+  const bool bg_on = bg && p.key.bgN > 0;
+  const bool el_on = el && p.key.elastic && warp_on;
+  const bool bft = p.key.flags & NRF_FLAG_BF16;
   {   // everything that is accumulated into, zeroed by one launch
     ZeroArgs z;
     memset(&z, 0, sizeof(z));
@@ -496,7 +497,7 @@ int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, con
     // the background batch's warp forward ran inside the coarse warp launch of the fused train step (the only caller that
     // passes `bg`: nrf_backward has no background argument)
     if (!bg_forward_done) return fail(NRF_E_STATE, "background regulariser without its forward pass");
-    launch_background_loss(bg_points_of(p, bg, ws), ws + L.wpoints, p.bgN, p.ntiles[BG] * TILE_ROWS, bg->loss_alpha, bg->loss_scale,
+    launch_background_loss(bg_points_of(p, bg, ws), ws + L.wpoints, p.key.bgN, p.ntiles[BG] * TILE_ROWS, bg->loss_alpha, bg->loss_scale,
                            bg->loss_weight, ws + L.d_points, ws + p.bg_loss, stream);
   }
   if (warp_on) {
@@ -528,7 +529,7 @@ int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, con
     if (bg_on) {
       WarpBwdArgs& w = wa[nlev++];
       common(w, BG);
-      w.B = p.bgN; w.S = 1;
+      w.B = p.key.bgN; w.S = 1;
       w.point_ids = bg_ids_of(p, bg, ws);
       w.grad_embed = grad + h->wpo.embed;
     }
@@ -594,7 +595,7 @@ int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, con
   double wg_rows = mlp_rows;
   // the SE3 groups also run over the background rows and, with the elastic regulariser, over the three tangent rows per
   // coarse sample (warping.py:385-387 jacfwd): algorithmic work of the step, counted
-  double warp_wg_rows = warp_on ? mlp_rows + (bg_on ? p.bgN : 0) + (el_on ? 3.0 * p.rows[0] : 0.0) : 0.0;
+  double warp_wg_rows = warp_on ? mlp_rows + (bg_on ? p.key.bgN : 0) + (el_on ? 3.0 * p.rows[0] : 0.0) : 0.0;
   if (!p.segs.empty()) {
     h->prof.begin("wgrad", (bft ? 0.0 : wgrad_flops_row(h)) * wg_rows + warp_fwd_flops_row_or0(h) * warp_wg_rows, stream);
     launch_wgrad(reinterpret_cast<const WgradGroup*>(tables + p.groups_off_b),
@@ -624,7 +625,7 @@ int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, con
     StatsArgs sa;
     memset(&sa, 0, sizeof(sa));
     sa.mse_ray = ws + p.mse; sa.B = B; sa.nlevels = h->nlevels;
-    if (bg_on) { sa.bg_sum = ws + p.bg_loss; sa.bgN = p.bgN; sa.bg_weight = bg->loss_weight; }
+    if (bg_on) { sa.bg_sum = ws + p.bg_loss; sa.bgN = p.key.bgN; sa.bg_weight = bg->loss_weight; }
     if (el_on) {
       sa.el_part = ws + p.el_sums; sa.el_nwg = (p.ntiles[0] * TILE_ROWS + 255) / 256; sa.el_rows = el->reduce_method == NRF_ELASTIC_MEDIAN ? B : p.rows[0]; sa.el_jac_rows = p.rows[0];
       sa.el_weight = el->loss_weight;
