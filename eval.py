@@ -103,6 +103,11 @@ def main(argv=None):
       20200823, model_config, batch_size=eval_config.chunk, appearance_ids=datasource.appearance_ids,
       camera_ids=datasource.camera_ids, warp_ids=datasource.warp_ids, near=datasource.near, far=datasource.far,
       use_warp_jacobian=False, use_weights=False, device=device)
+  if flags.bf16:   # as train.py: a model shape the bfloat16 / split-bf16 chains do not run is refused with the library's reason
+    try:
+      model.check_mode(flags.bf16)
+    except models.L.NrfError as e:
+      raise SystemExit(f'--bf16: {e}')
   init_state = training.TrainState(optimizer=training.Optimizer(params))
   renderer = evaluation.GraphedChunkRenderer(model, bf16=flags.bf16)   # hipGraph replay per chunk
   render_fn = functools.partial(evaluation.render_image, model_fn=renderer, device_count=world, chunk=eval_config.chunk)

@@ -37,7 +37,10 @@
 extern "C" {
 #endif
 
-#define NRF_VERSION 600 /* 0.6.0: nrf_model_desc grows warp_trunk_depth / warp_trunk_width (SE3Field / TranslationField trunk_depth <= 6,
+#define NRF_VERSION 610 /* 0.6.1: nerf_rgb_branch_depth accepts 1..4 (float32 mode, 64-row chains; the bfloat16 / split-bf16 modes and
+                           NRF_OPT_CHAIN_TILE_ROWS = 32 are refused for a handle with depth > 1); the parameter layout then holds
+                           MLP_1/hidden_1.. of both levels.  Nothing changes for depth 1.
+                           0.6.0: nrf_model_desc grows warp_trunk_depth / warp_trunk_width (SE3Field / TranslationField trunk_depth <= 6,
                            trunk_width <= 128 of ModelConfig.warp_kwargs); nerf_skip_layer accepts any single index 1..7 (float32
                            mode; the bfloat16 mode where the trunk can be laid out around the chains' layer 4); NRF_FLAG_BF16X3 (split-bf16,
                            float32-emulating inference chains).  Behaviour change
@@ -75,7 +78,10 @@ typedef struct nrf_model_desc {
   float far_plane;                 /* models.py:79  */
   int32_t nerf_trunk_depth;        /* 1..8; the kernels run 8 layers, a shallower trunk gets internal identity layers behind it */
   int32_t nerf_trunk_width;        /* <= 256; the kernels are 256 wide, narrower trunks run zero-padded (test_vrig.gin: 128) */
-  int32_t nerf_rgb_branch_depth;   /* 1   */
+  int32_t nerf_rgb_branch_depth;   /* 1..4 (modules.py:129-134): layer 0 reads [bottleneck, condition], layers 1.. are (width, width), leaves
+                                      MLP_1/hidden_1.. in flax order.  Depth > 1 runs the float32 64-row chains only: NRF_FLAG_BF16 /
+                                      NRF_FLAG_BF16X3 and NRF_OPT_CHAIN_TILE_ROWS = 32 -> NRF_E_UNSUPPORTED.  0 (the logits straight on
+                                      [bottleneck, condition]) and > 4 are refused by nrf_create */
   int32_t nerf_rgb_branch_width;   /* <= 128 (same) */
   int32_t nerf_skip_layer;         /* nerf_skips = (s,) -> s in 1..7 (modules.py:47-48: layer s reads [h, posenc]); -1 = none (or any index
                                       >= nerf_trunk_depth: never reached).  s <= 4 with nerf_trunk_depth - s <= 4 is laid out around the chains'
@@ -376,7 +382,8 @@ int nrf_debug_wgrad_segments(nrf_handle h, const void* workspace, double* out, i
 /* Test aid: float offset inside the workspace of an internal buffer of `level` (0 coarse, 1 fine, 2 background
  * points, 3 Jacobian tangents) for the last planned (num_rays, flags): "st_pe", "st_h", "st_bn", "st_rgbh",
  * "dy_trunk", "dy_bn", "dy_rgbh", "d_raw4", "z", "out4", "wpoints", "d_points", "w_st_win", "w_st_h", "w_st_wv",
- * "w_dy", "w_dw4", "w_dv4", "bits_trunk", "bits_rgbh", "w_bits".
+ * "w_dy", "w_dw4", "w_dv4", "bits_trunk", "bits_rgbh", "w_bits"; with nerf_rgb_branch_depth = D > 1 also "st_rgbx", "bits_rgbx",
+ * "dy_rgbx": the rgb branch layers 1..D-1 as [D-1][tiles] images of the "st_rgbh" / "bits_rgbh" / "dy_rgbh" kind (those keep meaning layer 0).
  * Stash tiles are [features][64 rows] in fragment order (csrc/chain_common.h frag_index); the ReLU sign bits are one
  * uint32 per (tile, wave, lane, column block): nibble q, bit e <-> tile row 4 * ((q&1) + 2*(lane>>5) + 4*(q>>1)) + e of
  * feature wave * 32 * NCB + 32 * cb + (lane & 31)  (NCB = 2 for the 256-wide trunk, 1 otherwise). */
@@ -397,7 +404,8 @@ int nrf_debug_plan_digest(nrf_handle h, uint64_t* digest);
  *                            0 = automatic (default: half tiles for forward launches that under-fill the 64-row grid).  The
  *                            forward results (and the stashes) are bit-identical under both tilings -- a ray's result does not
  *                            depend on the launch it rides in --, gradients agree to the order of float atomics; the workspace
- *                            layout does not depend on it. */
+ *                            layout does not depend on it.  A handle with nerf_rgb_branch_depth > 1 keeps the 64-row kernels at
+ *                            every launch size (automatic never picks half tiles for it) and refuses the value 32. */
 #define NRF_OPT_CHAIN_TILE_ROWS 1
 /*   NRF_OPT_BF16_WGRAD_MERGE bf16 training mode: 1 (default) = the weight-gradient GEMMs of the skip layer (X = [h4 | posenc]) and of
  *                            the bottleneck + alpha head (dY = [d bottleneck | d raw]) run as ONE group each, so dpre_4 and h8 are

@@ -234,6 +234,34 @@ __global__ __launch_bounds__(256, 2) void nerf_mlp_fwd_kernel(const ChainFwdArgs
       __syncthreads();
     }
 
+    // ---- rgb branch layers 1..nx (nerf_rgb_branch_depth = nx + 1, modules.py:41-50): Dense(128 -> 128)+ReLU on the LDS image of
+    //      the layer before; nx = 0 for every depth-1 model, which runs none of this ----
+#pragma unroll 1
+    for (int x = 0; x < A.nx; ++x) {
+      f32x16 acc1[2][1];
+      zero_acc<1>(acc1);
+      const int n = wave * 32 + j;
+      const float4* wx = wpk4 + ((A.pk.fwd_rgbx + x * RGB_W * RGB_W) / 4) + wave * 16 * 64;
+      const float bx = prm[A.po.rgbx_b[x] + n];
+      mfma_k_loop<1, true>(acc1, act, 8, wx, lane, prefetch_quad<1>(wx, lane));
+      const __amdgpu_buffer_rsrc_t st =
+          make_rsrc(STASH ? A.st_rgbx + ((size_t)x * A.ntiles + tile) * FRAG_TILE_128 : nullptr, FRAG_TILE_128 * 4);
+      __syncthreads();
+      uint32_t mb = 0u;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int g = q_granule(q, h);
+        float4 v4 = acc_piece<1>(acc1, 0, q);
+        v4.x += bx; v4.y += bx; v4.z += bx; v4.w += bx;
+        if (STASH) mb |= sign_nibble(v4) << (4 * q);
+        v4.x = relu(v4.x); v4.y = relu(v4.y); v4.z = relu(v4.z); v4.w = relu(v4.w);
+        *reinterpret_cast<float4*>(act + act_addr(n, g)) = v4;
+        if (STASH) buf_store4(v4, st, lane * 16, (wave * 8 + q) * 1024);
+      }
+      if (STASH) A.bits_rgbx[(((size_t)x * A.ntiles + tile) * 4 + wave) * 64 + lane] = mb;
+      __syncthreads();
+    }
+
     STAMP();   // rgb hidden done
     // ---- rgb logits Dense(128->3), sigmoid; sigma activation (models.py:276-277) ----
     {
@@ -315,7 +343,9 @@ void launch_chain_fwd(const ChainFwdArgs& a, bool stash, int grid, hipStream_t s
 // backward (data gradients; bias gradients accumulated per workgroup)
 // ---------------------------------------------------------------------------------------------
 // small_part layout (floats): db_trunk[8][256] | db_bn[256] | db_rgbh[128] | db_logit[3] | db_alpha
-constexpr int SP_DB_TRUNK = 0, SP_DB_BN = 2048, SP_DB_RGBH = 2304, SP_DB_LOGIT = 2432, SP_DB_ALPHA = 2435;
+//   ... | db_rgbx[3][128] (rgb branch layers 1..3; only written and reduced when the branch is deeper than one layer)
+constexpr int SP_DB_TRUNK = 0, SP_DB_BN = 2048, SP_DB_RGBH = 2304, SP_DB_LOGIT = 2432, SP_DB_ALPHA = 2435, SP_DB_RGBX = 2436;
+static_assert(SP_DB_RGBX + RGB_MAX_EXTRA * RGB_W <= SMALL_PART, "small_part too small for the rgb branch bias partials");
 
 // per-lane bias-gradient accumulators of one workgroup, carried across its tiles of one level
 struct BwdAcc {
@@ -330,6 +360,22 @@ __device__ __forceinline__ void bwd_acc_zero(BwdAcc& c) {
   c.db_bn[0] = c.db_bn[1] = 0.f;
   c.db_rgbh = 0.f;
   c.dsum[0] = c.dsum[1] = c.dsum[2] = c.dsum[3] = 0.f;
+}
+
+// Bias gradients of the rgb branch layers 1..nx.  The reverse kernel has no register to spare for more per-lane accumulators
+// (it sits at the 256-register bound), so these partials live in the workgroup's own small_part row: zeroed by the workgroup when
+// the kernel starts, added to once per tile by the one thread that owns feature n (lane half 0) -- no atomics, a fixed order.
+__device__ __forceinline__ void rgbx_bias_add(const ChainBwdArgs& A, int x, int n, int h, float bsum) {
+  const float v = bsum + __shfl_xor(bsum, 32);
+  if (h == 0) {
+    float* o = A.small_part + (size_t)blockIdx.x * SMALL_PART + SP_DB_RGBX + x * RGB_W + n;
+    *o += v;
+  }
+}
+__device__ __forceinline__ void rgbx_bias_zero(const ChainBwdArgs& A) {
+  const int lane = threadIdx.x & 63;
+  if (lane < 32)   // the threads rgbx_bias_add writes from: feature n = wave * 32 + lane
+    for (int x = 0; x < A.nx; ++x) A.small_part[(size_t)blockIdx.x * SMALL_PART + SP_DB_RGBX + x * RGB_W + (threadIdx.x >> 6) * 32 + lane] = 0.f;
 }
 
 // one 64-row tile of level A (tile = index inside the level)
@@ -364,23 +410,65 @@ __device__ __forceinline__ void bwd_tile(const ChainBwdArgs& A, const int tile, 
       const int lane = ln, j = ln & 31, h = ln >> 5;
       const int n = wave * 32 + j;
       const float w0 = prm[A.po.logit_k + 3 * n], w1 = prm[A.po.logit_k + 3 * n + 1], w2 = prm[A.po.logit_k + 3 * n + 2];
-      const uint32_t mb = A.bits_rgbh[((size_t)tile * 4 + wave) * 64 + lane];
-      const __amdgpu_buffer_rsrc_t dy = make_rsrc(A.dy_rgbh + (size_t)tile * FRAG_TILE_128, FRAG_TILE_128 * 4);
+      // the logits read the LAST rgb layer: layer nx's mask, dY image and bias partial when the branch is deeper than one layer
+      const int nx = A.nx;
+      const size_t xt = nx ? (size_t)(nx - 1) * A.ntiles + tile : 0;
+      const uint32_t mb = nx ? A.bits_rgbx[(xt * 4 + wave) * 64 + lane] : A.bits_rgbh[((size_t)tile * 4 + wave) * 64 + lane];
+      const __amdgpu_buffer_rsrc_t dy =
+          make_rsrc(nx ? A.dy_rgbx + xt * FRAG_TILE_128 : A.dy_rgbh + (size_t)tile * FRAG_TILE_128, FRAG_TILE_128 * 4);
+      float bsum = nx ? 0.f : db_rgbh;
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         const int g = q_granule(q, h);
         const float4 d0 = *reinterpret_cast<const float4*>(dr + 4 * g);
         const float4 d1 = *reinterpret_cast<const float4*>(dr + TILE_ROWS + 4 * g);
         const float4 d2 = *reinterpret_cast<const float4*>(dr + 2 * TILE_ROWS + 4 * g);
-        float4 v4 = make_float4(d0.x * w0 + d1.x * w1 + d2.x * w2, d0.y * w0 + d1.y * w1 + d2.y * w2,
-                                d0.z * w0 + d1.z * w1 + d2.z * w2, d0.w * w0 + d1.w * w1 + d2.w * w2);
+        // d0 w0 + d1 w1 + d2 w2 with the rounding steps spelled out (one product, two fused multiply-adds): left to the compiler's
+        // contraction, the grouping depends on the code around it, and the 32-row kernel (mlp_chain32.hip) must produce the same bits
+        auto dot3 = [&](float a0, float a1, float a2) { return fmaf(a2, w2, fmaf(a0, w0, __fmul_rn(a1, w1))); };
+        float4 v4 = make_float4(dot3(d0.x, d1.x, d2.x), dot3(d0.y, d1.y, d2.y), dot3(d0.z, d1.z, d2.z), dot3(d0.w, d1.w, d2.w));
         v4 = mask4(v4, (mb >> (4 * q)) & 15u);
-        db_rgbh += (v4.x + v4.y) + (v4.z + v4.w);
+        bsum += (v4.x + v4.y) + (v4.z + v4.w);
         *reinterpret_cast<float4*>(act + act_addr(n, g)) = v4;
         buf_store4(v4, dy, lane * 16, (wave * 8 + q) * 1024);
       }
+      if (nx) rgbx_bias_add(A, nx - 1, n, h, bsum);
+      else db_rgbh = bsum;
     }
     __syncthreads();
+    // ---- rgb branch layers nx..1 (none for a depth-1 branch):  dpre_{x-1} = (dpre_x . W_x^T) * mask_{x-1}; dpre_0 lands where the
+    //      depth-1 chain leaves it (LDS tile, dy_rgbh, db_rgbh), so everything below is the same for every depth ----
+#pragma unroll 1
+    for (int x = A.nx; x >= 1; --x) {
+      f32x16 acc1[2][1];
+      zero_acc<1>(acc1);
+      {
+        const float4* wx = wpk4 + ((A.pk.bwd_rgbxT + (x - 1) * RGB_W * RGB_W) / 4) + wave * 16 * 64;
+        mfma_k_loop<1, true>(acc1, act, 8, wx, lane, prefetch_quad<1>(wx, lane));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      const size_t xt = x > 1 ? (size_t)(x - 2) * A.ntiles + tile : 0;
+      const __amdgpu_buffer_rsrc_t dy =
+          make_rsrc(x > 1 ? A.dy_rgbx + xt * FRAG_TILE_128 : A.dy_rgbh + (size_t)tile * FRAG_TILE_128, FRAG_TILE_128 * 4);
+      __syncthreads();   // every wave has read dpre_x
+      int le = tid;
+      asm volatile("" : "+v"(le));   // epilogue-local lane constants
+      const int lane = le & 63, j = lane & 31, h = lane >> 5;
+      const int n = wave * 32 + j;
+      const uint32_t mb = x > 1 ? A.bits_rgbx[(xt * 4 + wave) * 64 + lane] : A.bits_rgbh[((size_t)tile * 4 + wave) * 64 + lane];
+      float bsum = 0.f;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int g = q_granule(q, h);
+        const float4 v4 = mask4(acc_piece<1>(acc1, 0, q), (mb >> (4 * q)) & 15u);
+        bsum += (v4.x + v4.y) + (v4.z + v4.w);
+        *reinterpret_cast<float4*>(act + act_addr(n, g)) = v4;
+        buf_store4(v4, dy, lane * 16, (wave * 8 + q) * 1024);
+      }
+      if (x > 1) rgbx_bias_add(A, x - 2, n, h, bsum);
+      else db_rgbh += bsum;
+      __syncthreads();
+    }
     // ---- per-ray sums of dpre_rgbh (gradient of the per-ray condition columns of the rgb branch):
     //      thread (n, half) walks 32 tile rows of feature n in LDS and flushes at ray boundaries ----
     {
@@ -651,6 +739,10 @@ __global__ __launch_bounds__(256, 2) void nerf_mlp_bwd_kernel(const ChainBwdArgs
   bwd_acc_zero(C);
   const int nt0 = P.nt0, ntot = P.ntot;
   int cur = -1;
+  if (P.a[0].nx > 0) {
+    rgbx_bias_zero(P.a[0]);
+    if (ntot > nt0) rgbx_bias_zero(P.a[1]);
+  }
   if ((int)blockIdx.x >= nt0 && nt0 > 0) bwd_flush(P.a[0], smem, C);   // no coarse tile for this workgroup: its partial is zero
 #pragma unroll 1
   for (int g = blockIdx.x; g < ntot; g += gridDim.x) {

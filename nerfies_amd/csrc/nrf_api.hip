@@ -46,8 +46,12 @@ int nrf_create(const nrf_model_desc* desc, nrf_handle* out) {
     return fail(NRF_E_UNSUPPORTED, "nerf_skips = (0,) (the first layer reading its input twice) is not built");
   if (d.nerf_trunk_width < 1 || d.nerf_trunk_width > TRUNK_W)   // narrower trunks run zero-padded (test_vrig.gin: 128)
     return fail(NRF_E_UNSUPPORTED, "nerf_trunk_width must be in [1,256]");
-  if (d.nerf_rgb_branch_depth != 1 || d.nerf_rgb_branch_width < 1 || d.nerf_rgb_branch_width > RGB_W)
-    return fail(NRF_E_UNSUPPORTED, "rgb branch must be 1 layer of width <= 128");
+  // rgb branch (modules.py:129-134): 1..4 layers; layer 0 reads [bottleneck, condition], layers 1.. are (width, width) and run
+  // under a run-time count in the float32 64-row chains.  Depth 0 (the logits straight on [bottleneck, condition]) is not built.
+  if (d.nerf_rgb_branch_depth < 1 || d.nerf_rgb_branch_depth > RGB_MAX_DEPTH)
+    return fail(NRF_E_UNSUPPORTED, "nerf_rgb_branch_depth must be in [1,4]");
+  if (d.nerf_rgb_branch_width < 1 || d.nerf_rgb_branch_width > RGB_W)
+    return fail(NRF_E_UNSUPPORTED, "nerf_rgb_branch_width must be in [1,128]");
   if (d.use_trunk_condition)   // models.py:203-204: never forwarded by construct_nerf, no preset; a silent no-op would change the layout
     return fail(NRF_E_UNSUPPORTED, "use_trunk_condition (trunk conditioning) is not built");
   if (d.use_alpha_condition && d.use_appearance_metadata && (d.num_appearance_features < 1 || d.num_appearance_features > 16))
@@ -150,6 +154,9 @@ static int check_flags(const nrf_handle_s* h, uint32_t flags) {
   if ((flags & (NRF_FLAG_BF16 | NRF_FLAG_BF16X3)) && h->d.nerf_skip_layer != SKIP_LAYER)
     return fail(NRF_E_UNSUPPORTED, "NRF_FLAG_BF16: the bfloat16 chains run the skip at trunk layer 4; this model's nerf_skips cannot be laid out "
                                    "around it (needs skip <= 4 and depth - skip <= 4): use the float32 mode");
+  if ((flags & (NRF_FLAG_BF16 | NRF_FLAG_BF16X3)) && h->d.nerf_rgb_branch_depth > 1)
+    return fail(NRF_E_UNSUPPORTED, "NRF_FLAG_BF16 / NRF_FLAG_BF16X3: the bfloat16 chains run an rgb branch of one layer; this model's "
+                                   "nerf_rgb_branch_depth > 1 (rgb branch layers 1..) exists in the float32 chains only: use the float32 mode");
   return NRF_OK;
 }
 
@@ -331,6 +338,9 @@ int nrf_set_option(nrf_handle h, int32_t option, int64_t value) {
   if (!h) return fail(NRF_E_NULL, "handle is null");
   if (option == NRF_OPT_CHAIN_TILE_ROWS) {
     if (value != 0 && value != 32 && value != 64) return fail(NRF_E_UNSUPPORTED, "NRF_OPT_CHAIN_TILE_ROWS: 0 (automatic), 32 or 64");
+    if (value == 32 && h->d.nerf_rgb_branch_depth > 1)
+      return fail(NRF_E_UNSUPPORTED, "NRF_OPT_CHAIN_TILE_ROWS = 32: the 32-row chains run an rgb branch of one layer; a model with "
+                                     "nerf_rgb_branch_depth > 1 keeps the 64-row kernels at every launch size");
     if (h->chain_rows_opt != (int)value) {
       h->chain_rows_opt = (int)value;
       h->stashed_ws = nullptr;   // a stash written under the old plan is not differentiated under the new one
@@ -383,6 +393,7 @@ int nrf_debug_ws_offset(nrf_handle h, const char* name, int32_t level, int64_t* 
       {"wpoints", L.wpoints}, {"d_points", L.d_points}, {"w_st_win", L.w_st_win}, {"w_st_h", L.w_st_h},
       {"w_st_wv", L.w_st_wv}, {"w_dy", L.w_dy}, {"w_dw4", L.w_dw4}, {"w_dv4", L.w_dv4},
       {"w_bits", L.w_bits}, {"bits_trunk", L.bits_trunk}, {"bits_rgbh", L.bits_rgbh},
+      {"st_rgbx", L.st_rgbx}, {"bits_rgbx", L.bits_rgbx}, {"dy_rgbx", L.dy_rgbx},   // rgb branch layers 1..D-1, [D-1][ntiles]...
       {"b_pe", L.b_pe}, {"b_h", L.b_h}, {"b_bn", L.b_bn}, {"b_rgbh", L.b_rgbh}, {"b_bits", L.b_bits}, {"b_dy", L.b_dy},
       {"b_dbn", L.b_dbn}, {"b_drgbh", L.b_drgbh}, {"b_dsmall", L.b_dsmall},
       {"bw_in", L.bw_in}, {"bw_h", L.bw_h}, {"bw_bits", L.bw_bits}, {"bw_dy", L.bw_dy}, {"bw_dhead", L.bw_dhead},

@@ -55,6 +55,7 @@ struct LevelWs {   // float offsets from the workspace base, per level (0 = coar
   int bw_ngroups = 0;
   size_t st_pe, st_h, st_bn, st_rgbh, bits_trunk, bits_rgbh;
   size_t d_raw4, dy_trunk, dy_bn, dy_rgbh, dray, small_part, cond_grad;
+  size_t st_rgbx = 0, bits_rgbx = 0, dy_rgbx = 0;   // rgb branch layers 1..D-1 (nerf_rgb_branch_depth > 1), [D-1][ntiles]...; not in the plan digest
   // SE3 warp field (per level: the field is evaluated on the coarse and on the fine samples)
   size_t wpoints, points_raw, d_points;
   size_t el_dw4, el_dv4;   // coarse level: dL/d(w, v) of the elastic regulariser through exp_se3's second derivatives

@@ -17,6 +17,8 @@ constexpr int ACT_FLOATS = TRUNK_W * TILE_ROWS;        // LDS activation tile
 constexpr int FRAG_TILE_256 = TRUNK_W * TILE_ROWS;     // floats per stash tile, 256 wide
 constexpr int FRAG_TILE_128 = RGB_W * TILE_ROWS;
 constexpr int SMALL_PART = 3080;  // per-workgroup small-gradient partials (see mlp_chain.hip)
+constexpr int RGB_MAX_DEPTH = 4;  // rgb branch layers (modules.py:129-134); layers 1.. are the run-time "extra" 128 x 128 layers
+constexpr int RGB_MAX_EXTRA = RGB_MAX_DEPTH - 1;
 
 // SE3 warp field trunk (warping.py:224-231 defaults): 6 x 128, skip at 4
 constexpr int WARP_W = 128;
@@ -40,6 +42,7 @@ struct MlpParamOffsets {
   int64_t rgbh_k, rgbh_b;      // [256+R,128], [128]
   int64_t logit_k, logit_b;    // [128,3], [3]
   int64_t alpha_k, alpha_b;    // [256,1], [1]
+  int64_t rgbx_k[RGB_MAX_EXTRA], rgbx_b[RGB_MAX_EXTRA];   // rgb branch layers 1..D-1: [128,128], [128] (nerf_rgb_branch_depth > 1)
 };
 
 // Offsets (floats) inside one MLP's packed-weight block (see pack kernel).
@@ -51,6 +54,7 @@ struct PackOffsets {
   int bwd_LT[TRUNK_DEPTH]; // [1..7] used (dX of layer l), [0] unused unless warp
   int bwd_L0T, bwd_L4bT;   // warp on: W0^T and the skip layer's posenc rows^T, 256 -> PK (64-column stream)
   int total;
+  int fwd_rgbx, bwd_rgbxT; // rgb branch layers 1..D-1: D-1 images of 128 x 128 each, forward / transposed (0 when D == 1)
 };
 
 // SE3 field leaves inside the flat parameter buffer
@@ -209,6 +213,10 @@ struct ChainFwdArgs {
   uint32_t* bits_trunk;      // [8][ntiles][4 waves][64 lanes] x 4 dwords
   uint32_t* bits_rgbh;       // [ntiles][4 waves][64 lanes] x 2 dwords
   BfStash bst;               // bf16 training chain (NRF_FLAG_BF16 | NRF_FLAG_TRAIN); pointers null otherwise
+  // rgb branch layers 1..nx (nerf_rgb_branch_depth = nx + 1; float32 64-row chains only)
+  int nx;
+  float* st_rgbx;            // [nx][ntiles][128*64] post-ReLU activations, fragment-native
+  uint32_t* bits_rgbx;       // [nx][ntiles][4 waves][64 lanes], words as bits_rgbh
 };
 
 struct ChainBwdArgs {
@@ -233,6 +241,10 @@ struct ChainBwdArgs {
   int* tile_counter;
   int k_old;                 // as ChainFwdArgs
   int alpha_on_bn;           // use_alpha_condition: d raw sigma enters at the bottleneck instead of the trunk output
+  // rgb branch layers 1..nx (as ChainFwdArgs); their bias partials: small_part + SP_DB_RGBX (mlp_chain.hip)
+  int nx;
+  const uint32_t* bits_rgbx;
+  float* dy_rgbx;            // [nx][ntiles][128*64] dpre of layers 1..nx
 };
 
 // SE3Field forward (warping.py:322-353): x = o + z d (or explicit points) -> warped points.

@@ -86,6 +86,11 @@ void build_layout(nrf_handle h) {
     }
     add_leaf(h, base + "/MLP_1/hidden_0/kernel", W + h->R, RW, &po.rgbh_k, XW + h->R, XRW, XW);
     add_leaf(h, base + "/MLP_1/hidden_0/bias", 1, RW, &po.rgbh_b, 1, XRW);
+    for (int i = 1; i < d.nerf_rgb_branch_depth; ++i) {   // modules.py:41-50: layers 1.. of the branch read the layer before, (w, w)
+      const std::string hn = base + "/MLP_1/hidden_" + std::to_string(i);
+      add_leaf(h, hn + "/kernel", RW, RW, &po.rgbx_k[i - 1], XRW, XRW);
+      add_leaf(h, hn + "/bias", 1, RW, &po.rgbx_b[i - 1], 1, XRW);
+    }
     add_leaf(h, base + "/MLP_1/logit/kernel", RW, 3, &po.logit_k, XRW, 3);
     add_leaf(h, base + "/MLP_1/logit/bias", 1, 3, &po.logit_b);
     add_leaf(h, base + "/MLP_2/logit/kernel", W + h->A, 1, &po.alpha_k, XW + h->A, 1, XW);   // [bottleneck | appearance code] (modules.py:152-157)
@@ -158,6 +163,11 @@ void build_pack_offsets(nrf_handle h) {
   for (int l = 1; l < TRUNK_DEPTH; ++l) pk.bwd_LT[l] = take(256 * 256);
   pk.bwd_L0T = pk.bwd_L4bT = 0;
   if (h->warp) { pk.bwd_L0T = take(256 * 64); pk.bwd_L4bT = take(256 * 64); }
+  pk.fwd_rgbx = pk.bwd_rgbxT = 0;
+  if (const int nx = h->d.nerf_rgb_branch_depth - 1) {   // rgb branch layers 1..nx, behind everything a depth-1 model packs
+    pk.fwd_rgbx = take(nx * RGB_W * RGB_W);
+    pk.bwd_rgbxT = take(nx * RGB_W * RGB_W);
+  }
   pk.total = o + 4096;   // slack: the K loop prefetches two quads past a layer's last weights
   if (h->warp) {
     WarpPackOffsets& w = h->wpk;
@@ -216,7 +226,10 @@ uint32_t plan_flags(uint32_t flags) {
 // twice over -- fewer than two tiles per workgroup slot, e.g. one GPU's 128-ray share of a 1024-ray batch: 128 + 384 tiles for
 // 512 slots -- runs 12-34 % faster on half tiles (coarse forward 0.160 -> 0.106 ms, fine 0.301 -> 0.264 ms).  The reverse
 // chain never won (0.303 -> 0.327 ms at 512 tiles): its automatic choice stays 64.
+// An rgb branch deeper than one layer exists in the 64-row kernels only: such a handle never takes half tiles (nrf_set_option
+// refuses 32 for it), whatever the launch size.
 bool chain32_for(const nrf_handle_s* h, int ntiles, bool reverse) {
+  if (h->d.nerf_rgb_branch_depth > 1) return false;
   if (h->chain_rows_opt == 32) return true;
   if (h->chain_rows_opt == 64) return false;
   return !reverse && ntiles < AUTO32_FWD_BELOW_TILES_PER_CU * h->num_cus;
@@ -493,7 +506,7 @@ void Planner::shapes() {
       // the 32-row reverse kernel has no d-points path: models with a warp field keep the 64-row one
     int nt_mlp = 0;
     for (int q = 0; q < h->nlevels; ++q) nt_mlp += p.ntiles[q];
-    p.bwd32 = train && !bft && !h->warp && chain32_for(h, nt_mlp, true);
+    p.bwd32 = train && !bft && !h->warp && chain32_for(h, nt_mlp, true);   // (false for an rgb branch deeper than one layer)
   }
   p.tg_tiles_per = jac ? p.ntiles[h->nlevels - 1] : k.elastic ? p.ntiles[0] : 0;   // Jacobian output: levels run one after the other
   p.ntiles[TG] = 3 * p.tg_tiles_per;
@@ -530,9 +543,16 @@ void Planner::fp32_specs(int lv) {
   }
   gemm(lv, 0, frag256(&L.st_h, (size_t)7 * layer), 256, frag256(&L.dy_bn), po.bn_k, 256);
   gemm(lv, 0, frag256(&L.st_bn), 256, frag128(&L.dy_rgbh), po.rgbh_k, 128);
-  // narrow heads on the VALU: alpha (X = h8, or the bottleneck under use_alpha_condition; vec.w) and rgb logits (X = rgb hidden, vec.xyz)
+  // rgb branch layers 1..nx: the stash of the layer before x its adjoint (the 128 x 128 shape of the SE3 trunk's groups)
+  const int nx = d.nerf_rgb_branch_depth - 1;
+  const size_t xlayer = (size_t)p.ntiles[lv] * FRAG_TILE_128;
+  for (int x = 0; x < nx; ++x)
+    gemm(lv, 0, x ? frag128(&L.st_rgbx, (size_t)(x - 1) * xlayer) : frag128(&L.st_rgbh), 128, frag128(&L.dy_rgbx, (size_t)x * xlayer),
+         po.rgbx_k[x], 128);
+  // narrow heads on the VALU: alpha (X = h8, or the bottleneck under use_alpha_condition; vec.w) and rgb logits (X = the last
+  // rgb hidden layer, vec.xyz)
   heads(lv, 0, h->A > 0 ? frag256(&L.st_bn) : frag256(&L.st_h, (size_t)7 * layer), 256, 1, po.alpha_k);
-  heads(lv, 0, frag128(&L.st_rgbh), 128, 3, po.logit_k);
+  heads(lv, 0, nx ? frag128(&L.st_rgbx, (size_t)(nx - 1) * xlayer) : frag128(&L.st_rgbh), 128, 3, po.logit_k);
 }
 
 // SE3 trunk + heads of level `lv` (coarse / fine samples, or the background-point batch, or the tangents)
@@ -767,6 +787,11 @@ void Planner::buffers() {
       L.dy_trunk = take(nt * FRAG_TILE_256 * TRUNK_DEPTH);
       L.dy_bn = take(nt * FRAG_TILE_256);
       L.dy_rgbh = take(nt * FRAG_TILE_128);
+      if (const size_t nx = d.nerf_rgb_branch_depth - 1) {   // rgb branch layers 1..nx: stash, sign bits, adjoints
+        L.st_rgbx = take(nx * nt * FRAG_TILE_128);
+        L.bits_rgbx = take(nx * nt * 4 * 64);
+        L.dy_rgbx = take(nx * nt * FRAG_TILE_128);
+      }
     }
     if (train) {
       L.dray = take((size_t)B * RGB_W);
@@ -825,6 +850,10 @@ void Planner::pack_descs() {
     add(po.bn_k, pk.fwd_bn, 256, 0, 256, 256, 2, 0);
     add(po.rgbh_k, pk.fwd_rgbh, 128, 0, 256, 256, 1, 0);
     add(po.rgbh_k, pk.bwd_rgbhT, 128, 0, 128, 128, 2, 1);
+    for (int x = 0; x < d.nerf_rgb_branch_depth - 1; ++x) {   // 128 x 128, one 32-column block per wave, as is and transposed
+      add(po.rgbx_k[x], pk.fwd_rgbx + x * RGB_W * RGB_W, 128, 0, 128, 128, 1, 0);
+      add(po.rgbx_k[x], pk.bwd_rgbxT + x * RGB_W * RGB_W, 128, 0, 128, 128, 1, 1);
+    }
     add(po.bn_k, pk.bwd_bnT, 256, 0, 256, 256, 2, 1);
     for (int l = 1; l < TRUNK_DEPTH; ++l) add(po.trunk_k[l], pk.bwd_LT[l], 256, 0, 256, 256, 2, 1);
     if (h->warp) {   // d posenc streams: B[k][n] = W[row0 + n][k], n < P, one 64-column group
@@ -910,6 +939,7 @@ void Planner::bias_reduces() {
     small(po.rgbh_b, 128, 2304);
     small(po.logit_b, 3, 2432);
     small(po.alpha_b, 1, 2435);
+    for (int x = 0; x < d.nerf_rgb_branch_depth - 1; ++x) small(po.rgbx_b[x], 128, 2436 + x * 128);   // SP_DB_RGBX (mlp_chain.hip)
     if (h->R > 0) add_reduce(reduce_desc(po.rgbh_k + 256 * 128, 128, h->R, 128, (int64_t)L.cond_grad, 128, 0, 1));
     if (h->warp && !bfw && lv == 0) {   // ONE SE3 dgrad launch (coarse + fine + background tiles), one set of bias partials
       const int nt_w = nt_mlp + (p.key.bgN > 0 ? p.ntiles[BG] : 0);
@@ -997,7 +1027,10 @@ void build_plan(nrf_handle h, int B, uint32_t flags, int bgN, int elastic) {
     h->plan.iparams = s.take((size_t)h->nparams);
     if (s.train) h->plan.igrad = s.take((size_t)h->nparams);
   }
-  if (!s.train || s.bft) s.weight_streams();
+  // The bf16 / x3 chains have their layer list compiled in: a handle with a deeper rgb branch builds none of their stream
+  // descriptors (check_flags refuses those modes for it)
+  if (h->d.nerf_rgb_branch_depth > 1) h->plan.bf_stream_ok = false;
+  else if (!s.train || s.bft) s.weight_streams();
   s.buffers();
   s.pack_descs();
   if (s.train) {

@@ -71,7 +71,9 @@ ChainFwdArgs fwd_args(nrf_handle h, int lv, const float* params, const nrf_rays*
     a.st_pe = ws + L.st_pe; a.st_h = ws + L.st_h; a.st_bn = ws + L.st_bn; a.st_rgbh = ws + L.st_rgbh;
     a.bits_trunk = reinterpret_cast<uint32_t*>(ws + L.bits_trunk);
     a.bits_rgbh = reinterpret_cast<uint32_t*>(ws + L.bits_rgbh);
+    a.st_rgbx = ws + L.st_rgbx; a.bits_rgbx = reinterpret_cast<uint32_t*>(ws + L.bits_rgbx);
   }
+  a.nx = h->d.nerf_rgb_branch_depth - 1;
   return a;
 }
 
@@ -82,12 +84,13 @@ int copy_out(float* dst, const float* src, size_t n, hipStream_t stream) {
 }
 
 // algorithmic flops per MLP row (2 flop / MAC, dense layers only, unpadded)
+double rgbx_flops_row(nrf_handle h) { return 2.0 * 16384.0 * (h->d.nerf_rgb_branch_depth - 1); }   // rgb branch layers 1..
 double fwd_flops_row(nrf_handle h) {
   const double P = h->P, R = h->R;
-  return 2.0 * (P * 256 + 6 * 65536.0 + (256 + P) * 256 + 65536.0 + 256 + (256 + R) * 128 + 128 * 3);
+  return 2.0 * (P * 256 + 6 * 65536.0 + (256 + P) * 256 + 65536.0 + 256 + (256 + R) * 128 + 128 * 3) + rgbx_flops_row(h);
 }
 double dgrad_flops_row(nrf_handle h, bool warp_on) {
-  const double base = 2.0 * (128 * 3 + 256 * 128 + 65536.0 + 256 + 7 * 65536.0);
+  const double base = 2.0 * (128 * 3 + 256 * 128 + 65536.0 + 256 + 7 * 65536.0) + rgbx_flops_row(h);
   return warp_on ? base + 2.0 * (2.0 * 256 * h->P) : base;   // + d posenc through layer 0 and the skip rows
 }
 // SE3 field per row: trunk + heads
@@ -99,7 +102,7 @@ double warp_dgrad_flops_row(nrf_handle h) { return 2.0 * (128 * 6 + 5 * 16384.0 
 double warp_fwd_flops_row_or0(nrf_handle h) { return h->warp ? warp_fwd_flops_row(h) : 0.0; }
 double wgrad_flops_row(nrf_handle h) {
   const double P = h->P, R = h->R;
-  return 2.0 * (2 * P * 256 + 7 * 65536.0 + 65536.0 + (256 + R) * 128 + 256 + 128 * 3);
+  return 2.0 * (2 * P * 256 + 7 * 65536.0 + 65536.0 + (256 + R) * 128 + 256 + 128 * 3) + rgbx_flops_row(h);
 }
 
 WarpFwdArgs warp_fwd_args(nrf_handle h, int lv, const float* params, const nrf_rays* rays, const nrf_step_scalars* sc, float* ws, bool train) {
@@ -448,6 +451,8 @@ int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, con
       if (warp_on) { a.d_points = ws + L.d_points; a.st_pe = ws + L.st_pe; }
       a.F = d.num_nerf_point_freqs; a.P = h->P; a.PK = h->PK; a.skip = d.nerf_skip_layer;
       a.alpha_on_bn = h->A > 0 ? 1 : 0;
+      a.nx = d.nerf_rgb_branch_depth - 1;
+      a.bits_rgbx = reinterpret_cast<const uint32_t*>(ws + L.bits_rgbx); a.dy_rgbx = ws + L.dy_rgbx;
       nt_all += p.ntiles[lv];
     }
     h->prof.begin("mlp_dgrad", dgrad_flops_row(h, warp_on) * mlp_rows, stream);

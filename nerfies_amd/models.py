@@ -278,6 +278,13 @@ class NerfModel:
       return L.NRF_FLAG_BF16 | L.NRF_FLAG_WARP_F32
     return L.NRF_FLAG_BF16
 
+  def check_mode(self, bf16, train: bool = False):
+    """Raises NrfError with the library's own message when this model cannot run in the `bf16` mode (a moved skip or an rgb
+    branch deeper than one layer exist in the float32 chains only): what the drivers ask before they load data or capture a graph."""
+    nbytes = C.c_size_t(0)
+    flags = (L.NRF_FLAG_TRAIN if train else 0) | self.bf16_flags(bf16)
+    L.check(self.lib.nrf_workspace_bytes(self.handle, 1, flags, C.byref(nbytes)), self.lib)
+
   def workspace(self, num_rays: int, train: bool, device, num_background_points: int = 0, elastic: bool = False,
                 jacobian: bool = False, bf16=False) -> torch.Tensor:
     # the TRAINING layout depends on it (bf16 stashes instead of the fp32 ones); so does an 'x3' inference plan (its weight streams)

@@ -98,6 +98,11 @@ def main(argv=None):
       exp_config.random_seed, model_config, batch_size=train_config.batch_size, appearance_ids=datasource.appearance_ids,
       camera_ids=datasource.camera_ids, warp_ids=datasource.warp_ids, near=datasource.near, far=datasource.far,
       use_warp_jacobian=train_config.use_elastic_loss, use_weights=train_config.use_elastic_loss, device=device)
+  if flags.bf16:   # a model shape the bfloat16 chains do not run is refused here, with the library's reason, not at the first step
+    try:
+      model.check_mode(flags.bf16, train=True)
+    except models.L.NrfError as e:
+      raise SystemExit(f'--bf16: {e}')
   state = training.TrainState(optimizer=training.Optimizer(params), warp_alpha=warp_alpha_sched(0),
                               time_alpha=time_alpha_sched(0))
   scalar_params = training.ScalarParams(
