@@ -400,7 +400,8 @@ int nrf_debug_plan_digest(nrf_handle h, uint64_t* digest);
  * re-plans; a stashed forward cannot be differentiated across a change: NRF_E_STATE).  Unknown option / value:
  * NRF_E_UNSUPPORTED.
  *   NRF_OPT_CHAIN_TILE_ROWS  rows per workgroup tile of the float32 NeRF-MLP chain kernels (modules.py:95-169):
- *                            64 = two workgroups per CU (csrc/mlp_chain.hip), 32 = four per CU (csrc/mlp_chain32.hip),
+ *                            64 = two workgroups per CU (csrc/mlp_chain.hip), 32 = four per CU (csrc/mlp_chain32.hip): one tile
+ *                            body, csrc/nerf_chain.h, instantiated on two tile geometries,
  *                            0 = automatic (default: half tiles for forward launches that under-fill the 64-row grid).  The
  *                            forward results (and the stashes) are bit-identical under both tilings -- a ray's result does not
  *                            depend on the launch it rides in --, gradients agree to the order of float atomics; the workspace

@@ -269,20 +269,21 @@ __device__ __forceinline__ BiasRegs<NCB> bias_load(const float* __restrict__ bia
   for (int cb = 0; cb < NCB; ++cb) r.b[cb] = bias[ncol0 + 32 * cb + (lane & 31)];
   return r;
 }
-template <int NCB>
-__device__ __forceinline__ void bias_set(f32x16 (&acc)[2][NCB], const BiasRegs<NCB>& r) {
+// RB row blocks per wave: 2 on 64-row tiles, 1 on 32-row tiles (deduced from the accumulator)
+template <int NCB, int RB>
+__device__ __forceinline__ void bias_set(f32x16 (&acc)[RB][NCB], const BiasRegs<NCB>& r) {
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
+    for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc[rb][cb][q] = r.b[cb];
 }
 
-template <int NCB>
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][NCB]) {
+template <int NCB, int RB>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[RB][NCB]) {
 #pragma unroll
-  for (int rb = 0; rb < 2; ++rb)
+  for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -309,34 +310,92 @@ __device__ __forceinline__ float4 mask4(const float4& v, uint32_t nib) {
   return make_float4((nib & 1u) ? v.x : 0.f, (nib & 2u) ? v.y : 0.f, (nib & 4u) ? v.z : 0.f, (nib & 8u) ? v.w : 0.f);
 }
 
-// Layer epilogue: write the wave's 64 x 32*NCB outputs to the LDS activation tile and, in training, to the
-// fragment-order stash.  MODE 0: linear; 1: ReLU (+ 1 sign bit per element out: bits_wave[lane*NCB + cb],
-// nibble q); 2: multiply by the 0/1 mask read from bits_wave (tangent pass: the ReLU derivative of the
-// primal pass, warping.py:385-387 jacfwd).
+// ---------------------------------------------------------------------------------------------
+// Tile geometry: what a chain body needs to know about the rows a workgroup owns.  Tile64 is the tiling described at the top
+// of this file, bundled from the helpers above; nerf_chain.h adds the 32-row tiling of the fp32 NeRF chain.  Every member is
+// resolved at compile time.
+// ---------------------------------------------------------------------------------------------
+struct Tile64 {
+  static constexpr int ROWS = TILE_ROWS;   // rows per workgroup tile
+  static constexpr int RB = 2;             // MFMA row blocks per wave
+  static constexpr int NPIECE = 8;         // float4 pieces (4 consecutive rows of one column) per lane and column block
+  static constexpr int PARTS = 4;          // threads per tile row in the per-row (VALU) phases: part = wave, row = lane
+  static constexpr int WG_PER_CU = 2;
+  static constexpr int SCRATCH_ROWS = 0;   // LDS rows behind the activation tile: max(PK, SCRATCH_ROWS)
+  static constexpr bool FULL = true;       // rgb branch layers 1..nx and the d points path are compiled in
+  static constexpr bool BIAS_IN_REGS = true;   // reverse pass: bias-gradient partials live in per-lane registers (BwdAcc)
+  __device__ static __forceinline__ int row0(int tile, int) { return tile * TILE_ROWS; }
+  __device__ static __forceinline__ int part(int wave, int) { return wave; }
+  __device__ static __forceinline__ int prow(int lane) { return lane; }
+  __device__ static __forceinline__ bool part_writer(int) { return true; }   // every lane holds a row's partial sum
+  __device__ static __forceinline__ int epilogue_lane(int lane) { return lane; }
+  __device__ static __forceinline__ int addr(int k, int g) { return act_addr(k, g); }
+  __device__ static __forceinline__ int elem(int k, int p) { return act_elem(k, p); }
+  __device__ static __forceinline__ int granule(int q, int h) { return q_granule(q, h); }
+  template <int NCB>
+  __device__ static __forceinline__ float4 piece(const f32x16 (&acc)[2][NCB], int cb, int q) { return acc_piece<NCB>(acc, cb, q); }
+  // piece q of a lane inside one 8 KiB feature block of the fragment-order tile: per-lane and per-piece byte offsets
+  __device__ static __forceinline__ int frag_voff(int lane, int) { return lane * 16; }
+  __device__ static __forceinline__ int frag_slot(int, int q) { return q * 1024; }
+  template <int NCB, bool SWZ>
+  __device__ static __forceinline__ void k_loop(f32x16 (&acc)[2][NCB], const float* lds_in, int nquads, const float4* __restrict__ wp, int lane,
+                                                const WQuad<NCB>& first) {
+    mfma_k_loop<NCB, SWZ>(acc, lds_in, nquads, wp, lane, first);
+  }
+  // sign-bit image: the word of (lane, column block cb) holds nibble q at bits 4q
+  template <int NCB>
+  __device__ static __forceinline__ void bits_store(const uint32_t (&nib)[NCB], int cb, uint32_t* words_wave, int lane, int) {
+    words_wave[lane * NCB + cb] = nib[cb];
+  }
+  template <int NCB> struct Mask { uint32_t w[NCB]; };
+  template <int NCB>
+  __device__ static __forceinline__ Mask<NCB> mask_load(const uint32_t* words_wave, int lane) {
+    Mask<NCB> m;
+    if constexpr (NCB == 2) {
+      const uint2 mq = *reinterpret_cast<const uint2*>(words_wave + lane * 2);
+      m.w[0] = mq.x; m.w[1] = mq.y;
+    } else {
+      m.w[0] = words_wave[lane];
+    }
+    return m;
+  }
+  template <int NCB>
+  __device__ static __forceinline__ uint32_t mask_nibble(const Mask<NCB>& m, int cb, int, int q, int) { return (m.w[cb] >> (4 * q)) & 15u; }
+  __device__ static __forceinline__ void stash_posenc(const float* tile_lds, int kvalid, int nblocks, float* stash_tile, int, int wave, int lane) {
+    stash_tile_from_lds(tile_lds, kvalid, nblocks, stash_tile, wave, lane);
+  }
+};
+
+// Layer epilogue: write the wave's ROWS x 32*NCB outputs to the LDS activation tile and, in training, to the
+// fragment-order stash.  MODE 0: linear; 1: ReLU (+ 1 sign bit per element out, G::bits_store); 2: multiply by the 0/1 mask
+// read from bits_wave (tangent pass: the ReLU derivative of the primal pass, warping.py:385-387 jacfwd; 64-row tiles).
+// T: which half of the 64-row stash tile a 32-row workgroup owns.
 enum { EPI_LINEAR = 0, EPI_RELU = 1, EPI_MASK = 2 };
-template <int NCB, int MODE, bool STASH>
-__device__ __forceinline__ void fwd_epilogue(f32x16 (&acc)[2][NCB], int ncol0, float* act,
+template <int NCB, int MODE, bool STASH, class G = Tile64>
+__device__ __forceinline__ void fwd_epilogue(f32x16 (&acc)[G::RB][NCB], int ncol0, float* act,
                                              __amdgpu_buffer_rsrc_t stash, int stash_soff, uint32_t* bits_wave,
-                                             int lane) {
+                                             int lane, int T = 0) {
+  lane = G::epilogue_lane(lane);
   const int j = lane & 31, h = lane >> 5;
   __syncthreads();   // every wave has finished reading the previous activations
+  uint32_t mb[NCB];
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb) {
     const int n = ncol0 + 32 * cb + j;
-    uint32_t mb = MODE == EPI_MASK ? bits_wave[lane * NCB + cb] : 0u;
+    mb[cb] = MODE == EPI_MASK ? bits_wave[lane * NCB + cb] : 0u;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      float4 v = acc_piece<NCB>(acc, cb, q);
+    for (int q = 0; q < G::NPIECE; ++q) {
+      float4 v = G::template piece<NCB>(acc, cb, q);
       if (MODE == EPI_RELU) {
-        if (STASH) mb |= sign_nibble(v) << (4 * q);
+        if (STASH) mb[cb] |= sign_nibble(v) << (4 * q);
         v.x = relu(v.x); v.y = relu(v.y); v.z = relu(v.z); v.w = relu(v.w);
       } else if (MODE == EPI_MASK) {
-        v = mask4(v, (mb >> (4 * q)) & 15u);
+        v = mask4(v, (mb[cb] >> (4 * q)) & 15u);
       }
-      *reinterpret_cast<float4*>(act + act_addr(n, q_granule(q, h))) = v;
-      if (STASH) buf_store4(v, stash, lane * 16, stash_soff + (cb * 8 + q) * 1024);
+      *reinterpret_cast<float4*>(act + G::addr(n, G::granule(q, h))) = v;
+      if (STASH) buf_store4(v, stash, G::frag_voff(lane, q), stash_soff + cb * 8 * 1024 + G::frag_slot(T, q));
     }
-    if (STASH && MODE == EPI_RELU) bits_wave[lane * NCB + cb] = mb;
+    if (STASH && MODE == EPI_RELU) G::template bits_store<NCB>(mb, cb, bits_wave, lane, T);
   }
   __syncthreads();
 }

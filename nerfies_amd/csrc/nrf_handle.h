@@ -111,8 +111,8 @@ struct WsPlan {
                                      // (background batch), 3 (Jacobian tangents) add into leaves shared with earlier passes
   LevelWs L[4];          // 0 coarse, 1 fine, 2 background points (SE3 field only, training.py:117-135),
                          // 3 tangent pass of the coarse warp Jacobian (elastic regulariser, 3 x coarse tiles)
-  bool bwd32 = false;    // training plan: the fp32 NeRF reverse chain runs on 32-row tiles (mlp_chain32.hip); decides the
-                         // number of bias partials the reduce table sums
+  bool bwd32 = false;    // training plan: the fp32 NeRF reverse chain runs on 32-row tiles (mlp_chain32.hip, nerf_chain.h
+                         // Tile32); decides the number of bias partials the reduce table sums
   int tg_tiles_per = 0;  // primal tiles one tangent pass covers (elastic: coarse level; Jacobian output: the larger level)
   size_t total_floats;
   std::vector<PackDesc> pack;

@@ -421,8 +421,8 @@ void launch_pack(const PackDesc* d_descs, int ndesc, const float* params, float*
 void launch_chain_fwd(const ChainFwdArgs& a, bool stash, int grid, hipStream_t stream);
 // a1 (optional): the fine level, run by the same launch (tiles [a0.ntiles, a0.ntiles + a1->ntiles))
 void launch_chain_bwd(const ChainBwdArgs& a0, const ChainBwdArgs* a1, int grid, hipStream_t stream);
-// the same chains on 32-row tiles, four workgroups per CU (mlp_chain32.hip); same arguments, same HBM images.  The reverse
-// kernel has no d-points path yet: warp-on plans keep the 64-row reverse pass
+// the same chains (nerf_chain.h: one tile body for both tilings) on 32-row tiles, four workgroups per CU (mlp_chain32.hip); same
+// arguments, same HBM images.  The d-points path is compiled for 64-row tiles only: warp-on plans keep the 64-row reverse pass
 void launch_chain_fwd32(const ChainFwdArgs& a, bool stash, int grid, hipStream_t stream);
 void launch_chain_bwd32(const ChainBwdArgs& a0, const ChainBwdArgs* a1, int grid, hipStream_t stream);
 // a1 (optional): a second level in the same launch (background points behind the coarse samples)

@@ -220,14 +220,14 @@ uint32_t plan_flags(uint32_t flags) {
 }
 
 // Rows per workgroup tile of the float32 NeRF chain kernels for a launch over `ntiles` 64-row tiles: true = 32-row half tiles,
-// four workgroups per CU (mlp_chain32.hip).  NRF_OPT_CHAIN_TILE_ROWS forces either.  Automatic = what the round-5 A/B measured
-// (profiles/r05_chain32_ab.md): in steady state the 64-row kernels win by 3-5 % (forward 130 vs 123.5 TF, reverse 129 vs 125,
+// four workgroups per CU (mlp_chain32.hip; nerf_chain.h Tile32).  NRF_OPT_CHAIN_TILE_ROWS forces either.  Automatic = what the
+// round-5 A/B measured (profiles/r05_chain32_ab.md): in steady state the 64-row kernels win by 3-5 % (forward 130 vs 123.5 TF, reverse 129 vs 125,
 // eval forward 137 vs 132: every B operand float feeds one MFMA instead of two), but a launch that cannot fill the 64-row grid
 // twice over -- fewer than two tiles per workgroup slot, e.g. one GPU's 128-ray share of a 1024-ray batch: 128 + 384 tiles for
 // 512 slots -- runs 12-34 % faster on half tiles (coarse forward 0.160 -> 0.106 ms, fine 0.301 -> 0.264 ms).  The reverse
 // chain never won (0.303 -> 0.327 ms at 512 tiles): its automatic choice stays 64.
-// An rgb branch deeper than one layer exists in the 64-row kernels only: such a handle never takes half tiles (nrf_set_option
-// refuses 32 for it), whatever the launch size.
+// An rgb branch deeper than one layer is compiled into the 64-row kernels only (nerf_chain.h Tile64::FULL): such a handle
+// never takes half tiles (nrf_set_option refuses 32 for it), whatever the launch size.
 bool chain32_for(const nrf_handle_s* h, int ntiles, bool reverse) {
   if (h->d.nerf_rgb_branch_depth > 1) return false;
   if (h->chain_rows_opt == 32) return true;

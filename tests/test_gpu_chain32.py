@@ -1,5 +1,5 @@
 """The float32 NeRF chain on 32-row tiles (csrc/mlp_chain32.hip, NRF_OPT_CHAIN_TILE_ROWS = 32) against the 64-row kernels
-(csrc/mlp_chain.hip) on the same inputs (modules.py:26-62, 65-169; models.py:270-277).
+(csrc/mlp_chain.hip; both instantiate the tile bodies of csrc/nerf_chain.h) on the same inputs (modules.py:26-62, 65-169; models.py:270-277).
 
 Both tilings write the SAME HBM images (64-row fragment-order stash, sign-bit words, d raw / out4 rows), and every output
 element is the same fmaf chain in both (bias, then k = 0, 1, ... through the same MFMA k-steps; the alpha head and the logits
