@@ -511,10 +511,7 @@ __device__ __forceinline__ void fwd_tile(const ChainFwdArgs& A, const int tile, 
 // ---------------------------------------------------------------------------------------------
 // backward (data gradients; bias gradients accumulated per workgroup)
 // ---------------------------------------------------------------------------------------------
-// small_part layout (floats): db_trunk[8][256] | db_bn[256] | db_rgbh[128] | db_logit[3] | db_alpha
-//   ... | db_rgbx[3][128] (rgb branch layers 1..3; only written and reduced when the branch is deeper than one layer)
-constexpr int SP_DB_TRUNK = 0, SP_DB_BN = 2048, SP_DB_RGBH = 2304, SP_DB_LOGIT = 2432, SP_DB_ALPHA = 2435, SP_DB_RGBX = 2436;
-static_assert(SP_DB_RGBX + RGB_MAX_EXTRA * RGB_W <= SMALL_PART, "small_part too small for the rgb branch bias partials");
+// (small_part layout: nrf_internal.h SP_DB_*)
 
 // Where a tile's column sums (bias gradients) go is the one thing the tilings do differently.
 // 64-row tiles: per-lane accumulators of one workgroup, carried across its tiles of one level and flushed once

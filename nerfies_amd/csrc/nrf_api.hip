@@ -317,18 +317,11 @@ int nrf_warp_points(nrf_handle h, const float* params, const float* points, cons
   hipError_t e = hipMemcpyAsync(ws + q.desc_f, h->wp_pack.data(), h->wp_pack.size() * sizeof(PackDesc), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return fail_hip(e, "upload warp pack table");
   launch_pack(reinterpret_cast<const PackDesc*>(ws + q.desc_f), (int)h->wp_pack.size(), params, ws, st);
-  WarpFwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.params = params; a.po = wo; a.wpk = ws + q.wpk_f; a.pk = h->wpk;
-  a.points_in = points; a.point_ids = warp_ids; a.points_out = ws + q.out_f;
-  a.embed_table = params + wo.embed;
-  a.S = 1; a.B = num_points; a.rows = num_points; a.ntiles = q.ntiles;
-  a.F = h->Fw; a.G = h->G; a.Win = h->Win; a.PKw = h->PKw; a.alpha = scalars->warp_alpha; a.dyn = scalars->dynamic;
-  const int grid = q.ntiles < 2 * h->num_cus ? q.ntiles : 2 * h->num_cus;
+  WarpFwdArgs a = warp_points_args(h, params, wo, ws + q.wpk_f, scalars, points, warp_ids, num_points, ws + q.out_f);
   e = hipMemsetAsync(ws + q.ctr_f, 0, 16 * sizeof(int), st);
   if (e != hipSuccess) return fail_hip(e, "zero tile counter");
   a.tile_counter = tile_counter_or_null(ws + q.ctr_f, 0);
-  launch_warp_fwd(a, nullptr, false, grid, st);
+  launch_warp_fwd(a, nullptr, false, tile_grid(a.ntiles, 2, h->num_cus), st);
   e = hipMemcpyAsync(warped, ws + q.out_f, (size_t)num_points * 3 * sizeof(float), hipMemcpyDeviceToDevice, st);
   if (e != hipSuccess) return fail_hip(e, "copy warped points");
   return check_launch("nrf_warp_points");
@@ -399,7 +392,7 @@ int nrf_debug_ws_offset(nrf_handle h, const char* name, int32_t level, int64_t* 
       {"bw_in", L.bw_in}, {"bw_h", L.bw_h}, {"bw_bits", L.bw_bits}, {"bw_dy", L.bw_dy}, {"bw_dhead", L.bw_dhead},
       {"points_raw", L.points_raw},
       {"bg_points", h->plan.bg_points}, {"bg_ids", h->plan.bg_ids},
-      {"timeline", h->plan.timeline + (size_t)(level & 1) * 2 * (256 + 512 + 4 * 2048)}};
+      {"timeline", h->plan.timeline + (size_t)(level & 1) * TIMELINE_LEVEL_F}};
   for (const auto& t : tab)
     if (!strcmp(t.n, name)) { *float_offset = (int64_t)t.v; return NRF_OK; }
   return fail(NRF_E_SHAPE, "unknown workspace buffer name");

@@ -42,6 +42,9 @@ inline int fail_hip(hipError_t e, const char* where) {
 
 constexpr size_t ALIGN_F = 64;   // workspace sub-buffers are aligned to 64 floats (256 B)
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// grid of a launch whose workgroups walk `ntiles` tiles: one workgroup per tile, at most `per_cu` on each CU
+inline int tile_grid(int ntiles, int per_cu, int num_cus) { return ntiles < per_cu * num_cus ? ntiles : per_cu * num_cus; }
+constexpr size_t TIMELINE_LEVEL_F = 2 * (256 + 512 + 4 * 2048);   // floats of one level's record in WsPlan::timeline (uint64 stamps)
 
 struct LevelWs {   // float offsets from the workspace base, per level (0 = coarse, 1 = fine)
   size_t wpk, z, out4, rgb, depth, med, acc, weights, condterm;
@@ -105,14 +108,18 @@ struct WsPlan {
   size_t wr_sums = 0;   // [64] warp_reg loss / residual accumulators (coarse: 0, 1; fine: 2, 3)
   size_t t_codes = 0, t_dcodes = 0, t_in = 0, t_h = 0, t_dpre = 0;   // TimeEncoder: codes [B][G], their gradient, stashes
   size_t counters;      // [64] ints: dynamic tile counters of the chain kernels, zeroed at the start of forward / backward
-  size_t timeline;      // [2 levels][4 waves][64] uint64 debug stamps of workgroup 0 of the forward chain kernel
+  size_t timeline;      // [2 levels][TIMELINE_LEVEL_F] debug stamps of workgroup 0 of the forward chain kernel
   size_t seg_clock;     // [nsegs] uint64 wall-clock ticks per wgrad segment (cost-model calibration)
   int nreduce_pass[4] = {0, 0, 0, 0};   // reduce descriptors by pass: pass 0 overwrites, passes 1 (fine level) and 2
                                      // (background batch), 3 (Jacobian tangents) add into leaves shared with earlier passes
   LevelWs L[4];          // 0 coarse, 1 fine, 2 background points (SE3 field only, training.py:117-135),
                          // 3 tangent pass of the coarse warp Jacobian (elastic regulariser, 3 x coarse tiles)
   bool bwd32 = false;    // training plan: the fp32 NeRF reverse chain runs on 32-row tiles (mlp_chain32.hip, nerf_chain.h
-                         // Tile32); decides the number of bias partials the reduce table sums
+                         // Tile32), which ADD their bias column sums into the workgroups' slices (zeroed before the launch)
+  // Grids of the two fp32 reverse launches (Planner::shapes): each workgroup writes one slice of bias partials and the reduce table
+  // sums exactly that many, so launch, zero list and table all read these (functions of ntiles, bwd32, bgN, CUs: not in the digest)
+  int grid_mlp_bwd = 0;  // NeRF chains, tiles of all levels: small_part[grid_mlp_bwd][SMALL_PART] per level
+  int grid_warp_bwd = 0; // SE3 chain, coarse + fine + background tiles: w_small_part[grid_warp_bwd][WARP_SMALL_PART]
   int tg_tiles_per = 0;  // primal tiles one tangent pass covers (elastic: coarse level; Jacobian output: the larger level)
   size_t total_floats;
   std::vector<PackDesc> pack;
@@ -120,6 +127,15 @@ struct WsPlan {
   std::vector<ReduceDesc> reduce;
 };
 
+
+// What a call runs: forward_impl decides it once (nrf_run.hip forward_modes), backward_impl reads it back from the stash's handle
+enum class WarpTrunk { F32, BF16, X3 };   // warp_chain.hip / warp_bf16.hip / warp_bf16x3.hip
+struct Modes {
+  bool train = false, warp_on = false;   // NRF_FLAG_TRAIN (keep the stashes); the SE3 field runs (models.py:296 use_warp argument)
+  bool bf16 = false, x3 = false;         // NeRF chains on bf16 operands (mlp_bf16.hip) / in split-bf16 arithmetic (mlp_bf16x3.hip)
+  bool jac = false;                      // NRF_FLAG_WARP_JACOBIAN: the tangent pass of an inference call
+  WarpTrunk trunk = WarpTrunk::F32;
+};
 
 struct ProfSlot { std::string name; double flops; hipEvent_t a = nullptr, b = nullptr; bool used = false; };
 struct ProfAcc { std::string name; double ms = 0; int launches = 0; double flops = 0; };
@@ -215,7 +231,7 @@ struct nrf_handle_s {
   void* stashed_ws = nullptr;
   uint64_t stashed_plan = 0;   // WsPlan::serial of the stashed forward
   int stashed_B = -1;
-  bool stashed_warp = false;
+  nrf::api::Modes stashed_modes;
   std::vector<nrf::PackDesc> wp_pack;   // pack table of nrf_warp_points (kept alive for the async upload)
   int64_t wp_pack_base = -1;
 };
@@ -238,6 +254,9 @@ void query_device(nrf_handle h);
 
 // nrf_run.hip: the launch sequences of NerfModel.apply (forward_impl) and of the gradient half of train_step (backward_impl)
 int check_launch(const char* where);
+// SE3 field on explicit points with one warp id per point (background batch of the train step, nrf_warp_points): `n` points -> out
+WarpFwdArgs warp_points_args(nrf_handle h, const float* params, const WarpParamOffsets& po, const float* wpk, const nrf_step_scalars* sc,
+                             const float* points, const int32_t* ids, int n, float* out);
 int forward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, const nrf_step_scalars* scalars, const nrf_rand* rnd,
                  const nrf_outputs* out, uint32_t flags, float* ws, size_t ws_bytes, hipStream_t stream, int bgN = 0,
                  int elastic = 0, const nrf_background* bg = nullptr);

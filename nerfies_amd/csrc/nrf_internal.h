@@ -19,6 +19,11 @@ constexpr int FRAG_TILE_128 = RGB_W * TILE_ROWS;
 constexpr int SMALL_PART = 3080;  // per-workgroup small-gradient partials (see mlp_chain.hip)
 constexpr int RGB_MAX_DEPTH = 4;  // rgb branch layers (modules.py:129-134); layers 1.. are the run-time "extra" 128 x 128 layers
 constexpr int RGB_MAX_EXTRA = RGB_MAX_DEPTH - 1;
+// small_part layout (floats), written by the reverse chains and summed by the plan's reduce table:
+//   db_trunk[8][256] | db_bn[256] | db_rgbh[128] | db_logit[3] | db_alpha
+//   ... | db_rgbx[3][128] (rgb branch layers 1..3; only written and reduced when the branch is deeper than one layer)
+constexpr int SP_DB_TRUNK = 0, SP_DB_BN = 2048, SP_DB_RGBH = 2304, SP_DB_LOGIT = 2432, SP_DB_ALPHA = 2435, SP_DB_RGBX = 2436;
+static_assert(SP_DB_RGBX + RGB_MAX_EXTRA * RGB_W <= SMALL_PART, "small_part too small for the rgb branch bias partials");
 
 // SE3 warp field trunk (warping.py:224-231 defaults): 6 x 128, skip at 4
 constexpr int WARP_W = 128;
@@ -26,6 +31,8 @@ constexpr int WARP_DEPTH = 6;
 constexpr int WARP_SKIP = 4;
 constexpr int WACT_FLOATS = WARP_W * TILE_ROWS;
 constexpr int WARP_SMALL_PART = 784;   // db_trunk[6][128] | db_w[3] | db_v[3] | pad
+constexpr int WSP_DB_TRUNK = 0, WSP_DB_W = 768, WSP_DB_V = 771;
+static_assert(WSP_DB_V + 3 <= WARP_SMALL_PART, "w_small_part too small for the head bias partials");
 constexpr int WARP_MAX_IN = 64;        // padded trunk input width (3 + 6 F_w + G <= 64)
 // workgroups of the SE3 chain kernels resident per CU (= waves per SIMD the register allocation leaves room for): 48 KiB of
 // LDS each, so three fit once the kernels stay within 168 VGPRs
@@ -241,7 +248,7 @@ struct ChainBwdArgs {
   int* tile_counter;
   int k_old;                 // as ChainFwdArgs
   int alpha_on_bn;           // use_alpha_condition: d raw sigma enters at the bottleneck instead of the trunk output
-  // rgb branch layers 1..nx (as ChainFwdArgs); their bias partials: small_part + SP_DB_RGBX (mlp_chain.hip)
+  // rgb branch layers 1..nx (as ChainFwdArgs); their bias partials: small_part + SP_DB_RGBX
   int nx;
   const uint32_t* bits_rgbx;
   float* dy_rgbx;            // [nx][ntiles][128*64] dpre of layers 1..nx

@@ -502,12 +502,14 @@ void Planner::shapes() {
     p.rows[lv] = lv == BG ? k.bgN : k.B * p.S[lv];
     p.ntiles[lv] = (p.rows[lv] + TILE_ROWS - 1) / TILE_ROWS;
   }
-  {   // the reverse chain's tiling is part of the plan (the reduce table sums one bias partial per workgroup of that launch);
-      // the 32-row reverse kernel has no d-points path: models with a warp field keep the 64-row one
-    int nt_mlp = 0;
-    for (int q = 0; q < h->nlevels; ++q) nt_mlp += p.ntiles[q];
-    p.bwd32 = train && !bft && !h->warp && chain32_for(h, nt_mlp, true);   // (false for an rgb branch deeper than one layer)
-  }
+  // the reverse chains' tiling and grids are part of the plan (the reduce table sums one bias partial per workgroup of those
+  // launches); the 32-row reverse kernel has no d-points path: models with a warp field keep the 64-row one
+  int nt_mlp = 0;
+  for (int q = 0; q < h->nlevels; ++q) nt_mlp += p.ntiles[q];
+  p.bwd32 = train && !bft && !h->warp && chain32_for(h, nt_mlp, true);   // (false for an rgb branch deeper than one layer)
+  // ONE dgrad launch over the tiles of all levels: two workgroups per CU on 64-row tiles, four on 32-row half tiles
+  p.grid_mlp_bwd = p.bwd32 ? tile_grid(2 * nt_mlp, 4, G) : tile_grid(nt_mlp, 2, G);
+  p.grid_warp_bwd = tile_grid(nt_mlp + p.ntiles[BG], warp_grid_mul(), G);   // ONE SE3 dgrad launch: + the background tiles (0 without that batch)
   p.tg_tiles_per = jac ? p.ntiles[h->nlevels - 1] : k.elastic ? p.ntiles[0] : 0;   // Jacobian output: levels run one after the other
   p.ntiles[TG] = 3 * p.tg_tiles_per;
   p.rows[TG] = p.ntiles[TG] * TILE_ROWS;
@@ -827,7 +829,7 @@ void Planner::buffers() {
   if (h->warp) p.warp_wpk = take(h->wpk.total);
   p.seg_clock = take(2 * (p.segs.size() + 1));
   p.counters = take(64);
-  p.timeline = take(2 * (2 * 4 * 64 + 1024 + 4 * 4096));
+  p.timeline = take(2 * TIMELINE_LEVEL_F);
 }
 
 // ---- pack descriptors (both levels, forward and transposed streams); a bf16 TRAINING plan reads only the bf16 images of the
@@ -923,34 +925,28 @@ void Planner::bf16_groups() {
 
 // ---- bias gradients of the fp32 dgrad launches (per-workgroup partials) and the per-ray condition rows ----
 void Planner::bias_reduces() {
-  int nt_mlp = 0;
-  for (int q = 0; q < h->nlevels; ++q) nt_mlp += p.ntiles[q];
-  // ONE dgrad launch over the tiles of all levels: two workgroups per CU on 64-row tiles, four on 32-row half tiles
-  const int grid = p.bwd32 ? (2 * nt_mlp < 4 * G ? 2 * nt_mlp : 4 * G) : (nt_mlp < 2 * G ? nt_mlp : 2 * G);
   for (int lv = 0; lv < h->nlevels; ++lv) {
     const MlpParamOffsets& po = h->po[lv];
     const LevelWs& L = p.L[lv];
     auto small = [&](int64_t dst, int cols, int sp_off) {
       if (bft) return;   // the bf16 wgrad kernel sums the bias columns itself
-      add_reduce(reduce_desc(dst, cols, 1, cols, (int64_t)L.small_part + sp_off, cols, SMALL_PART, grid));
+      add_reduce(reduce_desc(dst, cols, 1, cols, (int64_t)L.small_part + sp_off, cols, SMALL_PART, p.grid_mlp_bwd));
     };
-    for (int l = 0; l < TRUNK_DEPTH; ++l) small(po.trunk_b[l], 256, l * 256);
-    small(po.bn_b, 256, 2048);
-    small(po.rgbh_b, 128, 2304);
-    small(po.logit_b, 3, 2432);
-    small(po.alpha_b, 1, 2435);
-    for (int x = 0; x < d.nerf_rgb_branch_depth - 1; ++x) small(po.rgbx_b[x], 128, 2436 + x * 128);   // SP_DB_RGBX (mlp_chain.hip)
+    for (int l = 0; l < TRUNK_DEPTH; ++l) small(po.trunk_b[l], TRUNK_W, SP_DB_TRUNK + l * TRUNK_W);
+    small(po.bn_b, TRUNK_W, SP_DB_BN);
+    small(po.rgbh_b, RGB_W, SP_DB_RGBH);
+    small(po.logit_b, 3, SP_DB_LOGIT);
+    small(po.alpha_b, 1, SP_DB_ALPHA);
+    for (int x = 0; x < d.nerf_rgb_branch_depth - 1; ++x) small(po.rgbx_b[x], RGB_W, SP_DB_RGBX + x * RGB_W);
     if (h->R > 0) add_reduce(reduce_desc(po.rgbh_k + 256 * 128, 128, h->R, 128, (int64_t)L.cond_grad, 128, 0, 1));
-    if (h->warp && !bfw && lv == 0) {   // ONE SE3 dgrad launch (coarse + fine + background tiles), one set of bias partials
-      const int nt_w = nt_mlp + (p.key.bgN > 0 ? p.ntiles[BG] : 0);
-      const int wgrid = nt_w < warp_grid_mul() * G ? nt_w : warp_grid_mul() * G;
+    if (h->warp && !bfw && lv == 0) {   // the SE3 dgrad launch writes one set of bias partials for all its levels
       const WarpParamOffsets& w = h->wpo;
       auto wsmall = [&](int64_t dst, int cols, int sp_off) {
-        add_reduce(reduce_desc(dst, cols, 1, cols, (int64_t)L.w_small_part + sp_off, cols, WARP_SMALL_PART, wgrid));
+        add_reduce(reduce_desc(dst, cols, 1, cols, (int64_t)L.w_small_part + sp_off, cols, WARP_SMALL_PART, p.grid_warp_bwd));
       };
-      for (int l = 0; l < WARP_DEPTH; ++l) wsmall(w.trunk_b[l], WARP_W, l * WARP_W);
-      wsmall(w.w_b, 3, 768);
-      wsmall(w.v_b, 3, 771);
+      for (int l = 0; l < WARP_DEPTH; ++l) wsmall(w.trunk_b[l], WARP_W, WSP_DB_TRUNK + l * WARP_W);
+      wsmall(w.w_b, 3, WSP_DB_W);
+      wsmall(w.v_b, 3, WSP_DB_V);
     }
   }
 }
