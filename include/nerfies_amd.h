@@ -37,7 +37,9 @@
 extern "C" {
 #endif
 
-#define NRF_VERSION 610 /* 0.6.1: nerf_rgb_branch_depth accepts 1..4 (float32 mode, 64-row chains; the bfloat16 / split-bf16 modes and
+#define NRF_VERSION 620 /* 0.6.2: nrf_backward_ex (nrf_output_grads): cotangents for depth, acc, weights and warped_points next to
+                           rgb.  nrf_backward is unchanged.
+                           0.6.1: nerf_rgb_branch_depth accepts 1..4 (float32 mode, 64-row chains; the bfloat16 / split-bf16 modes and
                            NRF_OPT_CHAIN_TILE_ROWS = 32 are refused for a handle with depth > 1); the parameter layout then holds
                            MLP_1/hidden_1.. of both levels.  Nothing changes for depth 1.
                            0.6.0: nrf_model_desc grows warp_trunk_depth / warp_trunk_width (SE3Field / TranslationField trunk_depth <= 6,
@@ -269,6 +271,33 @@ int nrf_backward(nrf_handle h, const float* params, const nrf_rays* rays,
                  const float* d_rgb_coarse, const float* d_rgb_fine,
                  float* grad_params, void* workspace, size_t workspace_bytes,
                  void* stream);
+
+/* The cotangents of one level of the NerfModel output dict (models.py:278-287), the counterpart of nrf_level_out.  Any pointer
+ * may be NULL, which means zero. */
+typedef struct nrf_level_grads {
+  const float* d_rgb;           /* (B,3) */
+  const float* d_depth;         /* (B,)   depth = sum_i w_i z_i; the sample depths carry no gradient (the coarse ones do not
+                                   depend on the parameters, the fine ones sit behind stop_gradient, model_utils.py:187) */
+  const float* d_acc;           /* (B,)   acc = sum_i w_i, without the last sample under use_sample_at_infinity (model_utils.py:125-126) */
+  const float* d_weights;       /* (B,S) */
+  const float* d_warped_points; /* (B,S,3) needs a stashed forward that ran the warp field (NRF_E_STATE otherwise) */
+} nrf_level_grads;
+
+typedef struct nrf_output_grads {
+  nrf_level_grads coarse;
+  nrf_level_grads fine;
+} nrf_output_grads;
+
+/* Since 0.6.2: nrf_backward with a cotangent for every differentiable output of the stashed nrf_forward(NRF_FLAG_TRAIN) -- the
+ * VJP of NerfModel.apply proper (depth supervision, a mask term on acc, distortion / entropy terms on weights, a regulariser on
+ * the warped points).  Same state checks as nrf_backward (stashed workspace, ray count, plan); float32 and NRF_FLAG_BF16
+ * training stashes alike; no allocation, no synchronisation; grad_params is OVERWRITTEN.  All pointers NULL: a zero gradient.
+ * med_depth is piecewise constant in the parameters: it has no cotangent.  Out of scope: a cotangent of warp_jacobian (its
+ * adjoint exists only inside the elastic regulariser of nrf_train_step_loss_grad_ex), and extra cotangents through the fused
+ * nrf_train_step_loss_grad[_ex], whose loss is fixed.  nrf_backward(.., c, f, ..) == nrf_backward_ex with only d_rgb set. */
+int nrf_backward_ex(nrf_handle h, const float* params, const nrf_rays* rays,
+                    const nrf_output_grads* g, float* grad_params,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* training.train_step up to (excluding) pmean + Adam (training.py:168-265):
  * forward, loss = MSE_coarse + MSE_fine (training.py:172,261), backward.

@@ -178,8 +178,9 @@ int nrf_forward(nrf_handle h, const float* params, const nrf_rays* rays, const n
   return forward_impl(h, params, rays, scalars, rnd, out, flags, (float*)workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-int nrf_backward(nrf_handle h, const float* params, const nrf_rays* rays, const float* d_rgb_coarse,
-                 const float* d_rgb_fine, float* grad_params, void* workspace, size_t workspace_bytes, void* stream) {
+// nrf_backward / nrf_backward_ex: the state checks, the zero stand-in of a missing d_rgb, the reverse pass
+static int backward_checked(nrf_handle h, const float* params, const nrf_rays* rays, nrf_output_grads g, float* grad_params,
+                            void* workspace, size_t workspace_bytes, void* stream) {
   if (!h || !params || !rays || !grad_params || !workspace) return fail(NRF_E_NULL, "null argument");
   if (h->stashed_ws != workspace || h->stashed_B != rays->num_rays)
     return fail(NRF_E_STATE, "nrf_backward needs a preceding nrf_forward(NRF_FLAG_TRAIN) on this workspace");
@@ -187,15 +188,33 @@ int nrf_backward(nrf_handle h, const float* params, const nrf_rays* rays, const 
     return fail(NRF_E_STATE, "nrf_backward: the workspace layout changed since the stashed nrf_forward (an intervening call with "
                              "another num_rays / flags); run nrf_forward(NRF_FLAG_TRAIN) again");
   if (workspace_bytes < h->plan.total_floats * sizeof(float)) return fail(NRF_E_WORKSPACE, "workspace too small");
+  if (h->nlevels < 2) g.fine = nrf_level_grads{};   // no fine level: nothing to read
+  if ((g.coarse.d_warped_points || g.fine.d_warped_points) && !h->stashed_modes.warp_on)
+    return fail(NRF_E_STATE, "nrf_backward_ex: d_warped_points given, but the stashed nrf_forward ran without the warp field "
+                             "(there are no warped points to carry a gradient)");
   float* ws = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
   const float* zero = ws + h->plan.zero_rgb;
-  if (!d_rgb_coarse || (h->nlevels > 1 && !d_rgb_fine)) {
+  if (!g.coarse.d_rgb || (h->nlevels > 1 && !g.fine.d_rgb)) {
     hipError_t e = hipMemsetAsync(ws + h->plan.zero_rgb, 0, (size_t)rays->num_rays * 3 * sizeof(float), st);
     if (e != hipSuccess) return fail_hip(e, "zero d_rgb");
   }
-  const float* dr[2] = {d_rgb_coarse ? d_rgb_coarse : zero, d_rgb_fine ? d_rgb_fine : zero};
-  return backward_impl(h, params, rays, dr, nullptr, grad_params, nullptr, ws, st);
+  if (!g.coarse.d_rgb) g.coarse.d_rgb = zero;
+  if (!g.fine.d_rgb) g.fine.d_rgb = zero;
+  return backward_impl(h, params, rays, &g, nullptr, grad_params, nullptr, ws, st);
+}
+
+int nrf_backward(nrf_handle h, const float* params, const nrf_rays* rays, const float* d_rgb_coarse,
+                 const float* d_rgb_fine, float* grad_params, void* workspace, size_t workspace_bytes, void* stream) {
+  nrf_output_grads g{};
+  g.coarse.d_rgb = d_rgb_coarse; g.fine.d_rgb = d_rgb_fine;
+  return backward_checked(h, params, rays, g, grad_params, workspace, workspace_bytes, stream);
+}
+
+int nrf_backward_ex(nrf_handle h, const float* params, const nrf_rays* rays, const nrf_output_grads* g, float* grad_params,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+  if (!g) return fail(NRF_E_NULL, "nrf_output_grads is null (pass a zeroed struct for a zero gradient)");
+  return backward_checked(h, params, rays, *g, grad_params, workspace, workspace_bytes, stream);
 }
 
 int nrf_train_step_loss_grad(nrf_handle h, const float* params, const nrf_rays* rays, const float* target_rgb,
@@ -204,8 +223,7 @@ int nrf_train_step_loss_grad(nrf_handle h, const float* params, const nrf_rays* 
   if (!h || !target_rgb || !grad_params) return fail(NRF_E_NULL, "null argument");
   CK(forward_impl(h, params, rays, scalars, rnd, nullptr, NRF_FLAG_TRAIN, (float*)workspace, workspace_bytes,
                   (hipStream_t)stream));
-  const float* dr[2] = {nullptr, nullptr};
-  return backward_impl(h, params, rays, dr, target_rgb, grad_params, stats, (float*)workspace, (hipStream_t)stream);
+  return backward_impl(h, params, rays, nullptr, target_rgb, grad_params, stats, (float*)workspace, (hipStream_t)stream);
 }
 
 int nrf_train_step_loss_grad_ex(nrf_handle h, const float* params, const nrf_rays* rays, const float* target_rgb,
@@ -236,8 +254,7 @@ int nrf_train_step_loss_grad_ex(nrf_handle h, const float* params, const nrf_ray
   }
   CK(forward_impl(h, params, rays, scalars, rnd, nullptr, NRF_FLAG_TRAIN | flags, (float*)workspace, workspace_bytes,
                   (hipStream_t)stream, bgN, el ? 1 : 0, bgN > 0 ? bg : nullptr));
-  const float* dr[2] = {nullptr, nullptr};
-  return backward_impl(h, params, rays, dr, target_rgb, grad_params, stats, (float*)workspace, (hipStream_t)stream,
+  return backward_impl(h, params, rays, nullptr, target_rgb, grad_params, stats, (float*)workspace, (hipStream_t)stream,
                        bgN > 0 ? bg : nullptr, scalars, el, wr, /*bg_forward_done=*/bgN > 0);
 }
 

@@ -260,7 +260,7 @@ WarpFwdArgs warp_points_args(nrf_handle h, const float* params, const WarpParamO
 int forward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, const nrf_step_scalars* scalars, const nrf_rand* rnd,
                  const nrf_outputs* out, uint32_t flags, float* ws, size_t ws_bytes, hipStream_t stream, int bgN = 0,
                  int elastic = 0, const nrf_background* bg = nullptr);
-int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, const float* const d_rgb[2], const float* target,
+int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, const nrf_output_grads* og, const float* target,
                   float* grad_x, float* stats, float* ws, hipStream_t stream, const nrf_background* bg = nullptr,
                   const nrf_step_scalars* scalars = nullptr, const nrf_elastic* el = nullptr, const nrf_warp_reg* wr = nullptr,
                   bool bg_forward_done = false);

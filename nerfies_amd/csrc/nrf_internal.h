@@ -479,9 +479,17 @@ struct CompositeBwdArgs {
   float4* d_raw4; int rows_pad;
   float* mse_ray;      // [B] squared error per ray (or nullptr)
   float* dsig_ray;     // [B] sum of d sigma_raw over the ray (use_alpha_condition) or nullptr
+  // cotangents of the other rendered outputs (nrf_backward_ex), each nullptr = zero: every one is linear in the weights, so they
+  // only add to the per-sample scalar g_i the recurrence runs on
+  const float* d_depth;   // [B]
+  const float* d_acc;     // [B]
+  const float* d_w;       // [B][S]
 };
 struct CompositeBwdArgs2 { CompositeBwdArgs a[2]; };
-void launch_composite_bwd(const CompositeBwdArgs& a0, const CompositeBwdArgs* a1, hipStream_t stream);   // a1: second level or nullptr
+// a1: second level or nullptr.  The kernel that reads d_depth / d_acc / d_w is launched only when one of them is set at either level
+void launch_composite_bwd(const CompositeBwdArgs& a0, const CompositeBwdArgs* a1, hipStream_t stream);
+// d_points[rows][3] += d_warped[rows][3]: the caller's cotangent of the warped points (nrf_backward_ex), ahead of the SE3 dgrad
+void launch_add_point_cotangent(const float* d_warped, int rows, float* d_points, hipStream_t stream);
 // use_alpha_condition: gradient of the appearance-code rows of the alpha head and of the codes through it
 void launch_alpha_cond_grad(const float* params, const float* cond, const float* dsig_ray, const int32_t* app_ids, int B, int R,
                             int V, int app_feat, int64_t app_off, int64_t alpha_k, float* grad, hipStream_t stream);

@@ -347,10 +347,11 @@ struct Forward : Run {
 
 struct Backward : Run {
   const nrf_elastic* el;  const nrf_warp_reg* wr;  const bool el_on, wr_on;
+  const nrf_output_grads* og;   // the caller's cotangents (nrf_backward[_ex]) or nullptr (fused step: the MSE loss against `target`)
   float* grad = nullptr;   // INTERNAL layout, as params
   double mlp_rows = 0;     // samples of all levels
-  Backward(const Run& r, const nrf_elastic* el_, const nrf_warp_reg* wr_)
-      : Run(r), el(el_), wr(wr_), el_on(el_ && p.key.elastic && m.warp_on), wr_on(wr_ && m.warp_on) {
+  Backward(const Run& r, const nrf_elastic* el_, const nrf_warp_reg* wr_, const nrf_output_grads* og_)
+      : Run(r), el(el_), wr(wr_), el_on(el_ && p.key.elastic && m.warp_on), wr_on(wr_ && m.warp_on), og(og_) {
     for (int lv = 0; lv < h->nlevels; ++lv) mlp_rows += p.rows[lv];
   }
   int zero() const {   // everything that is accumulated into, zeroed by one launch
@@ -368,7 +369,9 @@ struct Backward : Run {
     return NRF_OK;
   }
 
-  void composite_bwd(const float* const d_rgb[2], const float* target) {
+  const nrf_level_grads* level_grads(int lv) const { return !og ? nullptr : lv == 0 ? &og->coarse : &og->fine; }
+
+  void composite_bwd(const float* target) {
     CompositeBwdArgs ca[2];
     for (int lv = 0; lv < h->nlevels; ++lv) {
       const LevelWs& L = p.L[lv];
@@ -376,7 +379,8 @@ struct Backward : Run {
       memset(&c, 0, sizeof(c));
       c.out4 = f4(L.out4); c.z = ws + L.z; c.dirs = rays->directions; c.sigma_act = d.sigma_activation;
       c.B = B; c.S = p.S[lv]; c.white_bkgd = d.use_white_background; c.sample_at_inf = d.use_sample_at_infinity;
-      c.rgb_out = ws + L.rgb; c.target = target; c.d_rgb = target ? nullptr : d_rgb[lv];
+      c.rgb_out = ws + L.rgb; c.target = target;
+      if (const nrf_level_grads* g = level_grads(lv)) { c.d_rgb = g->d_rgb; c.d_depth = g->d_depth; c.d_acc = g->d_acc; c.d_w = g->d_weights; }
       c.loss_scale = 2.0f / (3.0f * (float)B);   // d/d rgb of mean over (B,3) (training.py:172)
       c.d_raw4 = f4(L.d_raw4); c.rows_pad = rows_pad(lv);
       c.mse_ray = ws + p.mse + (size_t)lv * B; c.dsig_ray = h->A > 0 ? ws + L.dsig_ray : nullptr;
@@ -450,8 +454,11 @@ struct Backward : Run {
     launch_elastic(ea, stream);
     pf.end(stream);
   }
-  // the regularisers' gradients w.r.t. the warped points, added into d_points ahead of the SE3 dgrad
+  // the caller's and the regularisers' gradients w.r.t. the warped points, added into d_points ahead of the SE3 dgrad
   void point_regularisers() {
+    for (int lv = 0; lv < h->nlevels && m.warp_on; ++lv)   // nrf_backward_ex: the caller's own d loss / d warped point
+      if (const nrf_level_grads* g = level_grads(lv))
+        if (g->d_warped_points) launch_add_point_cotangent(g->d_warped_points, p.rows[lv], ws + p.L[lv].d_points, stream);
     if (el_on) elastic();
     if (wr_on)   // use_warp_reg_loss (training.py:199-212): + d loss / d warped point at the median-depth sample of each ray
       for (int lv = 0; lv < h->nlevels; ++lv) {
@@ -603,14 +610,15 @@ int forward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, cons
   return NRF_OK;
 }
 
-// d_rgb[lv] != nullptr: upstream gradient mode; else MSE-loss mode against `target`.
+// og != nullptr: upstream gradient mode, the cotangents of the rendered outputs (nrf_backward[_ex]; d_rgb of every level set by the
+// caller); else MSE-loss mode against `target` (the fused train step).
 // Launch order (round 3): the reverse passes of the two levels are independent, so every kernel type runs ONCE
 // over the tiles of all levels -- composite_bwd x levels, ONE NeRF-MLP dgrad launch (coarse + fine tiles), the regularisers'
 // point gradients, ONE SE3 dgrad launch (coarse + fine + background tiles), the tangent pass, then wgrad / reduce.
-int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, const float* const d_rgb[2], const float* target,
+int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, const nrf_output_grads* og, const float* target,
                   float* grad_x, float* stats, float* ws, hipStream_t stream, const nrf_background* bg,
                   const nrf_step_scalars* scalars, const nrf_elastic* el, const nrf_warp_reg* wr, bool bg_forward_done) {
-  Backward b(Run(h, h->stashed_modes, ws, stream, rays, scalars, bg), el, wr);
+  Backward b(Run(h, h->stashed_modes, ws, stream, rays, scalars, bg), el, wr, og);
   // the gradient buffer is zero-filled and accumulated into with 16-byte accesses (zero_ranges_kernel, reduce passes)
   if ((reinterpret_cast<uintptr_t>(grad_x) & 15u) != 0) return fail(NRF_E_SHAPE, "grad_params must be 16-byte aligned");
   // p.bwd32 alone selects the 32-row reverse path (zeroed slices and launch); that kernel has no d-points output
@@ -622,7 +630,7 @@ int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, con
   b.params = h->embed ? ws + b.p.iparams : params_x;
   b.grad = h->embed ? ws + b.p.igrad : grad_x;
   CK(b.zero());
-  b.composite_bwd(d_rgb, target);
+  b.composite_bwd(target);
   b.mlp_dgrad();
   b.point_regularisers();
   if (b.m.warp_on) b.warp_dgrad();

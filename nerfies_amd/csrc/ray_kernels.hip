@@ -203,6 +203,10 @@ void launch_composite_fwd(const float4* out4, const float* z, const float* dirs,
 // With g_i = c_i . dL/drgb, t_i = 1-alpha_i+1e-10 and Q_i = sum_{k>i} g_k alpha_k prod_{i<j<k} t_j
 // (reverse affine recurrence Q_i = g_{i+1} alpha_{i+1} + t_{i+1} Q_{i+1}; division free):
 //   dL/dalpha_i = T_i (g_i - Q_i);  dL/dsigma_i = dist_i exp(-sigma_i dist_i) dL/dalpha_i;  dL/dc_i = w_i dL/drgb.
+// EXTRA: cotangents of the other outputs of model_utils.py:116-126, all linear in the weights (depth = sum w_i z_i with z behind
+// stop_gradient, acc = sum w_i without the sample at infinity, weights_i = w_i), so they only add to g_i:
+//   g_i += d_depth z_i + d_acc [i < S-1 or not sample_at_inf] + d_w[i];   dL/dc_i stays w_i dL/drgb.
+template <bool EXTRA>
 __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompositeBwdArgs2 P) {
   const CompositeBwdArgs& A = P.a[blockIdx.y];   // blockIdx.y = level: both levels in one launch (kernarg-indexed, scalar loads)
   const float4* __restrict__ out4 = A.out4;
@@ -241,6 +245,13 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompositeBwdAr
   const float* zr = z + (size_t)ray * S;
   const float4* cr = out4 + (size_t)ray * S;
   const int E = (S + 63) >> 6;
+  float g_depth = 0.f, g_acc = 0.f;
+  const float* __restrict__ dwr = nullptr;
+  if constexpr (EXTRA) {
+    if (A.d_depth) g_depth = A.d_depth[ray];
+    if (A.d_acc) g_acc = A.d_acc[ray];
+    if (A.d_w) dwr = A.d_w + (size_t)ray * S;
+  }
   float Tv[MAX_E], av[MAX_E], tv[MAX_E], dv[MAX_E], gv[MAX_E];
   float4 cv[MAX_E];
   float Tc = 1.f;
@@ -264,6 +275,13 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompositeBwdAr
       Tc *= __shfl(incl, 63);
       float g = c.x * g0 + c.y * g1 + c.z * g2;
       if (white_bkgd) g -= gsum;
+      if constexpr (EXTRA) {
+        if (valid) {
+          g += g_depth * zr[s];                                // depth = sum w_i z_i (model_utils.py:121)
+          if (s < S - 1 || !sample_at_inf) g += g_acc;         // acc leaves the sample at infinity out (:125-126)
+          if (dwr) g += dwr[s];                                // one coalesced load per 64-sample chunk
+        }
+      }
       Tv[e] = T; av[e] = alpha; tv[e] = tt; dv[e] = dist; gv[e] = valid ? g : 0.f; cv[e] = c;
     }
   }
@@ -309,7 +327,22 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompositeBwdAr
 void launch_composite_bwd(const CompositeBwdArgs& a0, const CompositeBwdArgs* a1, hipStream_t stream) {
   CompositeBwdArgs2 p;
   p.a[0] = a0; p.a[1] = a1 ? *a1 : a0;
-  hipLaunchKernelGGL(composite_bwd_kernel, dim3((a0.B + 3) / 4, a1 ? 2 : 1), dim3(256), 0, stream, p);
+  const bool extra = p.a[0].d_depth || p.a[0].d_acc || p.a[0].d_w || p.a[1].d_depth || p.a[1].d_acc || p.a[1].d_w;
+  const dim3 grid((a0.B + 3) / 4, a1 ? 2 : 1);
+  if (extra) hipLaunchKernelGGL(composite_bwd_kernel<true>, grid, dim3(256), 0, stream, p);
+  else hipLaunchKernelGGL(composite_bwd_kernel<false>, grid, dim3(256), 0, stream, p);
+}
+
+// The caller's cotangent of the warped points (nrf_backward_ex) joins dL/dx' where the regularisers' do: added into d_points
+// (written before by the NeRF MLP's dgrad), one float per thread over (rows, 3).
+__global__ void add_point_cotangent_kernel(const float* __restrict__ d_warped, long long n, float* __restrict__ d_points) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) d_points[i] += d_warped[i];
+}
+
+void launch_add_point_cotangent(const float* d_warped, int rows, float* d_points, hipStream_t stream) {
+  const long long n = 3LL * rows;
+  hipLaunchKernelGGL(add_point_cotangent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_warped, n, d_points);
 }
 
 // ------------------------------------------------------------------ hierarchical sampling

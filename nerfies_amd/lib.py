@@ -81,6 +81,16 @@ class Outputs(C.Structure):
   _fields_ = [('coarse', LevelOut), ('fine', LevelOut)]
 
 
+class LevelGrads(C.Structure):
+  """nrf_level_grads: the cotangents of one level's outputs (nrf_backward_ex); a NULL pointer means zero."""
+  _fields_ = [('d_rgb', C.c_void_p), ('d_depth', C.c_void_p), ('d_acc', C.c_void_p), ('d_weights', C.c_void_p),
+              ('d_warped_points', C.c_void_p)]
+
+
+class OutputGrads(C.Structure):
+  _fields_ = [('coarse', LevelGrads), ('fine', LevelGrads)]
+
+
 class Background(C.Structure):
   _fields_ = [('num_points', C.c_int32), ('points', C.c_void_p), ('warp_ids', C.c_void_p), ('loss_weight', C.c_float),
               ('loss_alpha', C.c_float), ('loss_scale', C.c_float), ('id_choices', C.c_void_p), ('num_choices', C.c_int32),
@@ -118,7 +128,7 @@ EXPORTS = [
     'nrf_debug_wgrad_segments', 'nrf_debug_ws_offset', 'nrf_train_step_loss_grad_ex', 'nrf_workspace_bytes_ex',
     'nrf_warp_points_workspace_bytes', 'nrf_warp_points',
     'nrf_camera_pixels_to_rays', 'nrf_camera_pixels_to_points', 'nrf_camera_project',
-    'nrf_dynamic_scalars_write', 'nrf_adam_step_dynamic', 'nrf_set_option', 'nrf_debug_plan_digest',
+    'nrf_dynamic_scalars_write', 'nrf_adam_step_dynamic', 'nrf_set_option', 'nrf_debug_plan_digest', 'nrf_backward_ex',
 ]
 
 _lib = None
@@ -150,6 +160,7 @@ def load_library(path=None):
       'nrf_forward': [vp, vp, C.POINTER(Rays), C.POINTER(StepScalars), C.POINTER(Rand), C.POINTER(Outputs), u32, vp,
                       C.c_size_t, vp],
       'nrf_backward': [vp, vp, C.POINTER(Rays), vp, vp, vp, vp, C.c_size_t, vp],
+      'nrf_backward_ex': [vp, vp, C.POINTER(Rays), C.POINTER(OutputGrads), vp, vp, C.c_size_t, vp],
       'nrf_train_step_loss_grad': [vp, vp, C.POINTER(Rays), vp, C.POINTER(StepScalars), C.POINTER(Rand), vp, vp, vp,
                                    C.c_size_t, vp],
       'nrf_adam_step': [vp, vp, vp, vp, i64, f64, f64, f64, f64, i64, f64, vp],

@@ -429,8 +429,11 @@ class NerfModel:
     del keep, keep2
     return ret
 
-  def backward(self, variables, rays_dict, d_rgb_coarse, d_rgb_fine, grad_out: torch.Tensor = None):
-    """VJP of the last `apply(..., train=True)` on the same rays: returns the flat parameter gradient."""
+  def backward(self, variables, rays_dict, d_rgb_coarse=None, d_rgb_fine=None, grad_out: torch.Tensor = None, d_out=None):
+    """VJP of the last `apply(..., train=True)` on the same rays: returns the flat parameter gradient.
+    `d_out` = {'coarse': {...}, 'fine': {...}} carries a cotangent for any of 'rgb' (B,3), 'depth' (B,), 'acc' (B,),
+    'weights' (B,S) and 'warped_points' (B,S,3) per level (nrf_backward_ex); what is absent (or None) counts as zero.
+    'med_depth' is piecewise constant and has none.  `d_rgb_coarse` / `d_rgb_fine` are the 'rgb' entries, positionally."""
     device = torch.as_tensor(rays_dict['origins']).device
     fp = self.flat_params(variables, device)
     rays, keep = self._rays_struct(rays_dict, device)
@@ -444,10 +447,43 @@ class NerfModel:
       raise L.NrfError(f'backward(): the stashed forward was run on {stash[0]} rays, not {rays.num_rays}')
     ws = stash[1]   # the library also refuses a stash whose workspace plan was replaced by another call (NRF_E_STATE)
     stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    L.check(self.lib.nrf_backward(self.handle, _ptr(fp.flat), C.byref(rays), _ptr(dc), _ptr(df), _ptr(grad), _ptr(ws),
-                                  ws.numel() * 4, stream), self.lib)
+    if d_out is None:
+      L.check(self.lib.nrf_backward(self.handle, _ptr(fp.flat), C.byref(rays), _ptr(dc), _ptr(df), _ptr(grad), _ptr(ws),
+                                    ws.numel() * 4, stream), self.lib)
+    else:
+      og, keep2 = self._output_grads(d_out, {'coarse': dc, 'fine': df}, rays.num_rays, device)
+      L.check(self.lib.nrf_backward_ex(self.handle, _ptr(fp.flat), C.byref(rays), C.byref(og), _ptr(grad), _ptr(ws),
+                                       ws.numel() * 4, stream), self.lib)
+      del keep2
     del keep
     return grad
+
+  def _output_grads(self, d_out, d_rgb, B, device):
+    """lib.OutputGrads of a `backward(d_out=...)` dict.  Every buffer is read by the kernels at its full size, so the shapes are
+    checked here."""
+    S = {'coarse': self.num_coarse_samples, 'fine': self.num_coarse_samples + self.num_fine_samples}
+    og, keep = L.OutputGrads(), []
+    unknown = set(d_out) - set(S)
+    if unknown or ('fine' in d_out and d_out['fine'] and self.num_fine_samples <= 0):
+      raise L.NrfError(f"backward(d_out=...): levels {sorted(unknown) or ['fine']} do not exist in this model")
+    for name, lg in (('coarse', og.coarse), ('fine', og.fine)):
+      level = dict(d_out.get(name) or {})
+      if d_rgb[name] is not None:
+        if level.get('rgb') is not None:
+          raise L.NrfError(f"backward(): the rgb cotangent of level {name!r} was given twice (positionally and in d_out)")
+        level['rgb'] = d_rgb[name]
+      shapes = {'rgb': (B, 3), 'depth': (B,), 'acc': (B,), 'weights': (B, S[name]), 'warped_points': (B, S[name], 3)}
+      for key, t in level.items():
+        if key not in shapes:
+          raise L.NrfError(f"backward(d_out=...): {name}/{key} has no cotangent (differentiable outputs: {sorted(shapes)})")
+        if t is None:
+          continue
+        t = _f32(t, device)
+        if tuple(t.shape) != shapes[key]:
+          raise L.NrfError(f"backward(d_out=...): {name}/{key} must have shape {shapes[key]}, got {tuple(t.shape)}")
+        keep.append(t)
+        setattr(lg, 'd_' + key, _ptr(t))
+    return og, keep
 
   def loss_and_grad(self, fp: P.FlatParams, batch, warp_extra=None, rngs=None, grad_out=None, stats_out=None,
                     background=None, elastic=None, warp_reg=None, bf16=False, dynamic=None):
