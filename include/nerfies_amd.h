@@ -37,7 +37,9 @@
 extern "C" {
 #endif
 
-#define NRF_VERSION 620 /* 0.6.2: nrf_backward_ex (nrf_output_grads): cotangents for depth, acc, weights and warped_points next to
+#define NRF_VERSION 630 /* 0.6.3: NRF_FLAG_RAY_GRADS + nrf_backward_rays (nrf_ray_grads): gradients w.r.t. the ray origins, directions and
+                           viewdirs (float32 training mode).  nrf_backward / nrf_backward_ex and every plan without the flag are unchanged.
+                           0.6.2: nrf_backward_ex (nrf_output_grads): cotangents for depth, acc, weights and warped_points next to
                            rgb.  nrf_backward is unchanged.
                            0.6.1: nerf_rgb_branch_depth accepts 1..4 (float32 mode, 64-row chains; the bfloat16 / split-bf16 modes and
                            NRF_OPT_CHAIN_TILE_ROWS = 32 are refused for a handle with depth > 1); the parameter layout then holds
@@ -242,6 +244,15 @@ typedef struct nrf_outputs {
                                      the float32 kernels (bit-identical warped points; a call that returns the warp Jacobian uses them
                                      anyway).  Not with NRF_FLAG_TRAIN or NRF_FLAG_BF16; same model limits as NRF_FLAG_BF16 */
 
+#define NRF_FLAG_RAY_GRADS 64u     /* since 0.6.3, with NRF_FLAG_TRAIN on nrf_forward / nrf_workspace_bytes[_ex]: keep what nrf_backward_rays needs
+                                     to differentiate the stashed call w.r.t. the rays -- a d-points buffer and the transposed layer-0 / skip-row
+                                     weight images for a model without a warp field (it then runs the 64-row reverse chain), the warp Jacobian
+                                     of every sample ([rows][9] per level, one forward-mode tangent pass per level behind the primal pass) for
+                                     a model with one.  Float32 mode only: refused (NRF_E_UNSUPPORTED) without NRF_FLAG_TRAIN, with NRF_FLAG_BF16 /
+                                     NRF_FLAG_BF16X3 and by the fused nrf_train_step_loss_grad[_ex].  NRF_OPT_CHAIN_TILE_ROWS = 32 is NOT refused:
+                                     under the flag it is followed by the forward chain only, as on a model with a warp field (the 32-row
+                                     reverse chain has no d-points section, so the reverse pass runs on 64-row tiles over the same stash) */
+
 int nrf_version(void);
 const char* nrf_last_error(void);
 
@@ -298,6 +309,23 @@ typedef struct nrf_output_grads {
 int nrf_backward_ex(nrf_handle h, const float* params, const nrf_rays* rays,
                     const nrf_output_grads* g, float* grad_params,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* Since 0.6.3: the gradients of the stashed call w.r.t. its rays, each (B,3); any pointer may be NULL, which skips that part. */
+typedef struct nrf_ray_grads {
+  float* d_origins;    /* sum over levels and samples of J_s^T g_s: g_s = dL/d(warped point s), J_s = the warp Jacobian (I without the field) */
+  float* d_directions; /* sum z_s J_s^T g_s, plus the term of the compositing distances (z_{i+1} - z_i) |d| (model_utils.py:104-110).  The
+                          sample depths are constants (the coarse ones do not depend on the ray, the fine ones sit behind stop_gradient) */
+  float* d_viewdirs;   /* through the rgb condition's posenc(viewdirs); needs use_viewdirs and rays->viewdirs (the normalisation
+                          viewdirs = d / |d| is the caller's: differentiate it there) */
+} nrf_ray_grads;
+
+/* nrf_backward_ex plus the ray stage: grad_params exactly as nrf_backward_ex writes it, and the three ray gradients (OVERWRITTEN).  The
+ * stashed forward must have run with NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS (NRF_E_STATE otherwise); ray_grads NULL -> NRF_E_NULL; d_viewdirs for
+ * a model without viewdirs, or with rays->viewdirs NULL -> NRF_E_UNSUPPORTED: all decided before any launch.  One wave per ray, no atomics:
+ * d_origins / d_directions of two calls on one stash agree bit for bit (d_viewdirs reads the per-ray sums the reverse chain accumulates).
+ * A cotangent on warped_points reaches the rays through g_s; `points` carries none (rebuild o + z d from z_vals in the caller). */
+int nrf_backward_rays(nrf_handle h, const float* params, const nrf_rays* rays, const nrf_output_grads* grads,
+                      const nrf_ray_grads* ray_grads, float* grad_params, void* workspace, size_t workspace_bytes, void* stream);
 
 /* training.train_step up to (excluding) pmean + Adam (training.py:168-265):
  * forward, loss = MSE_coarse + MSE_fine (training.py:172,261), backward.

@@ -140,8 +140,13 @@ int nrf_param_layout(nrf_handle h, nrf_tensor_info* out, int32_t* n) {
 // (they used to pass through: NRF_FLAG_WARP_F32 without NRF_FLAG_BF16 was silently ignored, and TRAIN | WARP_JACOBIAN sized a
 // workspace for a plan no call can run).
 static int check_flags(const nrf_handle_s* h, uint32_t flags) {
-  const uint32_t known = NRF_FLAG_TRAIN | NRF_FLAG_NO_WARP | NRF_FLAG_BF16 | NRF_FLAG_WARP_JACOBIAN | NRF_FLAG_WARP_F32 | NRF_FLAG_BF16X3;
+  const uint32_t known = NRF_FLAG_TRAIN | NRF_FLAG_NO_WARP | NRF_FLAG_BF16 | NRF_FLAG_WARP_JACOBIAN | NRF_FLAG_WARP_F32 | NRF_FLAG_BF16X3 |
+                         NRF_FLAG_RAY_GRADS;
   if (flags & ~known) return fail(NRF_E_UNSUPPORTED, "unknown bits in flags");
+  if ((flags & NRF_FLAG_RAY_GRADS) && (flags & (NRF_FLAG_BF16 | NRF_FLAG_BF16X3)))
+    return fail(NRF_E_UNSUPPORTED, "NRF_FLAG_RAY_GRADS is built for the float32 mode: not with NRF_FLAG_BF16 / NRF_FLAG_BF16X3");
+  if ((flags & NRF_FLAG_RAY_GRADS) && !(flags & NRF_FLAG_TRAIN))
+    return fail(NRF_E_UNSUPPORTED, "NRF_FLAG_RAY_GRADS keeps what nrf_backward_rays reads of a stashed forward: only together with NRF_FLAG_TRAIN");
   if ((flags & NRF_FLAG_BF16X3) && (flags & (NRF_FLAG_TRAIN | NRF_FLAG_BF16)))
     return fail(NRF_E_UNSUPPORTED, "NRF_FLAG_BF16X3 is an inference mode of its own: not with NRF_FLAG_TRAIN (the training chains stash float32 or "
                                    "bfloat16 activations) and not with NRF_FLAG_BF16");
@@ -180,10 +185,17 @@ int nrf_forward(nrf_handle h, const float* params, const nrf_rays* rays, const n
 
 // nrf_backward / nrf_backward_ex: the state checks, the zero stand-in of a missing d_rgb, the reverse pass
 static int backward_checked(nrf_handle h, const float* params, const nrf_rays* rays, nrf_output_grads g, float* grad_params,
-                            void* workspace, size_t workspace_bytes, void* stream) {
+                            void* workspace, size_t workspace_bytes, void* stream, const nrf_ray_grads* rg = nullptr) {
   if (!h || !params || !rays || !grad_params || !workspace) return fail(NRF_E_NULL, "null argument");
   if (h->stashed_ws != workspace || h->stashed_B != rays->num_rays)
-    return fail(NRF_E_STATE, "nrf_backward needs a preceding nrf_forward(NRF_FLAG_TRAIN) on this workspace");
+    return fail(NRF_E_STATE, rg ? "nrf_backward_rays needs a preceding nrf_forward(NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS) on this workspace"
+                                : "nrf_backward needs a preceding nrf_forward(NRF_FLAG_TRAIN) on this workspace");
+  if (rg && !h->stashed_modes.ray_grads)
+    return fail(NRF_E_STATE, "nrf_backward_rays: the stashed nrf_forward ran without NRF_FLAG_RAY_GRADS (nothing of the rays' "
+                             "gradient was kept); run nrf_forward(NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS)");
+  if (rg && rg->d_viewdirs && (!h->d.use_viewdirs || !rays->viewdirs || h->V > 64))
+    return fail(NRF_E_UNSUPPORTED, "nrf_ray_grads.d_viewdirs needs a model with use_viewdirs (at most 64 encoded columns) and rays->viewdirs "
+                                   "(without them the condition does not read a view direction of its own)");
   if (h->stashed_plan != h->plan.serial)   // another call re-planned the handle (other num_rays / flags) since the stashed forward
     return fail(NRF_E_STATE, "nrf_backward: the workspace layout changed since the stashed nrf_forward (an intervening call with "
                              "another num_rays / flags); run nrf_forward(NRF_FLAG_TRAIN) again");
@@ -201,7 +213,7 @@ static int backward_checked(nrf_handle h, const float* params, const nrf_rays* r
   }
   if (!g.coarse.d_rgb) g.coarse.d_rgb = zero;
   if (!g.fine.d_rgb) g.fine.d_rgb = zero;
-  return backward_impl(h, params, rays, &g, nullptr, grad_params, nullptr, ws, st);
+  return backward_impl(h, params, rays, &g, nullptr, grad_params, nullptr, ws, st, nullptr, nullptr, nullptr, nullptr, false, rg);
 }
 
 int nrf_backward(nrf_handle h, const float* params, const nrf_rays* rays, const float* d_rgb_coarse,
@@ -215,6 +227,13 @@ int nrf_backward_ex(nrf_handle h, const float* params, const nrf_rays* rays, con
                     void* workspace, size_t workspace_bytes, void* stream) {
   if (!g) return fail(NRF_E_NULL, "nrf_output_grads is null (pass a zeroed struct for a zero gradient)");
   return backward_checked(h, params, rays, *g, grad_params, workspace, workspace_bytes, stream);
+}
+
+int nrf_backward_rays(nrf_handle h, const float* params, const nrf_rays* rays, const nrf_output_grads* g, const nrf_ray_grads* rg,
+                      float* grad_params, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!g) return fail(NRF_E_NULL, "nrf_output_grads is null (pass a zeroed struct for a zero gradient)");
+  if (!rg) return fail(NRF_E_NULL, "nrf_ray_grads is null (pass a struct of NULL pointers for no ray gradient)");
+  return backward_checked(h, params, rays, *g, grad_params, workspace, workspace_bytes, stream, rg);
 }
 
 int nrf_train_step_loss_grad(nrf_handle h, const float* params, const nrf_rays* rays, const float* target_rgb,
@@ -231,6 +250,8 @@ int nrf_train_step_loss_grad_ex(nrf_handle h, const float* params, const nrf_ray
                                 const nrf_elastic* el, const nrf_warp_reg* wr, uint32_t flags, float* grad_params, float* stats,
                                 void* workspace, size_t workspace_bytes, void* stream) {
   if (!h || !target_rgb || !grad_params) return fail(NRF_E_NULL, "null argument");
+  if (flags & NRF_FLAG_RAY_GRADS)
+    return fail(NRF_E_UNSUPPORTED, "NRF_FLAG_RAY_GRADS: the fused train step has a fixed loss and no ray gradient; use nrf_forward + nrf_backward_rays");
   if (flags & ~(uint32_t)(NRF_FLAG_BF16 | NRF_FLAG_WARP_F32)) return fail(NRF_E_UNSUPPORTED, "nrf_train_step_loss_grad_ex flags: 0, NRF_FLAG_BF16 [| NRF_FLAG_WARP_F32]");
   CK(check_flags(h, NRF_FLAG_TRAIN | flags));   // the same word nrf_workspace_bytes_ex validated (WARP_F32 without BF16 is refused here too)
   int bgN = 0;
@@ -265,6 +286,8 @@ int nrf_workspace_bytes_ex(nrf_handle h, int32_t num_rays, uint32_t flags, int32
   if ((num_background_points > 0 || use_elastic_loss) && !h->warp)
     return fail(NRF_E_UNSUPPORTED, "the background / elastic regularisers need the warp field");
   CK(check_flags(h, flags));
+  if ((flags & NRF_FLAG_RAY_GRADS) && (num_background_points > 0 || use_elastic_loss))
+    return fail(NRF_E_UNSUPPORTED, "NRF_FLAG_RAY_GRADS: the regularisers belong to the fused train step, which has no ray gradient");
   query_device(h);
   const bool tr = flags & NRF_FLAG_TRAIN;
   build_plan(h, num_rays, flags, tr ? num_background_points : 0, tr && use_elastic_loss ? 1 : 0);

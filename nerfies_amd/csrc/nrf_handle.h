@@ -63,6 +63,10 @@ struct LevelWs {   // float offsets from the workspace base, per level (0 = coar
   size_t wpoints, points_raw, d_points;
   size_t el_dw4, el_dv4;   // coarse level: dL/d(w, v) of the elastic regulariser through exp_se3's second derivatives
   size_t w_st_win, w_st_h, w_st_wv, w_bits, w_dy, w_dw4, w_dv4, w_small_part;
+  // NRF_FLAG_RAY_GRADS (taken behind everything else; not in the plan digest): the warp Jacobian [rows][9] of this level's samples, the
+  // per-ray sum of sigma dL/dsigma [B], and -- a model without a warp field -- the weight image the reverse chain reads instead of
+  // wpk: the transposed layers at their PackOffsets plus W0^T / the skip rows^T (what a warp model packs into wpk itself)
+  size_t rg_jac = 0, rg_sdsig = 0, rg_wpkT = 0;
 };
 
 // What a workspace plan is built for: a handle re-plans (and re-uploads the tables) when any of it changes
@@ -120,6 +124,7 @@ struct WsPlan {
   // sums exactly that many, so launch, zero list and table all read these (functions of ntiles, bwd32, bgN, CUs: not in the digest)
   int grid_mlp_bwd = 0;  // NeRF chains, tiles of all levels: small_part[grid_mlp_bwd][SMALL_PART] per level
   int grid_warp_bwd = 0; // SE3 chain, coarse + fine + background tiles: w_small_part[grid_warp_bwd][WARP_SMALL_PART]
+  int rg_L0T = 0, rg_L4bT = 0;   // NRF_FLAG_RAY_GRADS plan of a model without a warp field: PackOffsets::bwd_L0T / bwd_L4bT inside rg_wpkT
   int tg_tiles_per = 0;  // primal tiles one tangent pass covers (elastic: coarse level; Jacobian output: the larger level)
   size_t total_floats;
   std::vector<PackDesc> pack;
@@ -134,6 +139,7 @@ struct Modes {
   bool train = false, warp_on = false;   // NRF_FLAG_TRAIN (keep the stashes); the SE3 field runs (models.py:296 use_warp argument)
   bool bf16 = false, x3 = false;         // NeRF chains on bf16 operands (mlp_bf16.hip) / in split-bf16 arithmetic (mlp_bf16x3.hip)
   bool jac = false;                      // NRF_FLAG_WARP_JACOBIAN: the tangent pass of an inference call
+  bool ray_grads = false;                // NRF_FLAG_RAY_GRADS: the stash holds what nrf_backward_rays reads
   WarpTrunk trunk = WarpTrunk::F32;
 };
 
@@ -263,7 +269,7 @@ int forward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, cons
 int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, const nrf_output_grads* og, const float* target,
                   float* grad_x, float* stats, float* ws, hipStream_t stream, const nrf_background* bg = nullptr,
                   const nrf_step_scalars* scalars = nullptr, const nrf_elastic* el = nullptr, const nrf_warp_reg* wr = nullptr,
-                  bool bg_forward_done = false);
+                  bool bg_forward_done = false, const nrf_ray_grads* rg = nullptr);
 
 }  // namespace api
 }  // namespace nrf

@@ -484,10 +484,33 @@ struct CompositeBwdArgs {
   const float* d_depth;   // [B]
   const float* d_acc;     // [B]
   const float* d_w;       // [B][S]
+  // ray gradients (nrf_backward_rays): [B] sum_i sigma_i dL/dsigma_i of the ray, the |d| term of the distances; nullptr: not formed
+  float* sdsig_ray;
 };
 struct CompositeBwdArgs2 { CompositeBwdArgs a[2]; };
 // a1: second level or nullptr.  The kernel that reads d_depth / d_acc / d_w is launched only when one of them is set at either level
 void launch_composite_bwd(const CompositeBwdArgs& a0, const CompositeBwdArgs* a1, hipStream_t stream);
+// Gradients w.r.t. the rays (nrf_backward_rays), both levels in one launch, one wave per ray, lanes over samples, no atomics:
+//   d_origins[r] = sum_lv sum_s J_s^T g_s,  d_directions[r] = sum_lv sum_s z_s J_s^T g_s + d / |d|^2 sum_lv sdsig_lv[r],
+//   d_viewdirs[r] = posenc^T(sum_lv W_rgbh,lv[256 : 256 + V, :] dray_lv[r])
+// with g_s = d_points (dL/d warped point) and J_s = jac (the warp Jacobian, row-major d x'_i / d x_j; nullptr: the identity).
+struct RayGradArgs {
+  const float* d_points[2];   // [rows][3]
+  const float* z[2];          // [B][S]
+  const float* jac[2];        // [rows][9] or nullptr
+  const float* dray[2];       // [B][RGB_W] per-ray adjoint of the rgb layer's condition term
+  const float* sdsig[2];      // [B] (composite_bwd_kernel) or nullptr
+  long long rgbh_k[2];        // the rgb layer's kernel [256 + R][RGB_W] in params
+  int S[2];
+  const float* params;
+  const float* dirs;          // [B][3]
+  const float* viewdirs;      // [B][3]
+  int B, nlevels, V, Fv;      // V = 3 + 6 Fv viewdir columns of the condition
+  float* d_origins;           // [B][3], each may be nullptr: that part is skipped
+  float* d_directions;
+  float* d_viewdirs;
+};
+void launch_ray_grad(const RayGradArgs& a, hipStream_t stream);
 // d_points[rows][3] += d_warped[rows][3]: the caller's cotangent of the warped points (nrf_backward_ex), ahead of the SE3 dgrad
 void launch_add_point_cotangent(const float* d_warped, int rows, float* d_points, hipStream_t stream);
 // use_alpha_condition: gradient of the appearance-code rows of the alpha head and of the codes through it

@@ -216,6 +216,7 @@ uint32_t plan_flags(uint32_t flags) {
   uint32_t f = flags & (NRF_FLAG_TRAIN | NRF_FLAG_WARP_JACOBIAN);
   if ((flags & NRF_FLAG_TRAIN) && (flags & NRF_FLAG_BF16)) f |= NRF_FLAG_BF16 | (flags & NRF_FLAG_WARP_F32);
   if (!(flags & NRF_FLAG_TRAIN) && (flags & NRF_FLAG_BF16X3)) f |= NRF_FLAG_BF16X3;   // its own (tripled) weight streams
+  if ((flags & NRF_FLAG_TRAIN) && (flags & NRF_FLAG_RAY_GRADS)) f |= NRF_FLAG_RAY_GRADS;   // float32 training only (check_flags)
   return f;
 }
 
@@ -446,6 +447,8 @@ struct Planner {
   const bool jac;      // tangent pass in an inference plan
   const bool bfw;      // ... and so does the SE3 trunk (warp_bf16.hip)
   const bool wstash;   // the fp32 warp kernels keep their input / sign-bit stash
+  const bool rg;       // NRF_FLAG_RAY_GRADS: what nrf_backward_rays reads stays alive
+  std::vector<size_t> rg_packT[2];      // ... a model without a warp field: the level's pack descriptors that write into rg_wpkT
   const int G;
   std::vector<GroupSpec> specs;         // fp32 wgrad groups
   std::vector<BSpec> bspecs;            // bf16 wgrad groups
@@ -456,7 +459,8 @@ struct Planner {
   Planner(nrf_handle h_, uint32_t flags)
       : h(h_), p(h_->plan), d(h_->d), train(flags & NRF_FLAG_TRAIN), bft(train && (flags & NRF_FLAG_BF16)),
         x3(!train && (flags & NRF_FLAG_BF16X3)), jac((flags & NRF_FLAG_WARP_JACOBIAN) && h_->warp),
-        bfw(bft && h_->warp && !(flags & NRF_FLAG_WARP_F32)), wstash((train && !bfw) || jac), G(h_->num_cus) {}
+        bfw(bft && h_->warp && !(flags & NRF_FLAG_WARP_F32)), wstash((train && !bfw) || jac), rg(train && (flags & NRF_FLAG_RAY_GRADS)),
+        G(h_->num_cus) {}
   size_t take(size_t n) { size_t r = o; o = align_up(o + n, ALIGN_F); return r; }
   void add_reduce(const ReduceDesc& r) { by_pass[r.accumulate].push_back(r); }
   // fp32 groups: leaf [kvalid][cols] <- X^T dY; the narrow heads: leaf [kvalid][vec] <- X^T v
@@ -482,7 +486,9 @@ struct Planner {
   void cut_wgrad();
   void weight_streams();
   void buffers();
+  void take_warp_stash(LevelWs& L, size_t nt);
   void alloc_warp(LevelWs& L, size_t nt);
+  void ray_grad_buffers();
   void pack_descs();
   void fp32_groups();
   void bf16_groups();
@@ -506,11 +512,12 @@ void Planner::shapes() {
   // launches); the 32-row reverse kernel has no d-points path: models with a warp field keep the 64-row one
   int nt_mlp = 0;
   for (int q = 0; q < h->nlevels; ++q) nt_mlp += p.ntiles[q];
-  p.bwd32 = train && !bft && !h->warp && chain32_for(h, nt_mlp, true);   // (false for an rgb branch deeper than one layer)
+  // ... and so does a ray-gradient plan (its d-points buffer is what nrf_backward_rays reduces)
+  p.bwd32 = train && !bft && !h->warp && !rg && chain32_for(h, nt_mlp, true);   // (false for an rgb branch deeper than one layer)
   // ONE dgrad launch over the tiles of all levels: two workgroups per CU on 64-row tiles, four on 32-row half tiles
   p.grid_mlp_bwd = p.bwd32 ? tile_grid(2 * nt_mlp, 4, G) : tile_grid(nt_mlp, 2, G);
   p.grid_warp_bwd = tile_grid(nt_mlp + p.ntiles[BG], warp_grid_mul(), G);   // ONE SE3 dgrad launch: + the background tiles (0 without that batch)
-  p.tg_tiles_per = jac ? p.ntiles[h->nlevels - 1] : k.elastic ? p.ntiles[0] : 0;   // Jacobian output: levels run one after the other
+  p.tg_tiles_per = jac || (rg && h->warp) ? p.ntiles[h->nlevels - 1] : k.elastic ? p.ntiles[0] : 0;   // Jacobian output / ray gradients: levels run one after the other
   p.ntiles[TG] = 3 * p.tg_tiles_per;
   p.rows[TG] = p.ntiles[TG] * TILE_ROWS;
 }
@@ -717,13 +724,18 @@ void Planner::weight_streams() {
   p.bf_desc = take(p.bfpack.size() * sizeof(RcPackDesc) / 4 + 16);
 }
 
+// the fp32 warp kernels' input / activation / (w, v) stash of nt tiles (a tangent pass keeps these three and no sign bits)
+void Planner::take_warp_stash(LevelWs& L, size_t nt) {
+  L.w_st_win = take(nt * ((h->PKw + 31) / 32 * 32) * TILE_ROWS);
+  L.w_st_h = take(nt * FRAG_TILE_128 * WARP_DEPTH);
+  L.w_st_wv = take(nt * TILE_ROWS * 8);
+}
+
 void Planner::alloc_warp(LevelWs& L, size_t nt) {
   L.wpoints = take(nt * TILE_ROWS * 3);
   L.points_raw = take(nt * TILE_ROWS * 3);
   if (wstash) {
-    L.w_st_win = take(nt * ((h->PKw + 31) / 32 * 32) * TILE_ROWS);
-    L.w_st_h = take(nt * FRAG_TILE_128 * WARP_DEPTH);
-    L.w_st_wv = take(nt * TILE_ROWS * 8);
+    take_warp_stash(L, nt);
     L.w_bits = take(nt * 4 * 64 * WARP_DEPTH);
   }
   if (train && !bfw) {
@@ -832,18 +844,48 @@ void Planner::buffers() {
   p.timeline = take(2 * TIMELINE_LEVEL_F);
 }
 
+// ---- NRF_FLAG_RAY_GRADS: everything the flag adds, behind every offset a plan without it has ----
+void Planner::ray_grad_buffers() {
+  if (!rg) return;
+  for (int lv = 0; lv < h->nlevels; ++lv) {
+    LevelWs& L = p.L[lv];
+    const size_t nt = p.ntiles[lv];
+    L.rg_sdsig = take(p.key.B);
+    if (h->warp) {
+      L.rg_jac = take(nt * TILE_ROWS * 9);
+    } else {
+      L.d_points = take(nt * TILE_ROWS * 3);
+      // a whole second image: the reverse chain takes ONE wpk base and PackOffsets relative to it, so the transposed layers keep
+      // their slots (the forward layers' slots stay unused), W0^T / skip rows^T and the prefetch slack behind them
+      L.rg_wpkT = take((size_t)p.rg_L4bT + 256 * 64 + 4096);
+      for (size_t i : rg_packT[lv]) p.pack[i].dst_off += (int64_t)L.rg_wpkT;   // built relative to it by pack_descs
+    }
+  }
+  if (!h->warp) return;
+  // the tangent pass of one level at a time (as the inference Jacobian plan): its input / activation / (w, v) stash
+  LevelWs& T = p.L[TG];
+  const size_t nt = p.ntiles[TG];
+  T.wpoints = take(nt * TILE_ROWS * 3);
+  take_warp_stash(T, nt);
+}
+
 // ---- pack descriptors (both levels, forward and transposed streams); a bf16 TRAINING plan reads only the bf16 images of the
 //      NeRF MLPs (bfpack), so their fp32 fragment images are not rebuilt every step ----
 void Planner::pack_descs() {
   for (int lv = 0; lv < (bft ? 0 : h->nlevels); ++lv) {
     const MlpParamOffsets& po = h->po[lv];
     const int64_t base = (int64_t)p.L[lv].wpk;
+    // ray gradients without a warp field: the reverse chain reads its transposed images (and the two d-posenc ones) from rg_wpkT,
+    // taken behind everything else: those descriptors are built relative to it here and moved onto it by ray_grad_buffers
+    const bool rgT = rg && !h->warp;
+    if (rgT) { p.rg_L0T = h->pk.total; p.rg_L4bT = p.rg_L0T + 256 * 64; }   // behind the level's own images and their prefetch slack
     const PackOffsets& pk = h->pk;
     auto add = [&](int64_t src, int dst, int ld, int row0, int kvalid, int K, int ncb, int tr, int nwaves = 4,
                    int nvalid = 1 << 30) {
       PackDesc q;
-      q.src_off = src; q.dst_off = base + dst; q.src_ld = ld; q.src_row0 = row0; q.kvalid = kvalid; q.K = K; q.ncb = ncb;
+      q.src_off = src; q.dst_off = (tr && rgT ? 0 : base) + dst; q.src_ld = ld; q.src_row0 = row0; q.kvalid = kvalid; q.K = K; q.ncb = ncb;
       q.transposed = tr; q.nwaves = nwaves; q.nvalid = nvalid;
+      if (tr && rgT) rg_packT[lv].push_back(p.pack.size());
       p.pack.push_back(q);
     };
     add(po.trunk_k[0], pk.fwd_L[0], 256, 0, h->P, h->PK, 2, 0);
@@ -861,6 +903,9 @@ void Planner::pack_descs() {
     if (h->warp) {   // d posenc streams: B[k][n] = W[row0 + n][k], n < P, one 64-column group
       add(po.trunk_k[0], pk.bwd_L0T, 256, 0, 256, 256, 2, 1, 1, h->P);
       add(po.trunk_k[d.nerf_skip_layer], pk.bwd_L4bT, 256, 256, 256, 256, 2, 1, 1, h->P);
+    } else if (rgT) {
+      add(po.trunk_k[0], p.rg_L0T, 256, 0, 256, 256, 2, 1, 1, h->P);
+      add(po.trunk_k[d.nerf_skip_layer], p.rg_L4bT, 256, 256, 256, 256, 2, 1, 1, h->P);
     }
   }
   // fp32 fragment images of the SE3 trunk (a bf16-trunk training plan reads only its bf16 streams)
@@ -1036,6 +1081,8 @@ void build_plan(nrf_handle h, int B, uint32_t flags, int bgN, int elastic) {
   }
   s.chain_reduces();
   s.tables();
+  s.ray_grad_buffers();   // the flag's buffers lie behind everything a plan without it has
+
   h->plan.total_floats = s.o;
 }
 

@@ -79,6 +79,7 @@ Modes forward_modes(const nrf_handle_s* h, uint32_t flags) {
   m.warp_on = h->warp && !(flags & NRF_FLAG_NO_WARP);
   m.bf16 = flags & NRF_FLAG_BF16; m.x3 = flags & NRF_FLAG_BF16X3;   // x3: inference only (check_flags)
   m.jac = flags & NRF_FLAG_WARP_JACOBIAN;
+  m.ray_grads = m.train && (flags & NRF_FLAG_RAY_GRADS);
   // the SE3 trunk follows the MLPs into bf16 / split-bf16 unless the caller opts out (NRF_FLAG_WARP_F32) or asks for the Jacobian
   // output (inference tangent pass: fp32 kernels, their input stash); a training plan has decided already (its stash layout depends on it)
   const bool follows = m.train ? h->plan.bfw : !(flags & NRF_FLAG_WARP_F32) && !m.jac;
@@ -265,10 +266,13 @@ struct Forward : Run {
   }
   // forward-mode Jacobian of the warp: on the coarse samples for the elastic regulariser (models.py:345), per level
   // as an output (return_warp_jacobian, models.py:345-346, 367-368)
+  // ... and per level into the workspace for nrf_backward_rays (NRF_FLAG_RAY_GRADS: the tangent pass runs in the forward, right
+  // behind the primal pass whose (alpha, codes) it shares; the levels take turns on the one tangent stash)
   void jacobian(int lv) {
     float* jout = !out ? nullptr : lv == 0 ? out->coarse.warp_jacobian : out->fine.warp_jacobian;
-    if ((lv == 0 && m.train && p.key.elastic) || (m.jac && jout)) tangent_fwd(lv);
-    if (!m.jac || !jout) return;
+    if (m.ray_grads) jout = ws + p.L[lv].rg_jac;
+    if ((lv == 0 && m.train && p.key.elastic) || (m.jac && jout) || m.ray_grads) tangent_fwd(lv);
+    if (!(m.jac || m.ray_grads) || !jout) return;
     JacobianArgs ja;
     memset(&ja, 0, sizeof(ja));   // x_rows = nullptr: the points come from the fp32 input stash
     ja.prim_win = ws + p.L[lv].w_st_win; ja.prim_wv = f4(p.L[lv].w_st_wv); ja.tan_wv = f4(p.L[TG].w_st_wv); ja.out = jout;
@@ -347,6 +351,7 @@ struct Forward : Run {
 
 struct Backward : Run {
   const nrf_elastic* el;  const nrf_warp_reg* wr;  const bool el_on, wr_on;
+  const nrf_ray_grads* rg = nullptr;   // nrf_backward_rays: the ray gradients to write (the stash was kept under NRF_FLAG_RAY_GRADS)
   const nrf_output_grads* og;   // the caller's cotangents (nrf_backward[_ex]) or nullptr (fused step: the MSE loss against `target`)
   float* grad = nullptr;   // INTERNAL layout, as params
   double mlp_rows = 0;     // samples of all levels
@@ -384,6 +389,7 @@ struct Backward : Run {
       c.loss_scale = 2.0f / (3.0f * (float)B);   // d/d rgb of mean over (B,3) (training.py:172)
       c.d_raw4 = f4(L.d_raw4); c.rows_pad = rows_pad(lv);
       c.mse_ray = ws + p.mse + (size_t)lv * B; c.dsig_ray = h->A > 0 ? ws + L.dsig_ray : nullptr;
+      if (rg && rg->d_directions) c.sdsig_ray = ws + L.rg_sdsig;
     }
     pf.begin("composite_bwd", 0, stream);
     launch_composite_bwd(ca[0], h->nlevels > 1 ? &ca[1] : nullptr, stream);
@@ -399,6 +405,10 @@ struct Backward : Run {
     a.d_raw4 = f4(L.d_raw4); a.bits_trunk = u32(L.bits_trunk); a.bits_rgbh = u32(L.bits_rgbh);
     a.dy_trunk = ws + L.dy_trunk; a.dy_bn = ws + L.dy_bn; a.dy_rgbh = ws + L.dy_rgbh; a.dray = ws + L.dray; a.small_part = ws + L.small_part;
     if (m.warp_on) { a.d_points = ws + L.d_points; a.st_pe = ws + L.st_pe; }
+    else if (rg && (rg->d_origins || rg->d_directions)) {   // no warp field: d points only for the ray stage, W^T images of their own
+      a.d_points = ws + L.d_points; a.st_pe = ws + L.st_pe;
+    }
+    if (m.ray_grads && !h->warp) { a.wpk = ws + L.rg_wpkT; a.pk.bwd_L0T = p.rg_L0T; a.pk.bwd_L4bT = p.rg_L4bT; }
     a.F = d.num_nerf_point_freqs; a.P = h->P; a.PK = h->PK; a.skip = d.nerf_skip_layer;
     a.alpha_on_bn = h->A > 0 ? 1 : 0;
     a.nx = d.nerf_rgb_branch_depth - 1; a.bits_rgbx = u32(L.bits_rgbx); a.dy_rgbx = ws + L.dy_rgbx;
@@ -406,7 +416,8 @@ struct Backward : Run {
   }
   // ONE NeRF-MLP dgrad launch over the tiles of both levels, on the grid the plan's reduce table was built for
   void mlp_dgrad() {
-    const double flops = dgrad_flops_row(h, m.warp_on) * mlp_rows;
+    // the d-points section runs whenever chain_bwd_args hands d_points over
+    const double flops = dgrad_flops_row(h, m.warp_on || (rg && (rg->d_origins || rg->d_directions))) * mlp_rows;
     if (!m.bf16) {
       ChainBwdArgs ca[2];
       for (int lv = 0; lv < h->nlevels; ++lv) ca[lv] = chain_bwd_args(lv);
@@ -471,6 +482,22 @@ struct Backward : Run {
     if (bg_on)
       launch_background_loss(bg_points(), ws + p.L[BG].wpoints, p.key.bgN, rows_pad(BG), bg->loss_alpha, bg->loss_scale,
                              bg->loss_weight, ws + p.L[BG].d_points, ws + p.bg_loss, stream);
+  }
+  // nrf_backward_rays: d_points (+ the caller's warped-point cotangent) -> the three per-ray gradients, both levels in one launch
+  void ray_grads() {
+    RayGradArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int lv = 0; lv < h->nlevels; ++lv) {
+      const LevelWs& L = p.L[lv];
+      a.d_points[lv] = ws + L.d_points; a.z[lv] = ws + L.z; a.jac[lv] = m.warp_on ? ws + L.rg_jac : nullptr;
+      a.dray[lv] = ws + L.dray; a.sdsig[lv] = ws + L.rg_sdsig; a.rgbh_k[lv] = h->po[lv].rgbh_k; a.S[lv] = p.S[lv];
+    }
+    a.params = params; a.dirs = rays->directions; a.viewdirs = rays->viewdirs;
+    a.B = B; a.nlevels = h->nlevels; a.V = h->V; a.Fv = d.num_nerf_viewdir_freqs;
+    a.d_origins = rg->d_origins; a.d_directions = rg->d_directions; a.d_viewdirs = rg->d_viewdirs;
+    pf.begin("ray_grads", 0, stream);
+    launch_ray_grad(a, stream);
+    pf.end(stream);
   }
   // reverse arguments of the pass over level lv (BG: S = 1 from Planner::shapes), at the fp32 rows `x_rows` (bf16 trunk only)
   WarpBwdArgs warp_bwd_args(int lv, const float* x_rows) const {
@@ -617,12 +644,15 @@ int forward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, cons
 // point gradients, ONE SE3 dgrad launch (coarse + fine + background tiles), the tangent pass, then wgrad / reduce.
 int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, const nrf_output_grads* og, const float* target,
                   float* grad_x, float* stats, float* ws, hipStream_t stream, const nrf_background* bg,
-                  const nrf_step_scalars* scalars, const nrf_elastic* el, const nrf_warp_reg* wr, bool bg_forward_done) {
+                  const nrf_step_scalars* scalars, const nrf_elastic* el, const nrf_warp_reg* wr, bool bg_forward_done,
+                  const nrf_ray_grads* rg) {
   Backward b(Run(h, h->stashed_modes, ws, stream, rays, scalars, bg), el, wr, og);
+  if (rg && (rg->d_origins || rg->d_directions || rg->d_viewdirs)) b.rg = rg;   // nothing asked for: the stage (and its inputs) are skipped
   // the gradient buffer is zero-filled and accumulated into with 16-byte accesses (zero_ranges_kernel, reduce passes)
   if ((reinterpret_cast<uintptr_t>(grad_x) & 15u) != 0) return fail(NRF_E_SHAPE, "grad_params must be 16-byte aligned");
   // p.bwd32 alone selects the 32-row reverse path (zeroed slices and launch); that kernel has no d-points output
   if (b.p.bwd32 && b.m.warp_on) return fail(NRF_E_STATE, "plan built for the 32-row reverse chain but the stashed forward ran the warp field");
+  if (b.p.bwd32 && b.rg) return fail(NRF_E_STATE, "plan built for the 32-row reverse chain but ray gradients (NRF_FLAG_RAY_GRADS) are asked for");
   // the background batch's warp forward ran inside the coarse warp launch of the fused train step
   if (b.bg_on && !bg_forward_done) return fail(NRF_E_STATE, "background regulariser without its forward pass");
   // narrower model: the stashed forward left the padded parameter image in the workspace; gradients are formed
@@ -633,6 +663,7 @@ int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, con
   b.composite_bwd(target);
   b.mlp_dgrad();
   b.point_regularisers();
+  if (b.rg) b.ray_grads();
   if (b.m.warp_on) b.warp_dgrad();
   b.cond_grads();
   if (b.m.warp_on && h->time_enc) {   // reverse of the TimeEncoder: d codes -> its six layers' weight gradients

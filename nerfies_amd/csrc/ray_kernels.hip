@@ -206,7 +206,10 @@ void launch_composite_fwd(const float4* out4, const float* z, const float* dirs,
 // EXTRA: cotangents of the other outputs of model_utils.py:116-126, all linear in the weights (depth = sum w_i z_i with z behind
 // stop_gradient, acc = sum w_i without the sample at infinity, weights_i = w_i), so they only add to g_i:
 //   g_i += d_depth z_i + d_acc [i < S-1 or not sample_at_inf] + d_w[i];   dL/dc_i stays w_i dL/drgb.
-template <bool EXTRA>
+// RAYS (nrf_backward_rays): also sdsig_ray[ray] = sum_i sigma_i dL/dsigma_i, the ray's gradient w.r.t. log |d| through
+// dist_i = (z_{i+1} - z_i) |d| (model_utils.py:104-110).  The last distance is the finite 1e10 |d|: sigma = 0 gives 0 * finite,
+// sigma > 0 a finite factor times exp(-sigma 1e10 |d|) = 0 -- no inf * 0.
+template <bool EXTRA, bool RAYS = false>
 __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompositeBwdArgs2 P) {
   const CompositeBwdArgs& A = P.a[blockIdx.y];   // blockIdx.y = level: both levels in one launch (kernarg-indexed, scalar loads)
   const float4* __restrict__ out4 = A.out4;
@@ -287,6 +290,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompositeBwdAr
   }
   float Qin = 0.f;   // Q of the last sample of the chunk being processed
   float dsig_acc = 0.f;
+  [[maybe_unused]] float sdsig_acc = 0.f;
 #pragma unroll
   for (int e = MAX_E - 1; e >= 0; --e) {
     if (e < E) {
@@ -315,12 +319,17 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompositeBwdAr
         o.w = sigma_act == 1 ? dsigma * (1.f - expf(-c.w)) : (c.w > 0.f ? dsigma : 0.f);   // softplus' / relu'
         d_raw4[(size_t)ray * S + s] = o;
         dsig_acc += o.w;
+        if constexpr (RAYS) sdsig_acc += c.w * dsigma;
       }
     }
   }
   if (dsig_ray) {   // use_alpha_condition: the alpha head's per-ray input sees the sum over the ray's samples
     dsig_acc = wave_sum(dsig_acc);
     if (lane == 0) dsig_ray[ray] = dsig_acc;
+  }
+  if constexpr (RAYS) {
+    sdsig_acc = wave_sum(sdsig_acc);
+    if (lane == 0 && A.sdsig_ray) A.sdsig_ray[ray] = sdsig_acc;
   }
 }
 
@@ -329,8 +338,101 @@ void launch_composite_bwd(const CompositeBwdArgs& a0, const CompositeBwdArgs* a1
   p.a[0] = a0; p.a[1] = a1 ? *a1 : a0;
   const bool extra = p.a[0].d_depth || p.a[0].d_acc || p.a[0].d_w || p.a[1].d_depth || p.a[1].d_acc || p.a[1].d_w;
   const dim3 grid((a0.B + 3) / 4, a1 ? 2 : 1);
-  if (extra) hipLaunchKernelGGL(composite_bwd_kernel<true>, grid, dim3(256), 0, stream, p);
+  const bool rays = p.a[0].sdsig_ray || p.a[1].sdsig_ray;   // the gated instantiations: the two above keep their code
+  if (rays && extra) hipLaunchKernelGGL((composite_bwd_kernel<true, true>), grid, dim3(256), 0, stream, p);
+  else if (rays) hipLaunchKernelGGL((composite_bwd_kernel<false, true>), grid, dim3(256), 0, stream, p);
+  else if (extra) hipLaunchKernelGGL(composite_bwd_kernel<true>, grid, dim3(256), 0, stream, p);
   else hipLaunchKernelGGL(composite_bwd_kernel<false>, grid, dim3(256), 0, stream, p);
+}
+
+// ------------------------------------------------------------------ ray gradients (nrf_backward_rays)
+// One wave per ray, lanes over the samples of each level in chunks of 64 (any S: the chunk loop has no upper bound), sums by the
+// xor butterfly of wave_sum: a fixed order, no atomics.  x_s = o + z_s d, x'_s = warp(x_s), so with g_s = dL/dx'_s and u_s = J_s^T g_s
+// d_origins = sum u_s and d_directions = sum z_s u_s; the compositing distances (z_{i+1} - z_i) |d| add d / |d|^2 * sum_i sigma_i dL/dsigma_i.
+// d_viewdirs: the wave forms the adjoint of every condition column c < V, sum_n W_rgbh[256 + c][n] dray[n] over both levels (lanes over
+// n), lane c carries it
+// through SinusoidalEncoder (identity columns, then per frequency sin(2^f v) and sin(2^f v + pi/2), as ray_prep_kernel forms them).
+__global__ __launch_bounds__(256) void ray_grad_kernel(const RayGradArgs A) {
+  const int lane = threadIdx.x & 63;
+  const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (ray >= A.B) return;
+  if (A.d_origins || A.d_directions) {
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f, e0 = 0.f, e1 = 0.f, e2 = 0.f, sd = 0.f;
+    for (int lv = 0; lv < A.nlevels; ++lv) {
+      const int S = A.S[lv];
+      const float* __restrict__ g = A.d_points[lv] + (size_t)ray * S * 3;
+      const float* __restrict__ zr = A.z[lv] + (size_t)ray * S;
+      const float* __restrict__ J = A.jac[lv] ? A.jac[lv] + (size_t)ray * S * 9 : nullptr;
+      for (int s = lane; s < S; s += 64) {
+        const float g0 = g[3 * s], g1 = g[3 * s + 1], g2 = g[3 * s + 2];
+        float u0 = g0, u1 = g1, u2 = g2;
+        if (J) {   // u = J^T g, J row-major d x'_i / d x_j
+          const float* j = J + 9 * (size_t)s;
+          u0 = j[0] * g0 + j[3] * g1 + j[6] * g2;
+          u1 = j[1] * g0 + j[4] * g1 + j[7] * g2;
+          u2 = j[2] * g0 + j[5] * g1 + j[8] * g2;
+        }
+        const float zi = zr[s];
+        o0 += u0; o1 += u1; o2 += u2;
+        e0 += zi * u0; e1 += zi * u1; e2 += zi * u2;
+      }
+      if (A.d_directions && A.sdsig[lv]) sd += A.sdsig[lv][ray];
+    }
+    o0 = wave_sum(o0); o1 = wave_sum(o1); o2 = wave_sum(o2);
+    e0 = wave_sum(e0); e1 = wave_sum(e1); e2 = wave_sum(e2);
+    if (lane == 0) {
+      if (A.d_origins) { A.d_origins[3 * ray] = o0; A.d_origins[3 * ray + 1] = o1; A.d_origins[3 * ray + 2] = o2; }
+      if (A.d_directions) {
+        const float dx = A.dirs[3 * ray], dy = A.dirs[3 * ray + 1], dz = A.dirs[3 * ray + 2];
+        const float n2 = dx * dx + dy * dy + dz * dz;
+        const float k = n2 > 0.f ? sd / n2 : 0.f;   // (d / |d|) (1 / |d|) sum sigma dL/dsigma
+        A.d_directions[3 * ray] = e0 + k * dx; A.d_directions[3 * ray + 1] = e1 + k * dy; A.d_directions[3 * ray + 2] = e2 + k * dz;
+      }
+    }
+  }
+  if (A.d_viewdirs) {
+    // lanes over the RGB_W = 2 x 64 adjoints of each level (coalesced rows of W and of dray), one wave_sum per condition column;
+    // lane c keeps column c's sum
+    float d0[2] = {0.f, 0.f}, d1[2] = {0.f, 0.f};
+#pragma unroll
+    for (int lv = 0; lv < 2; ++lv)
+      if (lv < A.nlevels) {
+        const float* __restrict__ dr = A.dray[lv] + (size_t)ray * RGB_W;
+        d0[lv] = dr[lane]; d1[lv] = dr[lane + 64];
+      }
+    float dc = 0.f;
+    for (int c = 0; c < A.V; ++c) {
+      float a = 0.f;
+#pragma unroll
+      for (int lv = 0; lv < 2; ++lv)
+        if (lv < A.nlevels) {
+          const float* __restrict__ w = A.params + A.rgbh_k[lv] + (size_t)(TRUNK_W + c) * RGB_W;
+          a = fmaf(w[lane + 64], d1[lv], fmaf(w[lane], d0[lv], a));
+        }
+      a = wave_sum(a);
+      if (lane == c) dc = a;
+    }
+    int comp = 0;
+    float coef = 0.f;
+    if (lane < A.V) {
+      if (lane < 3) { comp = lane; coef = 1.f; }
+      else {
+        const int q = lane - 3, f = q / 6, rem = q - 6 * f, is_cos = rem / 3;
+        comp = rem - 3 * is_cos;
+        const float sc = (float)(1 << f);
+        float a = __fmul_rn(A.viewdirs[3 * ray + comp], sc);
+        if (is_cos) a = __fadd_rn(a, 1.57079632679489661923f);
+        coef = sc * cosf(a);
+      }
+    }
+    const float t = dc * coef;
+    const float v0 = wave_sum(comp == 0 ? t : 0.f), v1 = wave_sum(comp == 1 ? t : 0.f), v2 = wave_sum(comp == 2 ? t : 0.f);
+    if (lane == 0) { A.d_viewdirs[3 * ray] = v0; A.d_viewdirs[3 * ray + 1] = v1; A.d_viewdirs[3 * ray + 2] = v2; }
+  }
+}
+
+void launch_ray_grad(const RayGradArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(ray_grad_kernel, dim3((a.B + 3) / 4), dim3(256), 0, stream, a);
 }
 
 // The caller's cotangent of the warped points (nrf_backward_ex) joins dL/dx' where the regularisers' do: added into d_points

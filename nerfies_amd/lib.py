@@ -12,6 +12,7 @@ NRF_FLAG_BF16 = 4
 NRF_FLAG_WARP_JACOBIAN = 8
 NRF_FLAG_WARP_F32 = 16
 NRF_FLAG_BF16X3 = 32
+NRF_FLAG_RAY_GRADS = 64
 NRF_NUM_STATS = 16
 ACT = {'relu': 0, 'softplus': 1}
 WARP_FIELD = {'se3': 0, 'translation': 1}
@@ -91,6 +92,11 @@ class OutputGrads(C.Structure):
   _fields_ = [('coarse', LevelGrads), ('fine', LevelGrads)]
 
 
+class RayGrads(C.Structure):
+  """nrf_ray_grads: the gradients w.r.t. the rays (nrf_backward_rays), each (B,3); a NULL pointer skips that part."""
+  _fields_ = [('d_origins', C.c_void_p), ('d_directions', C.c_void_p), ('d_viewdirs', C.c_void_p)]
+
+
 class Background(C.Structure):
   _fields_ = [('num_points', C.c_int32), ('points', C.c_void_p), ('warp_ids', C.c_void_p), ('loss_weight', C.c_float),
               ('loss_alpha', C.c_float), ('loss_scale', C.c_float), ('id_choices', C.c_void_p), ('num_choices', C.c_int32),
@@ -129,6 +135,7 @@ EXPORTS = [
     'nrf_warp_points_workspace_bytes', 'nrf_warp_points',
     'nrf_camera_pixels_to_rays', 'nrf_camera_pixels_to_points', 'nrf_camera_project',
     'nrf_dynamic_scalars_write', 'nrf_adam_step_dynamic', 'nrf_set_option', 'nrf_debug_plan_digest', 'nrf_backward_ex',
+    'nrf_backward_rays',
 ]
 
 _lib = None
@@ -161,6 +168,7 @@ def load_library(path=None):
                       C.c_size_t, vp],
       'nrf_backward': [vp, vp, C.POINTER(Rays), vp, vp, vp, vp, C.c_size_t, vp],
       'nrf_backward_ex': [vp, vp, C.POINTER(Rays), C.POINTER(OutputGrads), vp, vp, C.c_size_t, vp],
+      'nrf_backward_rays': [vp, vp, C.POINTER(Rays), C.POINTER(OutputGrads), C.POINTER(RayGrads), vp, vp, C.c_size_t, vp],
       'nrf_train_step_loss_grad': [vp, vp, C.POINTER(Rays), vp, C.POINTER(StepScalars), C.POINTER(Rand), vp, vp, vp,
                                    C.c_size_t, vp],
       'nrf_adam_step': [vp, vp, vp, vp, i64, f64, f64, f64, f64, i64, f64, vp],

@@ -286,14 +286,17 @@ class NerfModel:
     L.check(self.lib.nrf_workspace_bytes(self.handle, 1, flags, C.byref(nbytes)), self.lib)
 
   def workspace(self, num_rays: int, train: bool, device, num_background_points: int = 0, elastic: bool = False,
-                jacobian: bool = False, bf16=False) -> torch.Tensor:
+                jacobian: bool = False, bf16=False, ray_grads: bool = False) -> torch.Tensor:
     # the TRAINING layout depends on it (bf16 stashes instead of the fp32 ones); so does an 'x3' inference plan (its weight streams)
     bf16 = 'x3' if bf16 in ('x3', 'x3mlp') else (bf16 if train else False)
     key = (int(num_rays), bool(train), str(device), int(num_background_points), bool(elastic), bool(jacobian), bf16)
+    if ray_grads:   # NRF_FLAG_RAY_GRADS: a larger layout of its own; every other key stays what it was
+      key += ('ray_grads',)
     ws = self._ws.get(key)
     if ws is None:
       nbytes = C.c_size_t(0)
-      flags = (L.NRF_FLAG_TRAIN if train else 0) | (L.NRF_FLAG_WARP_JACOBIAN if jacobian else 0) | self.bf16_flags(bf16)
+      flags = (L.NRF_FLAG_TRAIN if train else 0) | (L.NRF_FLAG_WARP_JACOBIAN if jacobian else 0) | self.bf16_flags(bf16) | \
+          (L.NRF_FLAG_RAY_GRADS if ray_grads else 0)
       L.check(self.lib.nrf_workspace_bytes_ex(self.handle, num_rays, flags,
                                               int(num_background_points), int(bool(elastic)), C.byref(nbytes)), self.lib)
       ws = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=device)
@@ -367,12 +370,14 @@ class NerfModel:
   # ---- NerfModel.__call__ (models.py:289-375) ---------------------------------------------
   def apply(self, variables, rays_dict: Dict[str, Any], warp_extra: Dict[str, Any] = None, metadata_encoded=False,
             use_warp=True, return_points=False, return_weights=False, return_warp_jacobian=False,
-            deterministic=False, rngs=None, *, train=False, return_z_vals=False, out=None, bf16=False):
+            deterministic=False, rngs=None, *, train=False, return_z_vals=False, out=None, bf16=False,
+            ray_grads=False):
     """Returns {'coarse': {...}, 'fine': {...}} like the reference.  `train=True` keeps the
     activation stash so `backward` can follow (used by training.train_step / autograd).  `out`: a dict
     returned by an earlier call with the same shapes/flags, to be overwritten in place (fixed output
     addresses: what a captured hipGraph replay needs).  `bf16=True` (inference only, no reference counterpart): the NeRF
-    MLPs take bfloat16 operands (NRF_FLAG_BF16), everything else stays fp32."""
+    MLPs take bfloat16 operands (NRF_FLAG_BF16), everything else stays fp32.  `ray_grads=True` (with train=True, float32 mode):
+    NRF_FLAG_RAY_GRADS, the stash also keeps what `backward(..., ray_grads=True)` needs for the gradients w.r.t. the rays."""
     del deterministic   # accepted and unused, as in the reference (models.py:298)
     warp_on = bool(self.use_warp and use_warp)
     # models.py:345-346, 367-368: the coarse level carries the Jacobian when the model was built with use_warp_jacobian
@@ -418,22 +423,26 @@ class NerfModel:
         setattr(lo, k, _ptr(t))
       ret[name] = d
     scal = _scalars(warp_extra)
-    ws = self.workspace(B, train, device, jacobian=bool(jac_levels), bf16=bf16)
+    ws = self.workspace(B, train, device, jacobian=bool(jac_levels), bf16=bf16, ray_grads=ray_grads)
     if train:
       self._train_ws = (B, ws)   # the stash `backward` differentiates (fp32 or bf16 layout), and the batch size it is for
     stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     flags = (L.NRF_FLAG_TRAIN if train else 0) | (L.NRF_FLAG_NO_WARP if self.use_warp and not warp_on else 0) | \
-        self.bf16_flags(bf16) | (L.NRF_FLAG_WARP_JACOBIAN if jac_levels else 0)
+        self.bf16_flags(bf16) | (L.NRF_FLAG_WARP_JACOBIAN if jac_levels else 0) | (L.NRF_FLAG_RAY_GRADS if ray_grads else 0)
     L.check(self.lib.nrf_forward(self.handle, _ptr(fp.flat), C.byref(rays), C.byref(scal), C.byref(rnd), C.byref(out),
                                  flags, _ptr(ws), ws.numel() * 4, stream), self.lib)
     del keep, keep2
     return ret
 
-  def backward(self, variables, rays_dict, d_rgb_coarse=None, d_rgb_fine=None, grad_out: torch.Tensor = None, d_out=None):
+  def backward(self, variables, rays_dict, d_rgb_coarse=None, d_rgb_fine=None, grad_out: torch.Tensor = None, d_out=None,
+               ray_grads=False):
     """VJP of the last `apply(..., train=True)` on the same rays: returns the flat parameter gradient.
     `d_out` = {'coarse': {...}, 'fine': {...}} carries a cotangent for any of 'rgb' (B,3), 'depth' (B,), 'acc' (B,),
     'weights' (B,S) and 'warped_points' (B,S,3) per level (nrf_backward_ex); what is absent (or None) counts as zero.
-    'med_depth' is piecewise constant and has none.  `d_rgb_coarse` / `d_rgb_fine` are the 'rgb' entries, positionally."""
+    'med_depth' is piecewise constant and has none.  `d_rgb_coarse` / `d_rgb_fine` are the 'rgb' entries, positionally.
+    `ray_grads`: True, or an iterable of 'origins' / 'directions' / 'viewdirs' -- after `apply(..., train=True, ray_grads=True)`;
+    returns (grad, {name: (B,3) gradient w.r.t. rays_dict[name]}) through nrf_backward_rays.  True asks for 'viewdirs' only where
+    the model and the rays have them."""
     device = torch.as_tensor(rays_dict['origins']).device
     fp = self.flat_params(variables, device)
     rays, keep = self._rays_struct(rays_dict, device)
@@ -447,6 +456,18 @@ class NerfModel:
       raise L.NrfError(f'backward(): the stashed forward was run on {stash[0]} rays, not {rays.num_rays}')
     ws = stash[1]   # the library also refuses a stash whose workspace plan was replaced by another call (NRF_E_STATE)
     stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    if ray_grads:
+      has_vd = bool(self.use_viewdirs) and 'viewdirs' in rays_dict
+      names = (('origins', 'directions') + (('viewdirs',) if has_vd else ())) if ray_grads is True else tuple(ray_grads)
+      if set(names) - {'origins', 'directions', 'viewdirs'}:
+        raise L.NrfError(f"backward(ray_grads=...): {sorted(names)} -- the rays' differentiable entries are 'origins', 'directions', 'viewdirs'")
+      rg_out = {k: torch.empty(rays.num_rays, 3, device=device) for k in names}
+      rg = L.RayGrads(*(_ptr(rg_out.get(k)) for k in ('origins', 'directions', 'viewdirs')))
+      og, keep2 = self._output_grads(d_out or {}, {'coarse': dc, 'fine': df}, rays.num_rays, device)
+      L.check(self.lib.nrf_backward_rays(self.handle, _ptr(fp.flat), C.byref(rays), C.byref(og), C.byref(rg), _ptr(grad), _ptr(ws),
+                                         ws.numel() * 4, stream), self.lib)
+      del keep, keep2
+      return grad, rg_out
     if d_out is None:
       L.check(self.lib.nrf_backward(self.handle, _ptr(fp.flat), C.byref(rays), _ptr(dc), _ptr(df), _ptr(grad), _ptr(ws),
                                     ws.numel() * 4, stream), self.lib)
