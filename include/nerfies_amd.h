@@ -37,7 +37,10 @@
 extern "C" {
 #endif
 
-#define NRF_VERSION 630 /* 0.6.3: NRF_FLAG_RAY_GRADS + nrf_backward_rays (nrf_ray_grads): gradients w.r.t. the ray origins, directions and
+#define NRF_VERSION 640 /* 0.6.4: camera tables (NRF_CAMERA_ROW): nrf_camera_table_rays / _project and their reverse passes into the camera
+                           parameters (nrf_camera_table_rays_backward / _project_backward, nrf_camera_table_workspace_bytes).  Nothing
+                           that existed changes.
+                           0.6.3: NRF_FLAG_RAY_GRADS + nrf_backward_rays (nrf_ray_grads): gradients w.r.t. the ray origins, directions and
                            viewdirs (float32 training mode).  nrf_backward / nrf_backward_ex and every plan without the flag are unchanged.
                            0.6.2: nrf_backward_ex (nrf_output_grads): cotangents for depth, acc, weights and warped_points next to
                            rgb.  nrf_backward is unchanged.
@@ -528,6 +531,53 @@ int nrf_camera_pixels_to_points(const nrf_camera* camera, const float* pixels, c
 
 /* Camera.project (camera.py:283-315): world points [n,3] -> distorted pixel positions [n,2]. */
 int nrf_camera_project(const nrf_camera* camera, const float* points, int64_t n, float* pixels, void* stream);
+
+/* ---- camera tables: differentiable cameras (since 0.6.4) ----
+ * A camera table is a DEVICE array (num_cameras, NRF_CAMERA_ROW) fp32, 16-byte aligned.  Row c holds the NRF_CAMERA_NPARAMS
+ * differentiable fields of nrf_camera in its field order -- orientation[9], position[3], focal_length, principal_point[2], skew,
+ * pixel_aspect_ratio, radial_distortion[3], tangential_distortion[2] -- and two pad floats, which are never read and always
+ * receive gradient 0.  image_size is not part of a row: these entry points always take explicit pixels.
+ *
+ * camera_index (n,) int32 names each ray's row; NULL = every ray uses row 0.  The table lives on the device, so its VALUES (and the
+ * indices) cannot be validated without a synchronisation and are not: a row with focal_length or pixel_aspect_ratio 0 gives inf / nan
+ * as the arithmetic does.  The kernels never read or write outside the table: a ray whose index lies outside [0, num_cameras) gets
+ * zero outputs, zero d_pixels / d_points, and contributes no gradient.
+ *
+ * As everywhere: device pointers plus sizes, nothing allocated or synchronised, every launch on `stream` (graph-capturable); the
+ * arguments are validated on the host before any HIP call (NRF_E_NULL / NRF_E_SHAPE / NRF_E_WORKSPACE).  n == 0 is a successful
+ * no-op, except that the reverse passes still zero d_cameras; the per-ray buffers of an empty batch may be NULL.  n <= INT32_MAX.  pixels / d_pixels are 8-byte aligned, the
+ * workspace 16-byte aligned.
+ *
+ * Forward, per ray exactly Camera.pixels_to_rays / Camera.project of its row; "distorted" (whether the Newton undistort runs) is
+ * decided per row on the device as on the host: any of the five coefficients non-zero. */
+#define NRF_CAMERA_ROW 24
+#define NRF_CAMERA_NPARAMS 22
+
+/* pixels (n,2) -> directions (n,3) and, when non-NULL, origins (n,3) = the row's position. */
+int nrf_camera_table_rays(const float* cameras, int32_t num_cameras, const int32_t* camera_index, const float* pixels, int64_t n,
+                          float* origins, float* directions, void* stream);
+
+/* points (n,3) -> pixels (n,2). */
+int nrf_camera_table_project(const float* cameras, int32_t num_cameras, const int32_t* camera_index, const float* points, int64_t n,
+                             float* pixels, void* stream);
+
+/* Bytes of workspace the two reverse passes below need for n rays (num_cameras is validated; today the size depends on n alone). */
+int nrf_camera_table_workspace_bytes(int64_t n, int32_t num_cameras, size_t* bytes);
+
+/* Reverse pass of nrf_camera_table_rays: d_origins, d_directions (n,3), either may be NULL (= zeros) -> d_cameras
+ * (num_cameras, NRF_CAMERA_ROW), OVERWRITTEN (rows without a ray and the pads become 0), and, when non-NULL, d_pixels (n,2).
+ * The undistort is differentiated by the implicit-function theorem at the forward's result, the second normalisation
+ * w / |w| is differentiated too (orientation is nine free parameters), and the distortion coefficients of a row whose coefficients
+ * are all zero receive the same formula's gradient (J = I there): a lens correction can be learned from zero.  DESIGN.md section 1.
+ * The sums over rays use no atomics: two calls on the same inputs give the same bits.  The workspace needs no clearing. */
+int nrf_camera_table_rays_backward(const float* cameras, int32_t num_cameras, const int32_t* camera_index, const float* pixels,
+                                   int64_t n, const float* d_origins, const float* d_directions, float* d_cameras, float* d_pixels,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* Reverse pass of nrf_camera_table_project: d_pixels (n,2) -> d_cameras as above and, when non-NULL, d_points (n,3). */
+int nrf_camera_table_project_backward(const float* cameras, int32_t num_cameras, const int32_t* camera_index, const float* points,
+                                      int64_t n, const float* d_pixels, float* d_cameras, float* d_points, void* workspace,
+                                      size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,23 @@ deltas, a learned lens correction), the call goes through `RayRenderFunction` in
 backward is ONE nrf_backward_rays call that returns the parameter gradient and the three (B,3) ray gradients (float32 mode only).
 viewdirs = d / |d| is the caller's own torch expression, so autograd carries d_viewdirs on to the directions.  The 'points' output
 stays non-differentiable: rebuild o + z d from 'z_vals' in torch; a cotangent on 'warped_points' does reach the rays.  With no
-requires_grad ray the call is the one above: same flag word, same launches."""
+requires_grad ray the call is the one above: same flag word, same launches.
+
+Cameras: the rays themselves come differentiably from a camera table (nerfies_amd.camera.pack_cameras, (C, 24) on the device) through
+`CameraRaysFunction` (nrf_camera_table_rays / _rays_backward), world points go to pixels through `CameraProjectFunction`.  The
+whole chain of a pose / intrinsics / lens refinement:
+
+    table = pack_cameras(cameras).requires_grad_()
+    origins, directions = rays_from_table(table, pixels, item_index)       # HIP, one table row per ray
+    viewdirs = directions / directions.norm(dim=-1, keepdim=True)          # torch
+    out = render_differentiable(model, flat, dict(batch, origins=origins, directions=directions, viewdirs=viewdirs))
+    loss(out).backward()                                                   # nrf_backward_rays, then nrf_camera_table_rays_backward
+    table.grad                                                             # (C, 24); the two pads of a row stay 0
+
+The distortion coefficients of a camera whose coefficients are all zero receive a gradient as well, so a lens
+correction can be learned from zero.  Out of scope: a table form of pixels_to_points, camera gradients through the fused
+`loss_and_grad`, the bf16 modes (ray gradients are float32 only), a rotation parametrisation (map your own 3-vector to the nine
+orientation entries in torch)."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -134,3 +150,122 @@ def render_differentiable(model, flat_params, rays, warp_extra=None, rngs=None, 
     out.setdefault(lv, {})[k] = t
   return out
 
+
+
+_camera_ws = {}   # device -> the cached workspace of the camera-table reverse passes
+
+
+def _camera_workspace(lib, n, num_cameras, device):
+  import ctypes as C
+  need = C.c_size_t(0)
+  L.check(lib.nrf_camera_table_workspace_bytes(n, num_cameras, C.byref(need)), lib)
+  ws = _camera_ws.get(device)
+  if ws is None or ws.numel() < need.value:
+    ws = _camera_ws[device] = torch.empty(need.value, dtype=torch.uint8, device=device)
+  return ws
+
+
+def _ptr(t):
+  return t.data_ptr() if t is not None else None
+
+
+def _table_args(table, x, last, camera_index):
+  """-> (table, x flattened to [n, last], index flattened to [n] or None, batch shape), validated."""
+  if table.dim() != 2 or table.shape[1] != L.NRF_CAMERA_ROW or table.dtype != torch.float32 or not table.is_cuda:
+    raise ValueError(f'a camera table is a float32 CUDA tensor (C, {L.NRF_CAMERA_ROW}) (see pack_cameras)')
+  if x.shape[-1] != last or x.dtype != torch.float32 or x.device != table.device:
+    raise ValueError(f'expected a float32 [..., {last}] tensor on the device of the table')
+  batch = tuple(x.shape[:-1])
+  n = 1
+  for b in batch:
+    n *= b
+  if camera_index is not None:
+    if camera_index.dtype != torch.int32 or camera_index.device != table.device or camera_index.numel() != n:
+      raise ValueError('camera_index must be an int32 tensor on the device of the table with one entry per ray')
+    camera_index = camera_index.reshape(-1).contiguous()
+  return table, x.reshape(-1, last), camera_index, batch
+
+
+class CameraRaysFunction(torch.autograd.Function):
+  """(table (C,24), pixels (n,2), camera_index (n,) or None) -> (origins, directions): nrf_camera_table_rays; backward: one
+  nrf_camera_table_rays_backward call."""
+
+  @staticmethod
+  def forward(ctx, table, pixels, camera_index):
+    lib = L.load_library()
+    table, pixels = table.detach().contiguous(), pixels.detach().contiguous()
+    n = pixels.shape[0]
+    origins = torch.empty((n, 3), dtype=torch.float32, device=table.device)
+    directions = torch.empty((n, 3), dtype=torch.float32, device=table.device)
+    with torch.cuda.device(table.device):
+      L.check(lib.nrf_camera_table_rays(table.data_ptr(), table.shape[0], _ptr(camera_index), pixels.data_ptr(), n,
+                                        origins.data_ptr(), directions.data_ptr(), torch.cuda.current_stream().cuda_stream), lib)
+    ctx.save_for_backward(table, pixels, camera_index)
+    ctx.set_materialize_grads(False)   # an unused d_origins reaches the library as NULL
+    return origins, directions
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, d_origins, d_directions):
+    table, pixels, camera_index = ctx.saved_tensors
+    lib = L.load_library()
+    n = pixels.shape[0]
+    d_origins = d_origins.contiguous().float() if d_origins is not None else None
+    d_directions = d_directions.contiguous().float() if d_directions is not None else None
+    d_table = torch.empty_like(table)
+    d_pixels = torch.empty_like(pixels) if ctx.needs_input_grad[1] else None
+    with torch.cuda.device(table.device):
+      ws = _camera_workspace(lib, n, table.shape[0], table.device)
+      L.check(lib.nrf_camera_table_rays_backward(table.data_ptr(), table.shape[0], _ptr(camera_index), pixels.data_ptr(), n,
+                                                 _ptr(d_origins), _ptr(d_directions), d_table.data_ptr(), _ptr(d_pixels),
+                                                 ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream), lib)
+    return (d_table if ctx.needs_input_grad[0] else None), d_pixels, None
+
+
+class CameraProjectFunction(torch.autograd.Function):
+  """(table (C,24), points (n,3), camera_index (n,) or None) -> pixels (n,2): nrf_camera_table_project; backward: one
+  nrf_camera_table_project_backward call."""
+
+  @staticmethod
+  def forward(ctx, table, points, camera_index):
+    lib = L.load_library()
+    table, points = table.detach().contiguous(), points.detach().contiguous()
+    n = points.shape[0]
+    pixels = torch.empty((n, 2), dtype=torch.float32, device=table.device)
+    with torch.cuda.device(table.device):
+      L.check(lib.nrf_camera_table_project(table.data_ptr(), table.shape[0], _ptr(camera_index), points.data_ptr(), n,
+                                           pixels.data_ptr(), torch.cuda.current_stream().cuda_stream), lib)
+    ctx.save_for_backward(table, points, camera_index)
+    ctx.set_materialize_grads(False)
+    return pixels
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, d_pixels):
+    table, points, camera_index = ctx.saved_tensors
+    if d_pixels is None:
+      return None, None, None
+    lib = L.load_library()
+    n = points.shape[0]
+    d_pixels = d_pixels.contiguous().float()
+    d_table = torch.empty_like(table)
+    d_points = torch.empty_like(points) if ctx.needs_input_grad[1] else None
+    with torch.cuda.device(table.device):
+      ws = _camera_workspace(lib, n, table.shape[0], table.device)
+      L.check(lib.nrf_camera_table_project_backward(table.data_ptr(), table.shape[0], _ptr(camera_index), points.data_ptr(), n,
+                                                    d_pixels.data_ptr(), d_table.data_ptr(), _ptr(d_points), ws.data_ptr(),
+                                                    ws.numel(), torch.cuda.current_stream().cuda_stream), lib)
+    return (d_table if ctx.needs_input_grad[0] else None), d_points, None
+
+
+def camera_rays(table, pixels, camera_index=None):
+  """nerfies_amd.camera.rays_from_table."""
+  table, px, idx, batch = _table_args(table, pixels, 2, camera_index)
+  origins, directions = CameraRaysFunction.apply(table, px, idx)
+  return origins.reshape(batch + (3,)), directions.reshape(batch + (3,))
+
+
+def camera_project(table, points, camera_index=None):
+  """nerfies_amd.camera.project_from_table."""
+  table, pts, idx, batch = _table_args(table, points, 3, camera_index)
+  return CameraProjectFunction.apply(table, pts, idx).reshape(batch + (2,))

@@ -8,7 +8,11 @@ of the reference's per-frame host NumPy pass.  The remaining methods only edit t
 host, as in the reference.
 
 Arrays: a CUDA torch tensor in -> a CUDA tensor out (no copy); a NumPy array in -> uploaded, NumPy out.
-There is no CPU implementation: without the HIP library these methods raise."""
+There is no CPU implementation: without the HIP library these methods raise.
+
+Differentiable cameras: `pack_cameras` lays cameras out as a device table (C, 24) (include/nerfies_amd.h, NRF_CAMERA_ROW),
+`rays_from_table` / `project_from_table` run the same geometry with one table row per ray (nrf_camera_table_*) and are
+differentiable in the table -- and in the pixels / points -- through nerfies_amd.autograd."""
 import copy
 import json
 
@@ -20,6 +24,13 @@ from . import lib as L
 
 def _stream():
   return torch.cuda.current_stream().cuda_stream
+
+
+# name -> slice of a camera-table row, in the field order of nrf_camera; floats 22, 23 of a row are pads
+CAMERA_PARAM_SLICES = {
+    'orientation': slice(0, 9), 'position': slice(9, 12), 'focal_length': slice(12, 13), 'principal_point': slice(13, 15),
+    'skew': slice(15, 16), 'pixel_aspect_ratio': slice(16, 17), 'radial_distortion': slice(17, 20),
+    'tangential_distortion': slice(20, 22)}
 
 
 class Camera:
@@ -207,3 +218,38 @@ class Camera:
 def camera_to_rays(camera, device='cuda'):
   """datasets/core.py:50-75."""
   return camera.to_rays(device)
+
+
+def pack_cameras(cameras, device='cuda'):
+  """Cameras -> their table: a (C, 24) float32 tensor on `device`, row c = the 22 parameters of cameras[c] in the order of
+  CAMERA_PARAM_SLICES and two zero pads.  image_size is not part of a row."""
+  rows = np.zeros((len(cameras), L.NRF_CAMERA_ROW), np.float32)
+  for r, c in zip(rows, cameras):
+    for name, sl in CAMERA_PARAM_SLICES.items():
+      r[sl] = np.asarray(getattr(c, name), np.float64).reshape(-1)
+  return torch.from_numpy(rows).to(device)
+
+
+def unpack_camera(row, image_size):
+  """One table row (a tensor or array of 24, or 22, floats) -> Camera."""
+  v = row.detach().cpu().numpy() if torch.is_tensor(row) else np.asarray(row)
+  f = {name: np.array(v[sl], np.float32) for name, sl in CAMERA_PARAM_SLICES.items()}
+  return Camera(orientation=f['orientation'].reshape(3, 3), position=f['position'], focal_length=f['focal_length'][0],
+                principal_point=f['principal_point'], image_size=image_size, skew=f['skew'][0],
+                pixel_aspect_ratio=f['pixel_aspect_ratio'][0], radial_distortion=f['radial_distortion'],
+                tangential_distortion=f['tangential_distortion'])
+
+
+def rays_from_table(table, pixels, camera_index=None):
+  """(origins, directions), each [..., 3], of `pixels` [..., 2] seen from row camera_index[...] of `table` (C, 24): per ray
+  Camera.pixels_to_rays and the tiled position of that row.  camera_index: int32 [...] or [..., 1], None = row 0 for every ray.
+  Differentiable in `table`, and in `pixels` when they require grad."""
+  from . import autograd
+  return autograd.camera_rays(table, pixels, camera_index)
+
+
+def project_from_table(table, points, camera_index=None):
+  """Pixels [..., 2] of world `points` [..., 3] in row camera_index[...] of `table`: per point Camera.project.
+  Differentiable in `table`, and in `points` when they require grad."""
+  from . import autograd
+  return autograd.camera_project(table, points, camera_index)

@@ -617,4 +617,75 @@ int nrf_camera_project(const nrf_camera* camera, const float* points, int64_t n,
   return check_launch("nrf_camera_project");
 }
 
+namespace {
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+// what every camera-table entry point checks before any HIP call
+int table_args(const float* cameras, int32_t num_cameras, int64_t n) {
+  if (!cameras) return fail(NRF_E_NULL, "cameras is null");
+  if (num_cameras <= 0) return fail(NRF_E_SHAPE, "num_cameras must be positive");
+  if (n < 0 || n > INT32_MAX) return fail(NRF_E_SHAPE, "n must be in [0, INT32_MAX]");
+  if (!aligned16(cameras)) return fail(NRF_E_SHAPE, "the camera table must be 16-byte aligned");
+  return NRF_OK;
+}
+int table_workspace_args(int64_t n, const void* workspace, size_t workspace_bytes) {
+  if (!workspace) return fail(NRF_E_NULL, "workspace is null");
+  if (!aligned16(workspace)) return fail(NRF_E_SHAPE, "workspace must be 16-byte aligned");
+  if (workspace_bytes < camera_table_workspace_bytes((long)n))
+    return fail(NRF_E_WORKSPACE, "workspace too small (see nrf_camera_table_workspace_bytes)");
+  return NRF_OK;
+}
+}  // namespace
+
+int nrf_camera_table_workspace_bytes(int64_t n, int32_t num_cameras, size_t* bytes) {
+  if (!bytes) return fail(NRF_E_NULL, "bytes is null");
+  if (num_cameras <= 0) return fail(NRF_E_SHAPE, "num_cameras must be positive");
+  if (n < 0 || n > INT32_MAX) return fail(NRF_E_SHAPE, "n must be in [0, INT32_MAX]");
+  *bytes = camera_table_workspace_bytes((long)n);
+  return NRF_OK;
+}
+
+int nrf_camera_table_rays(const float* cameras, int32_t num_cameras, const int32_t* camera_index, const float* pixels, int64_t n,
+                          float* origins, float* directions, void* stream) {
+  CK(table_args(cameras, num_cameras, n));
+  if (n == 0) return NRF_OK;   // nothing to do: the per-ray buffers of an empty batch may be NULL
+  if (!pixels || !directions) return fail(NRF_E_NULL, "pixels / directions is null");
+  if (!aligned8(pixels)) return fail(NRF_E_SHAPE, "pixel buffers must be 8-byte aligned");
+  launch_camera_table_rays(cameras, num_cameras, camera_index, pixels, (long)n, origins, directions, (hipStream_t)stream);
+  return check_launch("nrf_camera_table_rays");
+}
+
+int nrf_camera_table_project(const float* cameras, int32_t num_cameras, const int32_t* camera_index, const float* points, int64_t n,
+                             float* pixels, void* stream) {
+  CK(table_args(cameras, num_cameras, n));
+  if (n == 0) return NRF_OK;
+  if (!points || !pixels) return fail(NRF_E_NULL, "points / pixels is null");
+  if (!aligned8(pixels)) return fail(NRF_E_SHAPE, "pixel buffers must be 8-byte aligned");
+  launch_camera_table_project(cameras, num_cameras, camera_index, points, (long)n, pixels, (hipStream_t)stream);
+  return check_launch("nrf_camera_table_project");
+}
+
+int nrf_camera_table_rays_backward(const float* cameras, int32_t num_cameras, const int32_t* camera_index, const float* pixels,
+                                   int64_t n, const float* d_origins, const float* d_directions, float* d_cameras, float* d_pixels,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  CK(table_args(cameras, num_cameras, n));
+  if ((!pixels && n > 0) || !d_cameras) return fail(NRF_E_NULL, "pixels / d_cameras is null");
+  if (!aligned8(pixels) || !aligned8(d_pixels)) return fail(NRF_E_SHAPE, "pixel buffers must be 8-byte aligned");
+  CK(table_workspace_args(n, workspace, workspace_bytes));
+  launch_camera_table_rays_backward(cameras, num_cameras, camera_index, pixels, (long)n, d_origins, d_directions, d_cameras, d_pixels,
+                                    workspace, (hipStream_t)stream);
+  return check_launch("nrf_camera_table_rays_backward");
+}
+
+int nrf_camera_table_project_backward(const float* cameras, int32_t num_cameras, const int32_t* camera_index, const float* points,
+                                      int64_t n, const float* d_pixels, float* d_cameras, float* d_points, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  CK(table_args(cameras, num_cameras, n));
+  if (((!points || !d_pixels) && n > 0) || !d_cameras) return fail(NRF_E_NULL, "points / d_pixels / d_cameras is null");
+  if (!aligned8(d_pixels)) return fail(NRF_E_SHAPE, "pixel buffers must be 8-byte aligned");
+  CK(table_workspace_args(n, workspace, workspace_bytes));
+  launch_camera_table_project_backward(cameras, num_cameras, camera_index, points, (long)n, d_pixels, d_cameras, d_points, workspace,
+                                       (hipStream_t)stream);
+  return check_launch("nrf_camera_table_project_backward");
+}
+
 }  // extern "C"

@@ -591,5 +591,18 @@ struct CameraArgs {
 void launch_camera_rays(const CameraArgs& c, const float* pixels, const float* depth, long n, float* origins,
                         float* directions, float* pixels_out, hipStream_t stream);
 void launch_camera_project(const CameraArgs& c, const float* points, long n, float* pixels, hipStream_t stream);
+// camera table (C, NRF_CAMERA_ROW): the same geometry with the camera read per ray from device memory, and its reverse passes
+// (two launches each: per-ray partials + records, then one workgroup per camera; `workspace` as camera_table_workspace_bytes(n))
+size_t camera_table_workspace_bytes(long n);
+void launch_camera_table_rays(const float* cameras, int num_cameras, const int* camera_index, const float* pixels, long n,
+                              float* origins, float* directions, hipStream_t stream);
+void launch_camera_table_project(const float* cameras, int num_cameras, const int* camera_index, const float* points, long n,
+                                 float* pixels, hipStream_t stream);
+void launch_camera_table_rays_backward(const float* cameras, int num_cameras, const int* camera_index, const float* pixels, long n,
+                                       const float* d_origins, const float* d_directions, float* d_cameras, float* d_pixels,
+                                       void* workspace, hipStream_t stream);
+void launch_camera_table_project_backward(const float* cameras, int num_cameras, const int* camera_index, const float* points, long n,
+                                          const float* d_pixels, float* d_cameras, float* d_points, void* workspace,
+                                          hipStream_t stream);
 
 }  // namespace nrf

@@ -150,22 +150,30 @@ class DataSource:
     rays['rgb'] = torch.from_numpy(item['rgb']).to(rays['origins'].device)
     return rays
 
-  def create_ray_table(self, item_ids: Sequence[str], device='cuda', shuffle=True) -> 'RayTable':
+  def camera_table(self, item_ids: Sequence[str], device='cuda') -> torch.Tensor:
+    """The cameras of `item_ids` as a camera table (camera.pack_cameras): row k is the camera of item_ids[k], which is what the
+    'item_index' column of create_ray_table(item_ids, keep_item_index=True) names."""
+    return cam.pack_cameras([self.load_camera(i) for i in item_ids], device)
+
+  def create_ray_table(self, item_ids: Sequence[str], device='cuda', shuffle=True, keep_item_index=False) -> 'RayTable':
     """Every ray of `item_ids`, flattened, (optionally) under one global permutation, resident on `device`
-    (core.py:392-447 _create_preloaded_dataset with flatten=True)."""
+    (core.py:392-447 _create_preloaded_dataset with flatten=True).  keep_item_index: an extra column 'item_index' (N, 1) int32,
+    each ray's position in `item_ids`, permuted with the rest (camera refinement: the row of `camera_table(item_ids)`)."""
     host_items = parallel_map(self.get_item, list(item_ids))       # PNG decode + JSON on host threads
     cols: Dict[str, List[torch.Tensor]] = {}
     from . import evaluation
-    for item in host_items:
+    for k, item in enumerate(host_items):
       rays = evaluation.rays_from_camera(item['camera'], item['metadata'], device)
       h, w = rays['origins'].shape[:2]
       if item['rgb'].shape[:2] != (h, w):
         raise ValueError(f'image is {item["rgb"].shape[:2]} but the camera says {(h, w)}')
       rays['rgb'] = torch.from_numpy(item['rgb']).to(rays['origins'].device)
       flat = {'origins': rays['origins'], 'directions': rays['directions'], 'pixels': rays['pixels'], 'rgb': rays['rgb']}
-      flat.update({'metadata/' + k: v for k, v in rays.get('metadata', {}).items()})
-      for k, v in flat.items():
-        cols.setdefault(k, []).append(v.reshape(h * w, -1))
+      flat.update({'metadata/' + name: v for name, v in rays.get('metadata', {}).items()})
+      if keep_item_index:
+        flat['item_index'] = torch.full((h * w, 1), k, dtype=torch.int32, device=rays['origins'].device)
+      for name, v in flat.items():
+        cols.setdefault(name, []).append(v.reshape(h * w, -1))
     table = {k: torch.cat(v, 0) for k, v in cols.items()}
     n = table['origins'].shape[0]
     if shuffle:

@@ -14,6 +14,8 @@ NRF_FLAG_WARP_F32 = 16
 NRF_FLAG_BF16X3 = 32
 NRF_FLAG_RAY_GRADS = 64
 NRF_NUM_STATS = 16
+NRF_CAMERA_ROW = 24       # floats per row of a camera table
+NRF_CAMERA_NPARAMS = 22   # of which differentiable parameters (the rest: pads)
 ACT = {'relu': 0, 'softplus': 1}
 WARP_FIELD = {'se3': 0, 'translation': 1}
 META_ENCODER = {'glo': 0, 'time': 1}
@@ -136,6 +138,8 @@ EXPORTS = [
     'nrf_camera_pixels_to_rays', 'nrf_camera_pixels_to_points', 'nrf_camera_project',
     'nrf_dynamic_scalars_write', 'nrf_adam_step_dynamic', 'nrf_set_option', 'nrf_debug_plan_digest', 'nrf_backward_ex',
     'nrf_backward_rays',
+    'nrf_camera_table_rays', 'nrf_camera_table_project', 'nrf_camera_table_workspace_bytes', 'nrf_camera_table_rays_backward',
+    'nrf_camera_table_project_backward',
 ]
 
 _lib = None
@@ -192,6 +196,11 @@ def load_library(path=None):
       'nrf_camera_pixels_to_rays': [C.POINTER(CameraDesc), vp, i64, vp, vp, vp, vp],
       'nrf_camera_pixels_to_points': [C.POINTER(CameraDesc), vp, vp, i64, vp, vp],
       'nrf_camera_project': [C.POINTER(CameraDesc), vp, i64, vp, vp],
+      'nrf_camera_table_rays': [vp, i32, vp, vp, i64, vp, vp, vp],
+      'nrf_camera_table_project': [vp, i32, vp, vp, i64, vp, vp],
+      'nrf_camera_table_workspace_bytes': [i64, i32, C.POINTER(C.c_size_t)],
+      'nrf_camera_table_rays_backward': [vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, C.c_size_t, vp],
+      'nrf_camera_table_project_backward': [vp, i32, vp, vp, i64, vp, vp, vp, vp, C.c_size_t, vp],
   }
   for name, argtypes in sigs.items():
     fn = getattr(lib, name)

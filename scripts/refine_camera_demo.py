@@ -1,0 +1,86 @@
+#!/usr/bin/env python
+"""Camera refinement through the whole differentiable chain, on a synthetic capture:
+
+    pose 6-vector -> camera table row (torch) -> rays_from_table (HIP) -> viewdirs = d / |d| (torch)
+      -> render_differentiable (HIP, nrf_backward_rays) -> photometric + depth loss -> backward -> torch Adam
+
+The NeRF parameters are fixed (a freshly initialised field); the target is its own rendering from the true camera of frame 0.  That
+camera's position and orientation are then perturbed and recovered.  A demonstration, not a test:
+    python scripts/refine_camera_demo.py [--steps 300]"""
+import argparse
+import os
+import sys
+import tempfile
+import types
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from nerfies_amd import autograd, datasets, models  # noqa: E402
+from nerfies_amd.camera import CAMERA_PARAM_SLICES as SL, rays_from_table  # noqa: E402
+
+
+def hat(w):
+  z = torch.zeros((), device=w.device)
+  return torch.stack([torch.stack([z, -w[2], w[1]]), torch.stack([w[2], z, -w[0]]), torch.stack([-w[1], w[0], z])])
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--steps', type=int, default=300)
+  ap.add_argument('--lr', type=float, default=2e-3)
+  args = ap.parse_args()
+  dev = torch.device('cuda:0')
+  with tempfile.TemporaryDirectory() as d:
+    datasets.write_synthetic_scene(d, num_frames=4, size=(32, 24))
+    src = datasets.NerfiesDataSource(d, image_scale=1)
+    ids = src.train_ids
+    table0 = src.camera_table(ids, dev)
+    rays = src.create_ray_table(ids, dev, shuffle=True, keep_item_index=True)
+    near, far = src.near, src.far
+  cfg = types.SimpleNamespace(num_coarse_samples=32, num_fine_samples=32, num_nerf_point_freqs=6, nerf_trunk_width=128,
+                              use_stratified_sampling=False, sigma_activation='softplus')
+  model, fp = models.construct_nerf(0, cfg, 0, [0], [0], [0], near, far)
+  col = rays.columns
+  sel = (col['item_index'][:, 0] == 0).nonzero()[:, 0]   # the rays of frame 0, in the table's permuted order
+  pixels, index = col['pixels'][sel].contiguous(), col['item_index'][sel].contiguous()
+
+  def render(table):
+    origins, directions = rays_from_table(table, pixels, index)
+    viewdirs = directions / directions.norm(dim=-1, keepdim=True)
+    out = autograd.render_differentiable(model, fp.flat, {'origins': origins, 'directions': directions, 'viewdirs': viewdirs,
+                                                          'metadata': {}})
+    return out['fine']['rgb'], out['fine']['depth']
+
+  with torch.no_grad():
+    rgb_t, depth_t = (t.clone() for t in render(table0))
+  R0, p0 = table0[0, SL['orientation']].reshape(3, 3).clone(), table0[0, SL['position']].clone()
+  w_off = torch.tensor([0.02, -0.015, 0.01], device=dev)     # radians
+  p_off = torch.tensor([0.010, -0.008, 0.006], device=dev)   # scene units (the scene spans about 0.3)
+  R_start = torch.matrix_exp(hat(w_off)) @ R0
+  w = torch.zeros(3, device=dev, requires_grad=True)
+  t = torch.zeros(3, device=dev, requires_grad=True)
+  opt = torch.optim.Adam([w, t], lr=args.lr)
+  print(f'frame 0 of {len(ids)}: {pixels.shape[0]} rays; start: position error {p_off.norm().item():.5f}, rotation error '
+        f'{w_off.norm().item():.5f} rad')
+  for step in range(args.steps + 1):
+    R = torch.matrix_exp(hat(w)) @ R_start   # the caller's own rotation parametrisation -> nine orientation entries
+    row = torch.cat([R.reshape(9), p0 + p_off + t, table0[0, 12:]])
+    table = torch.cat([row[None], table0[1:]], 0)
+    rgb, depth = render(table)
+    loss = ((rgb - rgb_t) ** 2).mean() + ((depth - depth_t) ** 2).mean()
+    if step % 10 == 0:
+      with torch.no_grad():
+        cosang = ((R @ R0.T).diagonal().sum() - 1) / 2
+        print(f'step {step:4d}  loss {loss.item():.3e}  position error {(p_off + t).norm().item():.5f}  rotation error '
+              f'{torch.acos(cosang.clamp(-1, 1)).item():.5f} rad')
+    if step == args.steps:
+      break
+    opt.zero_grad()
+    loss.backward()
+    opt.step()
+
+
+if __name__ == '__main__':
+  main()
