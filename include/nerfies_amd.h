@@ -37,7 +37,11 @@
 extern "C" {
 #endif
 
-#define NRF_VERSION 640 /* 0.6.4: camera tables (NRF_CAMERA_ROW): nrf_camera_table_rays / _project and their reverse passes into the camera
+#define NRF_VERSION 650 /* 0.6.5: nrf_train_step_loss_grad_rays (the fused train step with ray gradients; nrf_workspace_bytes_ex accepts
+                           NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS together with the regularisers) and camera delta tables
+                           (NRF_CAMERA_DELTA_ROW): nrf_camera_table_compose / _compose_backward.  Plans without the flag, and plans
+                           with the flag but without regularisers, are unchanged.
+                           0.6.4: camera tables (NRF_CAMERA_ROW): nrf_camera_table_rays / _project and their reverse passes into the camera
                            parameters (nrf_camera_table_rays_backward / _project_backward, nrf_camera_table_workspace_bytes).  Nothing
                            that existed changes.
                            0.6.3: NRF_FLAG_RAY_GRADS + nrf_backward_rays (nrf_ray_grads): gradients w.r.t. the ray origins, directions and
@@ -401,6 +405,29 @@ int nrf_train_step_loss_grad_ex(nrf_handle h, const float* params, const nrf_ray
 int nrf_workspace_bytes_ex(nrf_handle h, int32_t num_rays, uint32_t flags, int32_t num_background_points,
                            int32_t use_elastic_loss, size_t* bytes);
 
+/* Since 0.6.5: nrf_train_step_loss_grad_ex (flags = 0) that also returns the gradients of the loss w.r.t. the rays -- what refining
+ * cameras next to the field needs.  One call: the forward under NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS, the fixed loss, the reverse
+ * pass.  grad_params and stats exactly as nrf_train_step_loss_grad_ex writes them; ray_grads->d_origins / d_directions (B,3) are
+ * OVERWRITTEN (either may be NULL, which skips it).  The workspace comes from nrf_workspace_bytes_ex(NRF_FLAG_TRAIN |
+ * NRF_FLAG_RAY_GRADS, num_background_points, use_elastic_loss).  Float32 only: NRF_FLAG_BF16* in flags -> NRF_E_UNSUPPORTED;
+ * ray_grads NULL -> NRF_E_NULL; both decided before any launch.  nrf_train_step_loss_grad_ex itself keeps refusing the flag.
+ *
+ * Photometric terms only: the ray gradients are those of MSE_coarse + MSE_fine.  The background, elastic and warp_reg terms
+ * regularise the field; their dependence on the sample positions is treated as stop-gradient and they add nothing to the rays
+ * (the ray stage runs before warp_reg adds into the warped points' gradient).
+ *
+ * rays->viewdirs == NULL on a use_viewdirs model (the condition then reads the directions, models.py:326-329): d_directions
+ * includes the view-dependence term, i.e. what nrf_backward_rays would return as d_directions + d_viewdirs when called with
+ * viewdirs = directions.  One wave owns a ray, so the order of that sum is fixed (no atomics).  d_viewdirs non-NULL in that case
+ * stays NRF_E_UNSUPPORTED (as in nrf_backward_rays, which is unchanged).
+ *
+ * With the elastic regulariser the coarse tangent pass serves both the regulariser and the coarse warp Jacobian of the ray
+ * stage; the fine level's Jacobian pass runs into a scratch level of its own. */
+int nrf_train_step_loss_grad_rays(nrf_handle h, const float* params, const nrf_rays* rays, const float* target_rgb,
+                                  const nrf_step_scalars* scalars, const nrf_rand* rnd, const nrf_background* bg,
+                                  const nrf_elastic* el, const nrf_warp_reg* wr, uint32_t flags, const nrf_ray_grads* ray_grads,
+                                  float* grad_params, float* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 /* warping.SE3Field on arbitrary points with one warp id per point: model.create_warp_field(num_batch_dims=1)
  * .apply(points, metadata, warp_extra, False, False) (models.py:165-184, warping.py:355-389). */
 int nrf_warp_points_workspace_bytes(nrf_handle h, int32_t num_points, size_t* bytes);
@@ -578,6 +605,24 @@ int nrf_camera_table_rays_backward(const float* cameras, int32_t num_cameras, co
 int nrf_camera_table_project_backward(const float* cameras, int32_t num_cameras, const int32_t* camera_index, const float* points,
                                       int64_t n, const float* d_pixels, float* d_cameras, float* d_points, void* workspace,
                                       size_t workspace_bytes, void* stream);
+
+/* ---- camera delta tables: refining a camera table (since 0.6.5) ----
+ * A delta table is a DEVICE array (num_cameras, NRF_CAMERA_DELTA_ROW) fp32, 16-byte aligned.  Row c changes row c of a base table:
+ *   [0:3]   omega            R = exp(hat omega) R0.  orientation is world-to-camera, so this turns the camera in its own frame
+ *   [3:6]   t                position = p0 + t
+ *   [6]     s                focal_length = f0 exp(s)
+ *   [7:9]   principal point  added
+ *   [9:12]  radial           added
+ *   [12:14] tangential       added
+ *   [14:16] pads             never read; their gradient is 0
+ * skew and pixel_aspect_ratio are copied through, the output row's pads are 0.  The rotation uses the closed forms and the
+ * theta^2 series of the SE3 field (exact value and gradient at omega = 0, where every refinement starts).  One thread per camera;
+ * validation, streams and graph capture as for the camera tables above.  `out` may not alias `cameras`. */
+#define NRF_CAMERA_DELTA_ROW 16
+int nrf_camera_table_compose(const float* cameras, const float* deltas, int32_t num_cameras, float* out, void* stream);
+/* d_cameras (num_cameras, NRF_CAMERA_ROW) -> d_deltas (num_cameras, NRF_CAMERA_DELTA_ROW), OVERWRITTEN. */
+int nrf_camera_table_compose_backward(const float* cameras, const float* deltas, int32_t num_cameras, const float* d_cameras,
+                                      float* d_deltas, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,9 +27,10 @@ whole chain of a pose / intrinsics / lens refinement:
     table.grad                                                             # (C, 24); the two pads of a row stay 0
 
 The distortion coefficients of a camera whose coefficients are all zero receive a gradient as well, so a lens
-correction can be learned from zero.  Out of scope: a table form of pixels_to_points, camera gradients through the fused
-`loss_and_grad`, the bf16 modes (ray gradients are float32 only), a rotation parametrisation (map your own 3-vector to the nine
-orientation entries in torch)."""
+correction can be learned from zero.  `CameraComposeFunction` (nerfies_amd.camera.compose_cameras) maps a per-camera delta table
+(rotation vector, translation, log focal, principal point, distortion) onto a camera table, differentiably in the deltas; the fused
+train step with ray gradients is `NerfModel.loss_and_grad(..., ray_grads=...)` / `training.train_step(cameras=...)`.  Out of scope: a
+table form of pixels_to_points, the bf16 modes (ray gradients are float32 only)."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -269,3 +270,40 @@ def camera_project(table, points, camera_index=None):
   """nerfies_amd.camera.project_from_table."""
   table, pts, idx, batch = _table_args(table, points, 3, camera_index)
   return CameraProjectFunction.apply(table, pts, idx).reshape(batch + (2,))
+
+
+class CameraComposeFunction(torch.autograd.Function):
+  """(table (C,24), deltas (C,16)) -> the composed table (C,24): nrf_camera_table_compose; backward: one
+  nrf_camera_table_compose_backward call into the deltas (the base table carries no gradient)."""
+
+  @staticmethod
+  def forward(ctx, table, deltas):
+    lib = L.load_library()
+    table, deltas = table.detach().contiguous(), deltas.detach().contiguous()
+    out = torch.empty_like(table)
+    with torch.cuda.device(table.device):
+      L.check(lib.nrf_camera_table_compose(table.data_ptr(), deltas.data_ptr(), table.shape[0], out.data_ptr(),
+                                           torch.cuda.current_stream().cuda_stream), lib)
+    ctx.save_for_backward(table, deltas)
+    return out
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, d_out):
+    table, deltas = ctx.saved_tensors
+    lib = L.load_library()
+    d_out = d_out.contiguous().float()
+    d_deltas = torch.empty_like(deltas)
+    with torch.cuda.device(table.device):
+      L.check(lib.nrf_camera_table_compose_backward(table.data_ptr(), deltas.data_ptr(), table.shape[0], d_out.data_ptr(),
+                                                    d_deltas.data_ptr(), torch.cuda.current_stream().cuda_stream), lib)
+    return None, d_deltas
+
+
+def camera_compose(table, deltas):
+  """nerfies_amd.camera.compose_cameras."""
+  if table.dim() != 2 or table.shape[1] != L.NRF_CAMERA_ROW or table.dtype != torch.float32 or not table.is_cuda:
+    raise ValueError(f'a camera table is a float32 CUDA tensor (C, {L.NRF_CAMERA_ROW}) (see pack_cameras)')
+  if tuple(deltas.shape) != (table.shape[0], L.NRF_CAMERA_DELTA_ROW) or deltas.dtype != torch.float32 or deltas.device != table.device:
+    raise ValueError(f'a delta table is a float32 tensor ({table.shape[0]}, {L.NRF_CAMERA_DELTA_ROW}) on the device of the camera table')
+  return CameraComposeFunction.apply(table, deltas)

@@ -33,6 +33,12 @@ CAMERA_PARAM_SLICES = {
     'tangential_distortion': slice(20, 22)}
 
 
+# name -> slice of a camera delta row (include/nerfies_amd.h, NRF_CAMERA_DELTA_ROW); floats 14, 15 of a row are pads
+CAMERA_DELTA_SLICES = {
+    'rotation': slice(0, 3), 'translation': slice(3, 6), 'log_focal': slice(6, 7), 'principal_point': slice(7, 9),
+    'radial_distortion': slice(9, 12), 'tangential_distortion': slice(12, 14)}
+
+
 class Camera:
   """Pinhole camera with skew, pixel aspect ratio and Brown-Conrady distortion (camera.py:108-140)."""
 
@@ -253,3 +259,12 @@ def project_from_table(table, points, camera_index=None):
   Differentiable in `table`, and in `points` when they require grad."""
   from . import autograd
   return autograd.camera_project(table, points, camera_index)
+
+
+def compose_cameras(table, deltas):
+  """The camera table (C, 24) that `deltas` (C, 16) make of `table` (nrf_camera_table_compose): per row R = exp(hat omega) R0 (the
+  camera turns in its own frame), position + t, focal_length * exp(s), principal point and distortion coefficients added; columns
+  as CAMERA_DELTA_SLICES.  Zero deltas reproduce the table.  Differentiable in `deltas` (exact at omega = 0); the base table is a
+  constant."""
+  from . import autograd
+  return autograd.camera_compose(table, deltas)

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "nrf_internal.h"
+#include "se3_math.h"
 
 namespace nrf {
 namespace {
@@ -472,7 +473,69 @@ __global__ __launch_bounds__(CAM_THREADS) void camera_table_reduce_kernel(TableW
   if (threadIdx.x < NRF_CAMERA_ROW) d_cameras[(long)cam * NRF_CAMERA_ROW + threadIdx.x] = threadIdx.x < NP ? r : 0.f;
 }
 
+// ---- camera delta tables (nrf_camera_table_compose*): one thread per camera.  The rotation is the SE3 field's closed form with
+// v = 0 on the columns of R0 (se3_math.h: the theta^2 series below |omega|^2 = 0.04), so value and VJP are exact at omega = 0.
+constexpr int ND = NRF_CAMERA_DELTA_ROW;
+
+__global__ __launch_bounds__(CAM_THREADS) void camera_compose_kernel(const float* __restrict__ cameras, const float* __restrict__ deltas,
+                                                                     int num_cameras, float* __restrict__ out) {
+  const int cam = blockIdx.x * CAM_THREADS + threadIdx.x;
+  if (cam >= num_cameras) return;
+  const float* __restrict__ b = cameras + (long)cam * NRF_CAMERA_ROW;
+  const float* __restrict__ d = deltas + (long)cam * ND;
+  float* __restrict__ o = out + (long)cam * NRF_CAMERA_ROW;
+  const V3 w = v3(d[0], d[1], d[2]), zero = v3(0.f, 0.f, 0.f);
+  const Se3Coef<float> k = se3_coef<float>(dot(w, w));
+  for (int j = 0; j < 3; ++j) {   // column j of R0 (row-major orientation[3 i + j])
+    const V3 c = v3(b[j], b[3 + j], b[6 + j]);
+    const V3 r = c + se3_delta_c<float>(k, w, zero, c);
+    o[j] = r.x; o[3 + j] = r.y; o[6 + j] = r.z;
+  }
+  for (int i = 0; i < 3; ++i) o[9 + i] = b[9 + i] + d[3 + i];
+  o[12] = b[12] * expf(d[6]);
+  o[13] = b[13] + d[7]; o[14] = b[14] + d[8];
+  o[15] = b[15]; o[16] = b[16];
+  for (int i = 0; i < 5; ++i) o[17 + i] = b[17 + i] + d[9 + i];   // radial [3], tangential [2]
+  o[22] = 0.f; o[23] = 0.f;
+}
+
+__global__ __launch_bounds__(CAM_THREADS) void camera_compose_bwd_kernel(const float* __restrict__ cameras, const float* __restrict__ deltas,
+                                                                         int num_cameras, const float* __restrict__ d_cameras,
+                                                                         float* __restrict__ d_deltas) {
+  const int cam = blockIdx.x * CAM_THREADS + threadIdx.x;
+  if (cam >= num_cameras) return;
+  const float* __restrict__ b = cameras + (long)cam * NRF_CAMERA_ROW;
+  const float* __restrict__ d = deltas + (long)cam * ND;
+  const float* __restrict__ g = d_cameras + (long)cam * NRF_CAMERA_ROW;
+  float* __restrict__ o = d_deltas + (long)cam * ND;
+  const V3 w = v3(d[0], d[1], d[2]), zero = v3(0.f, 0.f, 0.f);
+  const Se3Coef<float> k = se3_coef<float>(dot(w, w));
+  V3 dw = zero;
+  for (int j = 0; j < 3; ++j) {
+    V3 dwj, dvj;
+    se3_vjp_c<float>(k, w, zero, v3(b[j], b[3 + j], b[6 + j]), v3(g[j], g[3 + j], g[6 + j]), dwj, dvj);
+    dw = dw + dwj;
+  }
+  o[0] = dw.x; o[1] = dw.y; o[2] = dw.z;
+  for (int i = 0; i < 3; ++i) o[3 + i] = g[9 + i];
+  o[6] = g[12] * b[12] * expf(d[6]);
+  o[7] = g[13]; o[8] = g[14];
+  for (int i = 0; i < 5; ++i) o[9 + i] = g[17 + i];
+  o[14] = 0.f; o[15] = 0.f;
+}
+
 }  // namespace
+
+void launch_camera_compose(const float* cameras, const float* deltas, int num_cameras, float* out, hipStream_t stream) {
+  camera_compose_kernel<<<(unsigned)((num_cameras + CAM_THREADS - 1) / CAM_THREADS), CAM_THREADS, 0, stream>>>(cameras, deltas,
+                                                                                                              num_cameras, out);
+}
+
+void launch_camera_compose_backward(const float* cameras, const float* deltas, int num_cameras, const float* d_cameras, float* d_deltas,
+                                    hipStream_t stream) {
+  camera_compose_bwd_kernel<<<(unsigned)((num_cameras + CAM_THREADS - 1) / CAM_THREADS), CAM_THREADS, 0, stream>>>(
+      cameras, deltas, num_cameras, d_cameras, d_deltas);
+}
 
 void launch_camera_rays(const CameraArgs& c, const float* pixels, const float* depth, long n, float* origins,
                         float* directions, float* pixels_out, hipStream_t stream) {

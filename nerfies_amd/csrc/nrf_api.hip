@@ -245,15 +245,12 @@ int nrf_train_step_loss_grad(nrf_handle h, const float* params, const nrf_rays* 
   return backward_impl(h, params, rays, nullptr, target_rgb, grad_params, stats, (float*)workspace, (hipStream_t)stream);
 }
 
-int nrf_train_step_loss_grad_ex(nrf_handle h, const float* params, const nrf_rays* rays, const float* target_rgb,
-                                const nrf_step_scalars* scalars, const nrf_rand* rnd, const nrf_background* bg,
-                                const nrf_elastic* el, const nrf_warp_reg* wr, uint32_t flags, float* grad_params, float* stats,
-                                void* workspace, size_t workspace_bytes, void* stream) {
-  if (!h || !target_rgb || !grad_params) return fail(NRF_E_NULL, "null argument");
-  if (flags & NRF_FLAG_RAY_GRADS)
-    return fail(NRF_E_UNSUPPORTED, "NRF_FLAG_RAY_GRADS: the fused train step has a fixed loss and no ray gradient; use nrf_forward + nrf_backward_rays");
-  if (flags & ~(uint32_t)(NRF_FLAG_BF16 | NRF_FLAG_WARP_F32)) return fail(NRF_E_UNSUPPORTED, "nrf_train_step_loss_grad_ex flags: 0, NRF_FLAG_BF16 [| NRF_FLAG_WARP_F32]");
-  CK(check_flags(h, NRF_FLAG_TRAIN | flags));   // the same word nrf_workspace_bytes_ex validated (WARP_F32 without BF16 is refused here too)
+// nrf_train_step_loss_grad_ex / _rays behind their own flag checks: the regularisers' validation, forward, reverse.  `flags`: the
+// forward's whole word; rg: the ray gradients to write, or nullptr
+static int train_step_ex(nrf_handle h, const float* params, const nrf_rays* rays, const float* target_rgb,
+                         const nrf_step_scalars* scalars, const nrf_rand* rnd, const nrf_background* bg, const nrf_elastic* el,
+                         const nrf_warp_reg* wr, uint32_t flags, const nrf_ray_grads* rg, float* grad_params, float* stats,
+                         void* workspace, size_t workspace_bytes, void* stream) {
   int bgN = 0;
   if (el) {
     if (!h->warp) return fail(NRF_E_UNSUPPORTED, "the elastic regulariser needs the warp field");
@@ -273,10 +270,41 @@ int nrf_train_step_loss_grad_ex(nrf_handle h, const float* params, const nrf_ray
     if (!scalars) return fail(NRF_E_NULL, "nrf_step_scalars required");
     bgN = bg->num_points;
   }
-  CK(forward_impl(h, params, rays, scalars, rnd, nullptr, NRF_FLAG_TRAIN | flags, (float*)workspace, workspace_bytes,
-                  (hipStream_t)stream, bgN, el ? 1 : 0, bgN > 0 ? bg : nullptr));
+  CK(forward_impl(h, params, rays, scalars, rnd, nullptr, flags, (float*)workspace, workspace_bytes, (hipStream_t)stream, bgN,
+                  el ? 1 : 0, bgN > 0 ? bg : nullptr));
   return backward_impl(h, params, rays, nullptr, target_rgb, grad_params, stats, (float*)workspace, (hipStream_t)stream,
-                       bgN > 0 ? bg : nullptr, scalars, el, wr, /*bg_forward_done=*/bgN > 0);
+                       bgN > 0 ? bg : nullptr, scalars, el, wr, /*bg_forward_done=*/bgN > 0, rg);
+}
+
+int nrf_train_step_loss_grad_ex(nrf_handle h, const float* params, const nrf_rays* rays, const float* target_rgb,
+                                const nrf_step_scalars* scalars, const nrf_rand* rnd, const nrf_background* bg,
+                                const nrf_elastic* el, const nrf_warp_reg* wr, uint32_t flags, float* grad_params, float* stats,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  if (!h || !target_rgb || !grad_params) return fail(NRF_E_NULL, "null argument");
+  if (flags & NRF_FLAG_RAY_GRADS)
+    return fail(NRF_E_UNSUPPORTED, "NRF_FLAG_RAY_GRADS: nrf_train_step_loss_grad_ex has no ray gradient; use nrf_train_step_loss_grad_rays "
+                                   "(or nrf_forward + nrf_backward_rays)");
+  if (flags & ~(uint32_t)(NRF_FLAG_BF16 | NRF_FLAG_WARP_F32)) return fail(NRF_E_UNSUPPORTED, "nrf_train_step_loss_grad_ex flags: 0, NRF_FLAG_BF16 [| NRF_FLAG_WARP_F32]");
+  CK(check_flags(h, NRF_FLAG_TRAIN | flags));   // the same word nrf_workspace_bytes_ex validated (WARP_F32 without BF16 is refused here too)
+  return train_step_ex(h, params, rays, target_rgb, scalars, rnd, bg, el, wr, NRF_FLAG_TRAIN | flags, nullptr, grad_params, stats,
+                       workspace, workspace_bytes, stream);
+}
+
+int nrf_train_step_loss_grad_rays(nrf_handle h, const float* params, const nrf_rays* rays, const float* target_rgb,
+                                  const nrf_step_scalars* scalars, const nrf_rand* rnd, const nrf_background* bg,
+                                  const nrf_elastic* el, const nrf_warp_reg* wr, uint32_t flags, const nrf_ray_grads* ray_grads,
+                                  float* grad_params, float* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!h || !target_rgb || !grad_params) return fail(NRF_E_NULL, "null argument");
+  if (!ray_grads) return fail(NRF_E_NULL, "nrf_ray_grads is null (nrf_train_step_loss_grad_ex is the step without ray gradients)");
+  if (flags)
+    return fail(NRF_E_UNSUPPORTED, "nrf_train_step_loss_grad_rays flags: 0 (the float32 mode only: no NRF_FLAG_BF16, NRF_FLAG_BF16X3 or "
+                                   "NRF_FLAG_WARP_F32; NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS are implied)");
+  if (ray_grads->d_viewdirs && rays && (!h->d.use_viewdirs || !rays->viewdirs || h->V > 64))
+    return fail(NRF_E_UNSUPPORTED, "nrf_ray_grads.d_viewdirs needs a model with use_viewdirs (at most 64 encoded columns) and rays->viewdirs "
+                                   "(without them the view term is part of d_directions)");
+  CK(check_flags(h, NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS));
+  return train_step_ex(h, params, rays, target_rgb, scalars, rnd, bg, el, wr, NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS, ray_grads,
+                       grad_params, stats, workspace, workspace_bytes, stream);
 }
 
 int nrf_workspace_bytes_ex(nrf_handle h, int32_t num_rays, uint32_t flags, int32_t num_background_points,
@@ -286,8 +314,6 @@ int nrf_workspace_bytes_ex(nrf_handle h, int32_t num_rays, uint32_t flags, int32
   if ((num_background_points > 0 || use_elastic_loss) && !h->warp)
     return fail(NRF_E_UNSUPPORTED, "the background / elastic regularisers need the warp field");
   CK(check_flags(h, flags));
-  if ((flags & NRF_FLAG_RAY_GRADS) && (num_background_points > 0 || use_elastic_loss))
-    return fail(NRF_E_UNSUPPORTED, "NRF_FLAG_RAY_GRADS: the regularisers belong to the fused train step, which has no ray gradient");
   query_device(h);
   const bool tr = flags & NRF_FLAG_TRAIN;
   build_plan(h, num_rays, flags, tr ? num_background_points : 0, tr && use_elastic_loss ? 1 : 0);
@@ -686,6 +712,25 @@ int nrf_camera_table_project_backward(const float* cameras, int32_t num_cameras,
   launch_camera_table_project_backward(cameras, num_cameras, camera_index, points, (long)n, d_pixels, d_cameras, d_points, workspace,
                                        (hipStream_t)stream);
   return check_launch("nrf_camera_table_project_backward");
+}
+
+int nrf_camera_table_compose(const float* cameras, const float* deltas, int32_t num_cameras, float* out, void* stream) {
+  CK(table_args(cameras, num_cameras, 0));
+  if (!deltas || !out) return fail(NRF_E_NULL, "deltas / out is null");
+  if (!aligned16(deltas) || !aligned16(out)) return fail(NRF_E_SHAPE, "the delta table and the output table must be 16-byte aligned");
+  if (out == cameras) return fail(NRF_E_SHAPE, "out may not alias cameras");
+  launch_camera_compose(cameras, deltas, num_cameras, out, (hipStream_t)stream);
+  return check_launch("nrf_camera_table_compose");
+}
+
+int nrf_camera_table_compose_backward(const float* cameras, const float* deltas, int32_t num_cameras, const float* d_cameras,
+                                      float* d_deltas, void* stream) {
+  CK(table_args(cameras, num_cameras, 0));
+  if (!deltas || !d_cameras || !d_deltas) return fail(NRF_E_NULL, "deltas / d_cameras / d_deltas is null");
+  if (!aligned16(deltas) || !aligned16(d_cameras) || !aligned16(d_deltas))
+    return fail(NRF_E_SHAPE, "the delta table and the gradient tables must be 16-byte aligned");
+  launch_camera_compose_backward(cameras, deltas, num_cameras, d_cameras, d_deltas, (hipStream_t)stream);
+  return check_launch("nrf_camera_table_compose_backward");
 }
 
 }  // extern "C"

@@ -125,6 +125,9 @@ struct WsPlan {
   int grid_mlp_bwd = 0;  // NeRF chains, tiles of all levels: small_part[grid_mlp_bwd][SMALL_PART] per level
   int grid_warp_bwd = 0; // SE3 chain, coarse + fine + background tiles: w_small_part[grid_warp_bwd][WARP_SMALL_PART]
   int rg_L0T = 0, rg_L4bT = 0;   // NRF_FLAG_RAY_GRADS plan of a model without a warp field: PackOffsets::bwd_L0T / bwd_L4bT inside rg_wpkT
+  // NRF_FLAG_RAY_GRADS next to the elastic regulariser: the fine level's Jacobian pass has a tangent stash of its own
+  // (wpoints, w_st_win, w_st_h, w_st_wv of 3 x the fine tiles; no wgrad group, reduce entry or reverse launch reads it)
+  LevelWs rg_tan_fine;
   int tg_tiles_per = 0;  // primal tiles one tangent pass covers (elastic: coarse level; Jacobian output: the larger level)
   size_t total_floats;
   std::vector<PackDesc> pack;

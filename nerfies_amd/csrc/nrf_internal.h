@@ -509,6 +509,7 @@ struct RayGradArgs {
   float* d_origins;           // [B][3], each may be nullptr: that part is skipped
   float* d_directions;
   float* d_viewdirs;
+  int fold_viewdirs;          // the condition read the directions (rays->viewdirs == NULL): d_directions += the d_viewdirs term
 };
 void launch_ray_grad(const RayGradArgs& a, hipStream_t stream);
 // d_points[rows][3] += d_warped[rows][3]: the caller's cotangent of the warped points (nrf_backward_ex), ahead of the SE3 dgrad
@@ -604,5 +605,9 @@ void launch_camera_table_rays_backward(const float* cameras, int num_cameras, co
 void launch_camera_table_project_backward(const float* cameras, int num_cameras, const int* camera_index, const float* points, long n,
                                           const float* d_pixels, float* d_cameras, float* d_points, void* workspace,
                                           hipStream_t stream);
+// camera delta tables (C, NRF_CAMERA_DELTA_ROW): out row = base row with the delta applied (R = exp(hat omega) R0, ...), and its VJP
+void launch_camera_compose(const float* cameras, const float* deltas, int num_cameras, float* out, hipStream_t stream);
+void launch_camera_compose_backward(const float* cameras, const float* deltas, int num_cameras, const float* d_cameras, float* d_deltas,
+                                    hipStream_t stream);
 
 }  // namespace nrf

@@ -517,7 +517,13 @@ void Planner::shapes() {
   // ONE dgrad launch over the tiles of all levels: two workgroups per CU on 64-row tiles, four on 32-row half tiles
   p.grid_mlp_bwd = p.bwd32 ? tile_grid(2 * nt_mlp, 4, G) : tile_grid(nt_mlp, 2, G);
   p.grid_warp_bwd = tile_grid(nt_mlp + p.ntiles[BG], warp_grid_mul(), G);   // ONE SE3 dgrad launch: + the background tiles (0 without that batch)
-  p.tg_tiles_per = jac || (rg && h->warp) ? p.ntiles[h->nlevels - 1] : k.elastic ? p.ntiles[0] : 0;   // Jacobian output / ray gradients: levels run one after the other
+  // Jacobian output / ray gradients: levels run one after the other.  Ray gradients next to the elastic regulariser: TG stays the
+  // COARSE tangent level (the regulariser's reverse pass and the TG wgrad groups read it after the forward), the fine level's
+  // Jacobian pass gets a scratch of its own (ray_grad_buffers)
+  p.tg_tiles_per = rg && h->warp && k.elastic ? p.ntiles[0]
+                   : jac || (rg && h->warp)   ? p.ntiles[h->nlevels - 1]
+                   : k.elastic                ? p.ntiles[0]
+                                              : 0;
   p.ntiles[TG] = 3 * p.tg_tiles_per;
   p.rows[TG] = p.ntiles[TG] * TILE_ROWS;
 }
@@ -862,6 +868,14 @@ void Planner::ray_grad_buffers() {
     }
   }
   if (!h->warp) return;
+  if (p.key.elastic) {   // TG is the elastic regulariser's (buffers()) and serves the coarse Jacobian; the fine pass runs beside it
+    if (h->nlevels < 2) return;
+    LevelWs& F = p.rg_tan_fine;
+    const size_t nt = (size_t)3 * p.ntiles[1];
+    F.wpoints = take(nt * TILE_ROWS * 3);
+    take_warp_stash(F, nt);
+    return;
+  }
   // the tangent pass of one level at a time (as the inference Jacobian plan): its input / activation / (w, v) stash
   LevelWs& T = p.L[TG];
   const size_t nt = p.ntiles[TG];

@@ -250,8 +250,11 @@ struct Forward : Run {
     pf.end(stream);
   }
   // forward-mode pass of the warp Jacobian of level lv (warping.py:385-387): 3 tangent tiles per primal tile
+  // the stash a tangent pass of level lv writes: TG, or -- ray gradients next to the elastic regulariser, whose reverse pass and
+  // wgrad groups keep reading the coarse tangents in TG -- the fine level's scratch (Planner::ray_grad_buffers)
+  const LevelWs& tangent_level(int lv) const { return m.ray_grads && p.key.elastic && lv > 0 ? p.rg_tan_fine : p.L[TG]; }
   void tangent_fwd(int lv) {
-    const LevelWs &L = p.L[lv], &T = p.L[TG];
+    const LevelWs &L = p.L[lv], &T = tangent_level(lv);
     WarpFwdArgs ta = warp_fwd_args(lv);
     ta.nt_prim = p.ntiles[lv]; ta.prim_win = ws + L.w_st_win; ta.prim_bits = u32(L.w_bits);
     ta.ntiles = 3 * p.ntiles[lv]; ta.rows = ta.ntiles * TILE_ROWS;
@@ -267,7 +270,8 @@ struct Forward : Run {
   // forward-mode Jacobian of the warp: on the coarse samples for the elastic regulariser (models.py:345), per level
   // as an output (return_warp_jacobian, models.py:345-346, 367-368)
   // ... and per level into the workspace for nrf_backward_rays (NRF_FLAG_RAY_GRADS: the tangent pass runs in the forward, right
-  // behind the primal pass whose (alpha, codes) it shares; the levels take turns on the one tangent stash)
+  // behind the primal pass whose (alpha, codes) it shares; the levels take turns on the one tangent stash, except next to the
+  // elastic regulariser: tangent_level)
   void jacobian(int lv) {
     float* jout = !out ? nullptr : lv == 0 ? out->coarse.warp_jacobian : out->fine.warp_jacobian;
     if (m.ray_grads) jout = ws + p.L[lv].rg_jac;
@@ -275,7 +279,7 @@ struct Forward : Run {
     if (!(m.jac || m.ray_grads) || !jout) return;
     JacobianArgs ja;
     memset(&ja, 0, sizeof(ja));   // x_rows = nullptr: the points come from the fp32 input stash
-    ja.prim_win = ws + p.L[lv].w_st_win; ja.prim_wv = f4(p.L[lv].w_st_wv); ja.tan_wv = f4(p.L[TG].w_st_wv); ja.out = jout;
+    ja.prim_win = ws + p.L[lv].w_st_win; ja.prim_wv = f4(p.L[lv].w_st_wv); ja.tan_wv = f4(tangent_level(lv).w_st_wv); ja.out = jout;
     ja.rows = p.rows[lv]; ja.rows_pad = rows_pad(lv); ja.PKS = pks();
     launch_jacobian(ja, stream);
   }
@@ -352,6 +356,7 @@ struct Forward : Run {
 struct Backward : Run {
   const nrf_elastic* el;  const nrf_warp_reg* wr;  const bool el_on, wr_on;
   const nrf_ray_grads* rg = nullptr;   // nrf_backward_rays: the ray gradients to write (the stash was kept under NRF_FLAG_RAY_GRADS)
+  bool fold_viewdirs = false;          // nrf_train_step_loss_grad_rays: rays->viewdirs == NULL adds the view term to d_directions
   const nrf_output_grads* og;   // the caller's cotangents (nrf_backward[_ex]) or nullptr (fused step: the MSE loss against `target`)
   float* grad = nullptr;   // INTERNAL layout, as params
   double mlp_rows = 0;     // samples of all levels
@@ -465,11 +470,15 @@ struct Backward : Run {
     launch_elastic(ea, stream);
     pf.end(stream);
   }
-  // the caller's and the regularisers' gradients w.r.t. the warped points, added into d_points ahead of the SE3 dgrad
-  void point_regularisers() {
+  // The caller's and the regularisers' gradients w.r.t. the warped points, added into d_points ahead of the SE3 dgrad, in two
+  // parts around the ray stage: the caller's cotangent reaches the rays, the regularisers' terms do not (they regularise the field;
+  // nrf_train_step_loss_grad_rays treats their dependence on the sample positions as stop-gradient)
+  void point_cotangents() {
     for (int lv = 0; lv < h->nlevels && m.warp_on; ++lv)   // nrf_backward_ex: the caller's own d loss / d warped point
       if (const nrf_level_grads* g = level_grads(lv))
         if (g->d_warped_points) launch_add_point_cotangent(g->d_warped_points, p.rows[lv], ws + p.L[lv].d_points, stream);
+  }
+  void point_regularisers() {
     if (el_on) elastic();
     if (wr_on)   // use_warp_reg_loss (training.py:199-212): + d loss / d warped point at the median-depth sample of each ray
       for (int lv = 0; lv < h->nlevels; ++lv) {
@@ -493,6 +502,7 @@ struct Backward : Run {
       a.dray[lv] = ws + L.dray; a.sdsig[lv] = ws + L.rg_sdsig; a.rgbh_k[lv] = h->po[lv].rgbh_k; a.S[lv] = p.S[lv];
     }
     a.params = params; a.dirs = rays->directions; a.viewdirs = rays->viewdirs;
+    a.fold_viewdirs = fold_viewdirs && d.use_viewdirs && !rays->viewdirs;
     a.B = B; a.nlevels = h->nlevels; a.V = h->V; a.Fv = d.num_nerf_viewdir_freqs;
     a.d_origins = rg->d_origins; a.d_directions = rg->d_directions; a.d_viewdirs = rg->d_viewdirs;
     pf.begin("ray_grads", 0, stream);
@@ -647,7 +657,10 @@ int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, con
                   const nrf_step_scalars* scalars, const nrf_elastic* el, const nrf_warp_reg* wr, bool bg_forward_done,
                   const nrf_ray_grads* rg) {
   Backward b(Run(h, h->stashed_modes, ws, stream, rays, scalars, bg), el, wr, og);
-  if (rg && (rg->d_origins || rg->d_directions || rg->d_viewdirs)) b.rg = rg;   // nothing asked for: the stage (and its inputs) are skipped
+  // nothing asked for: the stage (and its inputs) are skipped
+  if (rg && (rg->d_origins || rg->d_directions || rg->d_viewdirs)) b.rg = rg;
+  // the fused step's ray gradients: with rays->viewdirs NULL the view term is folded into d_directions
+  b.fold_viewdirs = og == nullptr && rg != nullptr;
   // the gradient buffer is zero-filled and accumulated into with 16-byte accesses (zero_ranges_kernel, reduce passes)
   if ((reinterpret_cast<uintptr_t>(grad_x) & 15u) != 0) return fail(NRF_E_SHAPE, "grad_params must be 16-byte aligned");
   // p.bwd32 alone selects the 32-row reverse path (zeroed slices and launch); that kernel has no d-points output
@@ -662,8 +675,9 @@ int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, con
   CK(b.zero());
   b.composite_bwd(target);
   b.mlp_dgrad();
-  b.point_regularisers();
+  b.point_cotangents();
   if (b.rg) b.ray_grads();
+  b.point_regularisers();   // behind the ray stage: launch_warp_reg adds into d_points
   if (b.m.warp_on) b.warp_dgrad();
   b.cond_grads();
   if (b.m.warp_on && h->time_enc) {   // reverse of the TimeEncoder: d codes -> its six layers' weight gradients

@@ -390,7 +390,11 @@ __global__ __launch_bounds__(256) void ray_grad_kernel(const RayGradArgs A) {
       }
     }
   }
-  if (A.d_viewdirs) {
+  // fold_viewdirs (nrf_train_step_loss_grad_rays, rays->viewdirs == NULL): the condition read the directions, so what would have
+  // gone to d_viewdirs is added to d_directions by the lane that wrote it above (one wave owns the ray: a fixed order)
+  const bool fold = A.fold_viewdirs && A.d_directions;
+  if (A.d_viewdirs || fold) {
+    const float* __restrict__ vdirs = A.viewdirs ? A.viewdirs : A.dirs;
     // lanes over the RGB_W = 2 x 64 adjoints of each level (coalesced rows of W and of dray), one wave_sum per condition column;
     // lane c keeps column c's sum
     float d0[2] = {0.f, 0.f}, d1[2] = {0.f, 0.f};
@@ -420,14 +424,15 @@ __global__ __launch_bounds__(256) void ray_grad_kernel(const RayGradArgs A) {
         const int q = lane - 3, f = q / 6, rem = q - 6 * f, is_cos = rem / 3;
         comp = rem - 3 * is_cos;
         const float sc = (float)(1 << f);
-        float a = __fmul_rn(A.viewdirs[3 * ray + comp], sc);
+        float a = __fmul_rn(vdirs[3 * ray + comp], sc);
         if (is_cos) a = __fadd_rn(a, 1.57079632679489661923f);
         coef = sc * cosf(a);
       }
     }
     const float t = dc * coef;
     const float v0 = wave_sum(comp == 0 ? t : 0.f), v1 = wave_sum(comp == 1 ? t : 0.f), v2 = wave_sum(comp == 2 ? t : 0.f);
-    if (lane == 0) { A.d_viewdirs[3 * ray] = v0; A.d_viewdirs[3 * ray + 1] = v1; A.d_viewdirs[3 * ray + 2] = v2; }
+    if (lane == 0 && A.d_viewdirs) { A.d_viewdirs[3 * ray] = v0; A.d_viewdirs[3 * ray + 1] = v1; A.d_viewdirs[3 * ray + 2] = v2; }
+    if (lane == 0 && fold) { A.d_directions[3 * ray] += v0; A.d_directions[3 * ray + 1] += v1; A.d_directions[3 * ray + 2] += v2; }
   }
 }
 

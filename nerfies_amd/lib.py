@@ -16,6 +16,7 @@ NRF_FLAG_RAY_GRADS = 64
 NRF_NUM_STATS = 16
 NRF_CAMERA_ROW = 24       # floats per row of a camera table
 NRF_CAMERA_NPARAMS = 22   # of which differentiable parameters (the rest: pads)
+NRF_CAMERA_DELTA_ROW = 16 # floats per row of a camera delta table (nrf_camera_table_compose)
 ACT = {'relu': 0, 'softplus': 1}
 WARP_FIELD = {'se3': 0, 'translation': 1}
 META_ENCODER = {'glo': 0, 'time': 1}
@@ -140,6 +141,7 @@ EXPORTS = [
     'nrf_backward_rays',
     'nrf_camera_table_rays', 'nrf_camera_table_project', 'nrf_camera_table_workspace_bytes', 'nrf_camera_table_rays_backward',
     'nrf_camera_table_project_backward',
+    'nrf_train_step_loss_grad_rays', 'nrf_camera_table_compose', 'nrf_camera_table_compose_backward',
 ]
 
 _lib = None
@@ -190,6 +192,9 @@ def load_library(path=None):
       'nrf_train_step_loss_grad_ex': [vp, vp, C.POINTER(Rays), vp, C.POINTER(StepScalars), C.POINTER(Rand),
                                       C.POINTER(Background), C.POINTER(Elastic), C.POINTER(WarpReg), u32, vp, vp, vp,
                                       C.c_size_t, vp],
+      'nrf_train_step_loss_grad_rays': [vp, vp, C.POINTER(Rays), vp, C.POINTER(StepScalars), C.POINTER(Rand),
+                                        C.POINTER(Background), C.POINTER(Elastic), C.POINTER(WarpReg), u32, C.POINTER(RayGrads),
+                                        vp, vp, vp, C.c_size_t, vp],
       'nrf_workspace_bytes_ex': [vp, i32, u32, i32, i32, C.POINTER(C.c_size_t)],
       'nrf_warp_points_workspace_bytes': [vp, i32, C.POINTER(C.c_size_t)],
       'nrf_warp_points': [vp, vp, vp, vp, i32, C.POINTER(StepScalars), vp, vp, C.c_size_t, vp],
@@ -201,6 +206,8 @@ def load_library(path=None):
       'nrf_camera_table_workspace_bytes': [i64, i32, C.POINTER(C.c_size_t)],
       'nrf_camera_table_rays_backward': [vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, C.c_size_t, vp],
       'nrf_camera_table_project_backward': [vp, i32, vp, vp, i64, vp, vp, vp, vp, C.c_size_t, vp],
+      'nrf_camera_table_compose': [vp, vp, i32, vp, vp],
+      'nrf_camera_table_compose_backward': [vp, vp, i32, vp, vp, vp],
   }
   for name, argtypes in sigs.items():
     fn = getattr(lib, name)

@@ -507,7 +507,7 @@ class NerfModel:
     return og, keep
 
   def loss_and_grad(self, fp: P.FlatParams, batch, warp_extra=None, rngs=None, grad_out=None, stats_out=None,
-                    background=None, elastic=None, warp_reg=None, bf16=False, dynamic=None):
+                    background=None, elastic=None, warp_reg=None, bf16=False, dynamic=None, ray_grads=None, ray_grads_out=None):
     """forward + MSE_coarse + MSE_fine [+ background regulariser] + backward in one library call
     (training.py:168-265).  `background` = dict(points (N,3) already noised, warp_ids (N,), weight, alpha=-2,
     scale=1e-3) adds weight * mean(general_loss(|warp(x) - x|^2)) (training.py:117-135, 248-259).
@@ -519,7 +519,13 @@ class NerfModel:
     on the coarse samples (training.py:71-114, 177-197); `loss_type` in lib.ELASTIC_TYPE.  `warp_reg` = dict(weight,
     alpha=-2, scale=1e-3): training.py:199-212 on both levels.  `bf16`: bfloat16 MLP operands (NRF_FLAG_BF16).
     stats (lib.NRF_NUM_STATS floats) = [mse_c, mse_f, psnr_c, psnr_f, total, background_loss, loss/elastic,
-    residual/elastic, warp_reg_c, warp_reg_f, warp_reg residual c, f, jacobian det, div, curl, 0]."""
+    residual/elastic, warp_reg_c, warp_reg_f, warp_reg residual c, f, jacobian det, div, curl, 0].
+    `ray_grads`: an iterable of 'origins' / 'directions' -- the call goes through nrf_train_step_loss_grad_rays (float32 mode
+    only) and returns (grad, stats, {name: (B,3) gradient of MSE_coarse + MSE_fine w.r.t. batch[name]}); the regularisers
+    add nothing to the rays.  A batch without 'viewdirs' on a use_viewdirs model: the view term is part of 'directions'.
+    `ray_grads_out`: {name: (B,3) float32 tensor} to write into instead of fresh tensors."""
+    if ray_grads is not None and bf16:
+      raise L.NrfError('loss_and_grad(ray_grads=...): ray gradients are built for the float32 mode, not with bf16')
     device = fp.flat.device
     rays, keep = self._rays_struct(batch, device)
     rnd, keep2 = self._rand_struct(rngs, rays.num_rays, device)
@@ -555,8 +561,26 @@ class NerfModel:
     wr = None
     if warp_reg is not None:
       wr = L.WarpReg(float(warp_reg.get('weight', 0.0)), float(warp_reg.get('alpha', -2.0)), float(warp_reg.get('scale', 0.001)))
-    ws = self.workspace(rays.num_rays, True, device, nbg, el is not None, bf16=bf16)
+    ws = self.workspace(rays.num_rays, True, device, nbg, el is not None, bf16=bf16, ray_grads=ray_grads is not None)
     stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    if ray_grads is not None:
+      names = tuple(ray_grads)
+      if set(names) - {'origins', 'directions'}:
+        raise L.NrfError(f"loss_and_grad(ray_grads=...): {sorted(names)} -- the fused step returns 'origins' and 'directions'")
+      rg_out = {k: (ray_grads_out or {}).get(k) for k in names}
+      for k in names:
+        if rg_out[k] is None:
+          rg_out[k] = torch.empty(rays.num_rays, 3, device=device)
+        elif tuple(rg_out[k].shape) != (rays.num_rays, 3) or rg_out[k].dtype != torch.float32 or not rg_out[k].is_contiguous():
+          raise L.NrfError(f'loss_and_grad(ray_grads_out=...): {k!r} must be a contiguous float32 ({rays.num_rays}, 3) tensor')
+      rg = L.RayGrads(_ptr(rg_out.get('origins')), _ptr(rg_out.get('directions')), None)
+      L.check(self.lib.nrf_train_step_loss_grad_rays(self.handle, _ptr(fp.flat), C.byref(rays), _ptr(target), C.byref(scal),
+                                                     C.byref(rnd), C.byref(bg) if bg is not None else None,
+                                                     C.byref(el) if el is not None else None,
+                                                     C.byref(wr) if wr is not None else None, 0, C.byref(rg),
+                                                     _ptr(grad), _ptr(stats), _ptr(ws), ws.numel() * 4, stream), self.lib)
+      del keep, keep2, keep3
+      return grad, stats, rg_out
     L.check(self.lib.nrf_train_step_loss_grad_ex(self.handle, _ptr(fp.flat), C.byref(rays), _ptr(target), C.byref(scal),
                                                  C.byref(rnd), C.byref(bg) if bg is not None else None,
                                                  C.byref(el) if el is not None else None,

@@ -168,32 +168,173 @@ def _stats_dict(stats, scalar_params, use_elastic_loss, use_background_loss, use
   return out
 
 
+CAMERA_GROUPS = {   # trainable group -> its columns of a delta row (camera.CAMERA_DELTA_SLICES)
+    'pose': ('rotation', 'translation'), 'focal': ('log_focal',), 'principal_point': ('principal_point',),
+    'distortion': ('radial_distortion', 'tangential_distortion')}
+CAMERA_GROUP_PRESETS = {'pose': ('pose',), 'pose+focal': ('pose', 'focal'), 'all': tuple(CAMERA_GROUPS)}
+
+
+class CameraRefiner:
+  """Per-camera pose / intrinsics deltas trained next to the field (no reference counterpart).  Owns the delta table (C, 16),
+  zeros at the start, its Adam moments (nrf_adam_step on the C * 16 floats; the columns of groups that are not trained get a zero
+  gradient, so they stay exactly zero), the composed table and the camera workspace.  `groups`: 'pose' (rotation and
+  translation), 'pose+focal', 'all', or an iterable of CAMERA_GROUPS names.  Every per-ray step is a library call: compose ->
+  nrf_camera_table_rays -> (the fused step with ray gradients) -> nrf_camera_table_rays_backward -> compose backward."""
+
+  def __init__(self, table0: torch.Tensor, groups='pose', beta1=0.9, beta2=0.999, eps=1e-8):
+    from nerfies_amd import camera as cam
+    if table0.dim() != 2 or table0.shape[1] != L.NRF_CAMERA_ROW or table0.dtype != torch.float32 or not table0.is_cuda:
+      raise ValueError(f'a camera table is a float32 CUDA tensor (C, {L.NRF_CAMERA_ROW}) (see pack_cameras)')
+    names = CAMERA_GROUP_PRESETS.get(groups) if isinstance(groups, str) else tuple(groups)
+    if names is None or set(names) - set(CAMERA_GROUPS) or not names:
+      raise ValueError(f'groups: one of {sorted(CAMERA_GROUP_PRESETS)} or an iterable of {sorted(CAMERA_GROUPS)}, got {groups!r}')
+    self.groups = tuple(names)
+    dev = table0.device
+    self.table0 = table0.detach().clone().contiguous()
+    C_ = self.num_cameras = table0.shape[0]
+    self.deltas = torch.zeros(C_, L.NRF_CAMERA_DELTA_ROW, device=dev)
+    self.m, self.v = torch.zeros_like(self.deltas), torch.zeros_like(self.deltas)
+    self.d_deltas = torch.zeros_like(self.deltas)
+    self.table = torch.empty_like(self.table0)      # the composed table of the current step
+    self.d_table = torch.empty_like(self.table0)
+    mask = torch.zeros(L.NRF_CAMERA_DELTA_ROW)
+    for g in self.groups:
+      for col in CAMERA_GROUPS[g]:
+        mask[cam.CAMERA_DELTA_SLICES[col]] = 1.0
+    self.mask = mask.to(dev)
+    self.step = 0
+    self.beta1, self.beta2, self.eps = beta1, beta2, eps
+    self._rays = {}   # B -> (origins, directions, d_origins, d_directions)
+    self._ws = None
+
+  def _stream(self):
+    return C.c_void_p(torch.cuda.current_stream(self.deltas.device).cuda_stream)
+
+  def compose(self) -> torch.Tensor:
+    """The camera table of the current deltas (nrf_camera_table_compose), in the refiner's own buffer."""
+    lib = L.load_library()
+    L.check(lib.nrf_camera_table_compose(self.table0.data_ptr(), self.deltas.data_ptr(), self.num_cameras, self.table.data_ptr(),
+                                         self._stream()), lib)
+    return self.table
+
+  @staticmethod
+  def _batch_columns(batch):
+    if 'pixels' not in batch or 'item_index' not in batch:
+      raise L.NrfError("camera refinement needs the batch's 'pixels' and 'item_index' (create_ray_table(..., keep_item_index=True))")
+    px = batch['pixels'].reshape(-1, 2)
+    idx = batch['item_index'].reshape(-1)
+    if px.dtype != torch.float32 or idx.dtype != torch.int32 or not px.is_contiguous() or not idx.is_contiguous():
+      raise L.NrfError("'pixels' must be contiguous float32 (B, 2), 'item_index' contiguous int32 (B,) or (B, 1)")
+    return px, idx
+
+  def rays(self, batch):
+    """(origins, directions) of the batch's pixels seen from the composed table (call `compose` first): nrf_camera_table_rays."""
+    lib = L.load_library()
+    px, idx = self._batch_columns(batch)
+    n = px.shape[0]
+    buf = self._rays.get(n)
+    if buf is None:
+      buf = self._rays[n] = tuple(torch.empty(n, 3, device=self.deltas.device) for _ in range(4))
+    L.check(lib.nrf_camera_table_rays(self.table.data_ptr(), self.num_cameras, idx.data_ptr(), px.data_ptr(), n, buf[0].data_ptr(),
+                                      buf[1].data_ptr(), self._stream()), lib)
+    return buf[0], buf[1]
+
+  def ray_grad_buffers(self, n):
+    return {'origins': self._rays[n][2], 'directions': self._rays[n][3]}
+
+  def backward(self, batch, d_origins, d_directions) -> torch.Tensor:
+    """Ray gradients -> d_deltas (C, 16): nrf_camera_table_rays_backward, then nrf_camera_table_compose_backward; the columns of
+    untrained groups are zeroed."""
+    lib = L.load_library()
+    px, idx = self._batch_columns(batch)
+    n = px.shape[0]
+    need = C.c_size_t(0)
+    L.check(lib.nrf_camera_table_workspace_bytes(n, self.num_cameras, C.byref(need)), lib)
+    if self._ws is None or self._ws.numel() < need.value:
+      self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.deltas.device)
+    st = self._stream()
+    L.check(lib.nrf_camera_table_rays_backward(self.table.data_ptr(), self.num_cameras, idx.data_ptr(), px.data_ptr(), n,
+                                               d_origins.data_ptr(), d_directions.data_ptr(), self.d_table.data_ptr(), None,
+                                               self._ws.data_ptr(), self._ws.numel(), st), lib)
+    L.check(lib.nrf_camera_table_compose_backward(self.table0.data_ptr(), self.deltas.data_ptr(), self.num_cameras,
+                                                  self.d_table.data_ptr(), self.d_deltas.data_ptr(), st), lib)
+    self.d_deltas.mul_(self.mask)   # per-camera data, C * 16 floats
+    return self.d_deltas
+
+  def apply_gradient(self, learning_rate: float, grad_scale: float = 1.0):
+    lib = L.load_library()
+    L.check(lib.nrf_adam_step(self.deltas.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.d_deltas.data_ptr(),
+                              self.deltas.numel(), float(learning_rate), self.beta1, self.beta2, self.eps, int(self.step),
+                              float(grad_scale), self._stream()), lib)
+    self.step += 1
+    return self
+
+  def state_dict(self):
+    return {'deltas': self.deltas.cpu().numpy(), 'm': self.m.cpu().numpy(), 'v': self.v.cpu().numpy(), 'step': int(self.step),
+            'groups': list(self.groups)}
+
+  def load_state_dict(self, d):
+    import numpy as np
+    saved = tuple(str(g) for g in d['groups'])
+    if set(saved) != set(self.groups):   # the moments of a newly trained column would be stale, a dropped one would freeze mid-way
+      raise ValueError(f'camera state was saved with groups {sorted(saved)}, this refiner trains {sorted(self.groups)}: '
+                       'resume with the same groups (--refine_cameras) or start the cameras afresh')
+    for name in ('deltas', 'm', 'v'):
+      a = np.asarray(d[name], np.float32)
+      if a.shape != tuple(self.deltas.shape):
+        raise ValueError(f'camera state {name}: shape {a.shape}, expected {tuple(self.deltas.shape)}')
+      getattr(self, name).copy_(torch.from_numpy(a))
+    self.step = int(d['step'])
+    return self
+
+
 def train_step(model: models.NerfModel, rng_key, state: TrainState, batch: Dict[str, Any],
                scalar_params: ScalarParams, use_elastic_loss: bool = False, elastic_reduce_method: str = 'median',
                elastic_loss_type: str = 'log_svals', use_background_loss: bool = False,
-               use_warp_reg_loss: bool = False, *, rngs: Optional[Dict[str, Any]] = None, bf16: bool = False):
+               use_warp_reg_loss: bool = False, *, rngs: Optional[Dict[str, Any]] = None, bf16: bool = False,
+               cameras: Optional[CameraRefiner] = None, camera_learning_rate: float = 2e-3):
   """One optimisation step (training.py:138-271).  `batch` holds this rank's ray shard
   ('rgb','origins','directions','metadata').  Returns (new_state, stats, rng_key).
   `rngs` (extra, parity runs): explicit uniforms {'coarse': (B,N_c), 'fine': (B,N_f)} instead of the streams derived
   from `rng_key` (the reference's threefry stream is not reproducible without JAX).  `bf16` (extra, no reference
   counterpart; BASELINE config D): the NeRF MLPs run forward / dgrad / wgrad on bfloat16 MFMA operands with a bfloat16
-  activation stash; master weights, loss, compositing, the gradient all-reduce and Adam stay float32."""
+  activation stash; master weights, loss, compositing, the gradient all-reduce and Adam stay float32.
+  `cameras` (extra): a CameraRefiner -- the batch's origins / directions are replaced by those of its 'pixels' / 'item_index'
+  seen from the refined cameras, the fused step also returns the ray gradients (photometric terms only), and the deltas take an
+  Adam step of `camera_learning_rate` (untuned default) on their gradient, all-reduced like the field's.  float32 mode only."""
   if use_elastic_loss and elastic_loss_type not in L.ELASTIC_TYPE:
     raise L.NrfError(f"elastic_loss_type {elastic_loss_type!r} is not built (one of {sorted(L.ELASTIC_TYPE)}; 'nr' produces "
                      'NaNs in the reference itself, training.py:58)')
   next_key, fine_key, coarse_key, _ = _step_keys(rng_key)   # random.split(rng_key, 4) (training.py:168)
   opt = state.optimizer
   background = _background_of(model, batch, scalar_params, opt.target.flat.device) if use_background_loss else None
-  grad, stats = model.loss_and_grad(opt.target, batch, warp_extra=state.warp_extra,
-                                    rngs=rngs if rngs is not None else {'fine': fine_key, 'coarse': coarse_key},
-                                    grad_out=opt.grad, stats_out=opt.stats, bf16=bf16,
-                                    background=background,
-                                    elastic={'weight': scalar_params.elastic_loss_weight, 'reduce_method': elastic_reduce_method,
-                                             'loss_type': elastic_loss_type} if use_elastic_loss else None,
-                                    warp_reg={'weight': scalar_params.warp_reg_loss_weight, 'alpha': scalar_params.warp_reg_loss_alpha,
-                                              'scale': scalar_params.warp_reg_loss_scale} if use_warp_reg_loss else None)
+  rg_kw = {}
+  if cameras is not None:
+    if bf16:
+      raise L.NrfError('train_step(cameras=...): ray gradients are built for the float32 mode, not with bf16')
+    cameras.compose()
+    origins, directions = cameras.rays(batch)
+    # a precomputed 'viewdirs' would be that of the unrefined camera: the condition reads the directions (models.py:326-329)
+    batch = {k: v for k, v in batch.items() if k != 'viewdirs'}
+    batch['origins'], batch['directions'] = origins, directions
+    rg_kw = {'ray_grads': ('origins', 'directions'), 'ray_grads_out': cameras.ray_grad_buffers(origins.shape[0])}
+  res = model.loss_and_grad(opt.target, batch, warp_extra=state.warp_extra, **rg_kw,
+                            rngs=rngs if rngs is not None else {'fine': fine_key, 'coarse': coarse_key},
+                            grad_out=opt.grad, stats_out=opt.stats, bf16=bf16,
+                            background=background,
+                            elastic={'weight': scalar_params.elastic_loss_weight, 'reduce_method': elastic_reduce_method,
+                                     'loss_type': elastic_loss_type} if use_elastic_loss else None,
+                            warp_reg={'weight': scalar_params.warp_reg_loss_weight, 'alpha': scalar_params.warp_reg_loss_alpha,
+                                      'scale': scalar_params.warp_reg_loss_scale} if use_warp_reg_loss else None)
+  grad, stats = res[0], res[1]
+  if cameras is not None:
+    d_deltas = cameras.backward(batch, res[2]['origins'], res[2]['directions'])
+    if dist.is_available() and dist.is_initialized():
+      dist.all_reduce(d_deltas, op=dist.ReduceOp.SUM)
   grad, stats, n = psum_gradients(grad, stats, fused=opt._gs)
   opt.apply_gradient(grad, learning_rate=scalar_params.learning_rate, grad_scale=1.0 / n)
+  if cameras is not None:
+    cameras.apply_gradient(camera_learning_rate, grad_scale=1.0 / n)
   out = _stats_dict(stats, scalar_params, use_elastic_loss, use_background_loss, use_warp_reg_loss)
   return state, out, next_key
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Camera refinement through the whole differentiable chain, on a synthetic capture:
 
-    pose 6-vector -> camera table row (torch) -> rays_from_table (HIP) -> viewdirs = d / |d| (torch)
+    pose deltas (C, 16) -> compose_cameras (HIP) -> rays_from_table (HIP) -> viewdirs = d / |d| (torch)
       -> render_differentiable (HIP, nrf_backward_rays) -> photometric + depth loss -> backward -> torch Adam
 
 The NeRF parameters are fixed (a freshly initialised field); the target is its own rendering from the true camera of frame 0.  That
@@ -18,12 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from nerfies_amd import autograd, datasets, models  # noqa: E402
-from nerfies_amd.camera import CAMERA_PARAM_SLICES as SL, rays_from_table  # noqa: E402
-
-
-def hat(w):
-  z = torch.zeros((), device=w.device)
-  return torch.stack([torch.stack([z, -w[2], w[1]]), torch.stack([w[2], z, -w[0]]), torch.stack([-w[1], w[0], z])])
+from nerfies_amd.camera import CAMERA_DELTA_SLICES as DL, CAMERA_PARAM_SLICES as SL, compose_cameras, rays_from_table  # noqa: E402
 
 
 def main():
@@ -58,22 +53,25 @@ def main():
   R0, p0 = table0[0, SL['orientation']].reshape(3, 3).clone(), table0[0, SL['position']].clone()
   w_off = torch.tensor([0.02, -0.015, 0.01], device=dev)     # radians
   p_off = torch.tensor([0.010, -0.008, 0.006], device=dev)   # scene units (the scene spans about 0.3)
-  R_start = torch.matrix_exp(hat(w_off)) @ R0
-  w = torch.zeros(3, device=dev, requires_grad=True)
-  t = torch.zeros(3, device=dev, requires_grad=True)
-  opt = torch.optim.Adam([w, t], lr=args.lr)
+  offset = torch.zeros(table0.shape[0], 16, device=dev)
+  offset[0, DL['rotation']], offset[0, DL['translation']] = w_off, p_off
+  with torch.no_grad():
+    start = compose_cameras(table0, offset)   # frame 0 turned by exp(hat w_off) and moved by p_off
+  pose = torch.zeros(6, device=dev, requires_grad=True)   # frame 0's (rotation, translation) delta; the other columns stay 0
+  opt = torch.optim.Adam([pose], lr=args.lr)
   print(f'frame 0 of {len(ids)}: {pixels.shape[0]} rays; start: position error {p_off.norm().item():.5f}, rotation error '
         f'{w_off.norm().item():.5f} rad')
   for step in range(args.steps + 1):
-    R = torch.matrix_exp(hat(w)) @ R_start   # the caller's own rotation parametrisation -> nine orientation entries
-    row = torch.cat([R.reshape(9), p0 + p_off + t, table0[0, 12:]])
-    table = torch.cat([row[None], table0[1:]], 0)
+    deltas = torch.zeros_like(offset)
+    deltas[0, :6] = pose
+    table = compose_cameras(start, deltas)   # R = exp(hat w) R_start, position + t: differentiable in the deltas
     rgb, depth = render(table)
     loss = ((rgb - rgb_t) ** 2).mean() + ((depth - depth_t) ** 2).mean()
     if step % 10 == 0:
       with torch.no_grad():
+        R = table[0, SL['orientation']].reshape(3, 3)
         cosang = ((R @ R0.T).diagonal().sum() - 1) / 2
-        print(f'step {step:4d}  loss {loss.item():.3e}  position error {(p_off + t).norm().item():.5f}  rotation error '
+        print(f'step {step:4d}  loss {loss.item():.3e}  position error {(table[0, SL["position"]] - p0).norm().item():.5f}  rotation error '
               f'{torch.acos(cosang.clamp(-1, 1)).item():.5f} rad')
     if step == args.steps:
       break

@@ -9,13 +9,14 @@ batch; gradients meet in one all-reduce (RCCL) inside training.train_step.  Tens
 scalar log under <exp>/summaries/train."""
 import argparse
 import dataclasses
+import json
 import os
 import sys
 
 import torch
 import torch.distributed as dist
 
-from nerfies_amd import checkpoints, configs, datasets, models, schedules, training, utils
+from nerfies_amd import camera, checkpoints, configs, datasets, models, schedules, training, utils
 from nerfies_amd import gin_lite as gin
 
 
@@ -37,6 +38,16 @@ def parse_flags(argv=None):
   p.add_argument('--graph', action='store_true', help='replay the whole train step (loss + gradient, all-reduce, Adam) from ONE hipGraph '
                  '(training.GraphedTrainStep): the reference jits the step into one XLA executable (train.py:254-262); worth it for small '
                  'per-GPU batches, where the ~25 launches of a step take about as long as the kernels')
+  p.add_argument('--refine_cameras', default=None, choices=['pose', 'pose+focal', 'all'],
+                 help='train per-camera deltas next to the field (training.CameraRefiner; no reference counterpart): pose = rotation and '
+                      'translation, pose+focal, or all (+ principal point and distortion).  Every step recomputes the batch\'s rays from the '
+                      'refined cameras and back-propagates the photometric loss into them (float32 mode; not with --graph / --bf16).  '
+                      'The deltas are checkpointed as cameras_<step> next to checkpoint_<step>; at the end the refined cameras are '
+                      'written to <exp>/camera_refined/<item_id>.json, in the format and frame of the capture\'s camera/ directory')
+  p.add_argument('--camera_lr', type=float, default=2e-3, help='Adam learning rate of the camera deltas (the value of '
+                 'scripts/refine_camera_demo.py; untuned)')
+  p.add_argument('--refine_cameras_from', type=int, default=0, metavar='STEP', help='first step that refines the cameras (earlier steps '
+                 'train the field alone, on the unrefined rays)')
   flags = p.parse_args(argv)
   flags.bf16 = {'all': True, 'mlp': 'mlp', 'x3': 'x3', 'x3mlp': 'x3mlp', None: False}[flags.bf16]   # the value models / training take (False, True, 'mlp', 'x3')
   return flags
@@ -65,6 +76,10 @@ def main(argv=None):
   flags = parse_flags(argv)
   if flags.bf16 in ('x3', 'x3mlp'):
     raise SystemExit('--bf16 x3 is an inference mode (eval.py): the training chains stash float32 or bfloat16 activations')
+  if flags.refine_cameras and flags.graph:
+    raise SystemExit('--refine_cameras: not with --graph (the captured step has no ray gradients)')
+  if flags.refine_cameras and flags.bf16:
+    raise SystemExit('--refine_cameras: not with --bf16 (ray gradients are built for the float32 mode)')
   gin.parse_config_files_and_bindings(config_files=flags.gin_configs, bindings=flags.gin_bindings, skip_unknown=True)
   exp_config, model_config, train_config = configs.ExperimentConfig(), configs.ModelConfig(), configs.TrainConfig()
   rank, world, device = init_distributed()
@@ -81,8 +96,14 @@ def main(argv=None):
     raise ValueError('Batch size must be divisible by the number of devices.')
 
   datasource = make_datasource(flags, exp_config, model_config)
-  train_iter = datasource.create_iterator(datasource.train_ids, flatten=True, shuffle=True,
-                                          batch_size=train_config.batch_size, device=device)
+  refiner = None
+  if flags.refine_cameras:   # the rays carry their pixel and their row of the camera table: train_step recomputes them
+    train_ids = list(datasource.train_ids)
+    train_iter = datasource.create_ray_table(train_ids, device, shuffle=True, keep_item_index=True).batches(train_config.batch_size)
+    refiner = training.CameraRefiner(datasource.camera_table(train_ids, device), groups=flags.refine_cameras)
+  else:
+    train_iter = datasource.create_iterator(datasource.train_ids, flatten=True, shuffle=True,
+                                            batch_size=train_config.batch_size, device=device)
   points = None
   if train_config.use_background_loss:      # train.py:177-189: per-device slices of the shuffled point cloud
     points = torch.from_numpy(datasource.load_points(shuffle=True)).to(device)
@@ -111,6 +132,10 @@ def main(argv=None):
       warp_reg_loss_scale=train_config.warp_reg_loss_scale, background_loss_weight=train_config.background_loss_weight)
   state = checkpoints.restore_checkpoint(checkpoint_dir, state)
   init_step = state.optimizer.step + 1
+  if refiner is not None and state.optimizer.step > 0:
+    cam_path = os.path.join(checkpoint_dir, f'cameras_{state.optimizer.step}')
+    if os.path.exists(cam_path):   # absent: the run so far trained the field alone
+      refiner.load_state_dict(checkpoints.restore_checkpoint(cam_path, None))
   writer = utils.ScalarLog(summary_dir) if rank == 0 else None
   if writer:
     writer.text('gin/train', config_str, 0)
@@ -126,6 +151,12 @@ def main(argv=None):
   step_flags = dict(use_elastic_loss=train_config.use_elastic_loss, elastic_reduce_method=train_config.elastic_reduce_method,
                     elastic_loss_type=train_config.elastic_loss_type, use_background_loss=train_config.use_background_loss,
                     use_warp_reg_loss=train_config.use_warp_reg_loss)
+
+  def save_all(at):   # the flax-layout checkpoint_<step> stays what the reference reads; the camera state is a file of its own
+    checkpoints.save_checkpoint(checkpoint_dir, state, at, keep=5)
+    if refiner is not None:
+      checkpoints.save_checkpoint(checkpoint_dir, refiner.state_dict(), at, prefix='cameras_', keep=5)
+
   for step in range(init_step, max_steps + 1):
     batch = next(train_iter)
     if points is not None:
@@ -144,7 +175,9 @@ def main(argv=None):
         stats = gstep(key, scalar_params, warp_alpha=state.warp_alpha, time_alpha=state.time_alpha, batch=batch)
         key = training._step_keys(key)[0]
       else:
-        state, stats, key = training.train_step(model, key, state, batch, scalar_params, bf16=flags.bf16, **step_flags)
+        cameras = refiner if refiner is not None and step >= flags.refine_cameras_from else None
+        state, stats, key = training.train_step(model, key, state, batch, scalar_params, bf16=flags.bf16, cameras=cameras,
+                                                camera_learning_rate=flags.camera_lr, **step_flags)
       if step % train_config.print_every == 0 or step % train_config.log_every == 0:
         torch.cuda.synchronize(device)            # only when the numbers are read
     tracker.toc('total')
@@ -154,7 +187,7 @@ def main(argv=None):
       for lv in ('coarse', 'fine'):
         log(f'\t{lv} metrics: ' + ', '.join(f'{k}={float(v):.04f}' for k, v in stats[lv].items()))
     if step % train_config.save_every == 0 and rank == 0:
-      checkpoints.save_checkpoint(checkpoint_dir, state, step, keep=5)
+      save_all(step)
     if step % train_config.log_every == 0 and writer:
       writer.scalar('params/learning_rate', scalar_params.learning_rate, step)
       writer.scalar('params/warp_alpha', state.warp_alpha, step)
@@ -169,7 +202,25 @@ def main(argv=None):
       tracker.reset()
     tracker.tic('data', 'total')
   if rank == 0 and step >= init_step and step % train_config.save_every != 0:
-    checkpoints.save_checkpoint(checkpoint_dir, state, step, keep=5)
+    save_all(step)
+  if rank == 0 and refiner is not None:
+    # the hand-over to eval.py and other tools: the refined cameras as the capture stores its own (camera/<item_id>.json) -- back at
+    # full resolution and out of the normalised scene frame the datasource moved them into (datasets.load_camera)
+    out_dir = os.path.join(exp_dir, 'camera_refined')
+    os.makedirs(out_dir, exist_ok=True)
+    table = refiner.compose().cpu()
+    center, scale = getattr(datasource, 'scene_center', None), getattr(datasource, 'scene_scale', None)
+    image_scale = getattr(datasource, 'image_scale', 1)
+    for row, item_id in zip(table, train_ids):
+      cam = camera.unpack_camera(row, datasource.load_camera(item_id).image_size)
+      if scale is not None:
+        cam.position = cam.position / scale
+      if center is not None:
+        cam.position = cam.position + center
+      if image_scale != 1:
+        cam = cam.scale(image_scale)
+      with open(os.path.join(out_dir, f'{item_id}.json'), 'w') as f:
+        json.dump(cam.to_json(), f, indent=2)
   if world > 1:
     dist.barrier()
     dist.destroy_process_group()
