@@ -316,7 +316,9 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompositeBwdAr
         o.x = w * g0 * c.x * (1.f - c.x);           // through sigmoid (models.py:276)
         o.y = w * g1 * c.y * (1.f - c.y);
         o.z = w * g2 * c.z * (1.f - c.z);
-        o.w = sigma_act == 1 ? dsigma * (1.f - expf(-c.w)) : (c.w > 0.f ? dsigma : 0.f);   // softplus' / relu'
+        // softplus' = sigmoid(raw) = 1 - exp(-sigma) from the activated value: expm1f keeps its relative precision where sigma is
+        // small (1 - expf(-sigma) is a multiple of 2^-24, exactly 0 below sigma = 6e-8: empty space would get no gradient) / relu'
+        o.w = sigma_act == 1 ? dsigma * -expm1f(-c.w) : (c.w > 0.f ? dsigma : 0.f);
         d_raw4[(size_t)ray * S + s] = o;
         dsig_acc += o.w;
         if constexpr (RAYS) sdsig_acc += c.w * dsigma;

@@ -195,7 +195,7 @@ def leaf(tree, path):
 
 
 def run_pinned(spec, B, alpha, seed=3, strat=True, elastic=None, background=None, params=None, batch=None, t_rand=None, u=None,
-               warp_reg=None, time_alpha=None):
+               warp_reg=None, time_alpha=None, check_fine_z=True):
   """GPU loss_and_grad, masks read back, fp64 oracle pinned to them.  Returns a dict of everything compared."""
   from nerfies_amd import params as P
   p64 = params if params is not None else O.init_params(spec, seed=seed, trained_like=True, dtype=torch.float64)
@@ -252,8 +252,14 @@ def run_pinned(spec, B, alpha, seed=3, strat=True, elastic=None, background=None
       z_nat = O.sample_pdf(.5 * (ret['coarse']['z_vals'][..., 1:] + ret['coarse']['z_vals'][..., :-1]), ret['coarse']['weights'][..., 1:-1],
                            b64['origins'], b64['directions'], ret['coarse']['z_vals'], spec.num_fine_samples,
                            spec.use_stratified_sampling, u)[0]
-    assert (z_nat - z_fine).abs().max().item() < 2e-4 * (spec.far - spec.near), (z_nat - z_fine).abs().max().item()
-    assert (z_nat - z_fine).abs().mean().item() < 2e-6 * (spec.far - spec.near)
+    # check_fine_z=False (tests/test_gpu_density_regimes.py): where the coarse weights are 1e-9 or a step, the inverse CDF of
+    # model_utils.py:139-215 is flat or vertical and moves single samples by whole bins under float32 rounding of the weights in ANY
+    # float32 evaluation; the oracle is given the HIP path's depths either way, and the resampling has its own forward tests
+    if check_fine_z:
+      assert (z_nat - z_fine).abs().max().item() < 2e-4 * (spec.far - spec.near), (z_nat - z_fine).abs().max().item()
+      assert (z_nat - z_fine).abs().mean().item() < 2e-6 * (spec.far - spec.near)
+    else:
+      print(f'[fine depths, HIP path vs the oracle\'s own resampling] max {(z_nat - z_fine).abs().max().item():.2e} mean {(z_nat - z_fine).abs().mean().item():.2e}')
   got = P.tree_from_flat(grad.cpu(), model.layout)
   errs = {}
   for path, og in O.tree_leaves_with_path(ograds):
@@ -316,6 +322,67 @@ def assert_forward(r, spec, atol=1e-4):
       np.testing.assert_allclose(out[lv][k].cpu().numpy(), r['ret'][lv][k].detach().numpy(), atol=atol, err_msg=f'{lv}/{k}')
 
 
+# ---------------------------------------------------------------------------------------------
+# One stashed training forward + the float64 oracle pinned to it (moved here from tests/test_gpu_backward_ex.py so that
+# tests/test_gpu_density_regimes.py shares it; `params` / `batch` let a caller bring its own tree instead of the seeded one)
+# ---------------------------------------------------------------------------------------------
+OUTPUTS = ('rgb', 'depth', 'acc', 'weights')
+
+
+def cotangents_to_gpu(cot):
+  return {lv: {k: t.float().to(DEV) for k, t in d.items()} for lv, d in cot.items()}
+
+
+class Pinned:
+  """One stashed training forward on the GPU and the float64 oracle pinned to its ReLU pattern and fine depths; `compare(cot)`
+  back-propagates the cotangents `cot` through both and returns the worst per-leaf error relative to the leaf's max-abs."""
+
+  def __init__(self, spec, nrays, seed, alpha=0.0, tile_rows=0, points=False, params=None, batch=None):
+    self.spec, self.alpha = spec, alpha
+    self.p64 = params if params is not None else O.init_params(spec, seed=seed, trained_like=True, dtype=torch.float64)
+    self.b64 = batch if batch is not None else O.synthetic_batch(nrays, seed=seed + 1, dtype=torch.float64)
+    self.model, self.fp = gpu_model(spec, self.p64, nrays)
+    if tile_rows:
+      self.model.set_chain_tile_rows(tile_rows)
+    self.gb = gpu_batch(self.b64)
+    out = self.model.apply({'params': self.fp}, self.gb, {'alpha': alpha}, train=True, return_weights=True, return_z_vals=True)
+    torch.cuda.synchronize()
+    masks = gpu_relu_masks(self.model, spec, nrays)
+    z_fine = out['fine']['z_vals'].cpu().double()
+    leaves = list(O.tree_leaves_with_path(self.p64))
+    self.paths = [p for p, _ in leaves]
+    self.req = [t.detach().clone().requires_grad_(True) for _, t in leaves]
+    it = iter(self.req)
+    params_r = O.tree_map(lambda _: next(it), self.p64)
+    self.hook = PinnedRelu(masks)
+    with O.relu_hook(self.hook):
+      self.ret = O.nerf_model_apply(params_r, spec, self.b64, warp_alpha=alpha, fixed_fine_z=z_fine, return_points=points)
+    for lv in ('coarse', 'fine'):   # the two forwards agree, so the pinned comparison is of one function
+      for k in OUTPUTS:
+        np.testing.assert_allclose(out[lv][k].cpu().numpy(), self.ret[lv][k].detach().numpy(), atol=1e-4, err_msg=f'{lv}/{k}')
+    assert self.hook.flips <= FLIP_FRACTION * self.hook.total, (self.hook.flips, self.hook.total)
+
+  def oracle_grads(self, cot):
+    loss = sum((self.ret[lv][k] * t).sum() for lv, d in cot.items() for k, t in d.items())
+    grads = torch.autograd.grad(loss, self.req, allow_unused=True, retain_graph=True)
+    return {p: (g if g is not None else torch.zeros_like(t)) for p, g, t in zip(self.paths, grads, self.req)}
+
+  def gpu_grads(self, cot, **kw):
+    from nerfies_amd import params as P
+    grad = self.model.backward({'params': self.fp}, self.gb, d_out=cotangents_to_gpu(cot), **kw)
+    return P.tree_from_flat(grad.cpu(), self.model.layout)
+
+  def compare(self, cot, label):
+    want, got = self.oracle_grads(cot), self.gpu_grads(cot)
+    errs = {}
+    for path, og in want.items():
+      scale = max(og.abs().max().item(), 1e-30)
+      errs[path] = ((leaf(got, path).double() - og).abs().max().item() / scale, scale)
+    worst = max(errs.items(), key=lambda kv: kv[1][0])
+    print(f'[{label}] worst leaf {worst[0]} rel err {worst[1][0]:.2e} (max-abs {worst[1][1]:.2e}); tolerance {grad_tol(self.spec):.0e}')
+    for path, (err, scale) in errs.items():
+      assert err < grad_tol(self.spec), (label, path, err, scale)
+    return want, got
 
 
 # ---------------------------------------------------------------------------------------------
@@ -381,3 +448,324 @@ def tree_dot(grads, direction, path=()):
       tot += float((g * direction[path + (k,)]).sum())
   return tot
 
+
+
+# ---------------------------------------------------------------------------------------------
+# Density regimes (tests/test_density_regimes_host.py, tests/test_gpu_density_regimes.py, profiles/density_regimes.md)
+#
+# oracle.init_params(trained_like=True) keeps every softplus density within (0.4, 0.8) and the fine relu density at 0.  A regime
+# rewrites each level's density head (MLP_2/logit: kernel x K, a new bias) so that chosen quantiles of the level's own raw density
+# land at chosen values, measured on the float64 oracle; the optional colour option scales the rgb head (MLP_1/logit) the same way.
+# ---------------------------------------------------------------------------------------------
+REGIMES = ('empty', 'surface', 'opaque')
+LEVELS = ('coarse', 'fine')
+
+
+def _heads(params, spec, batch):
+  """One float64 oracle evaluation: {level: dict(raw (B,S) raw density, rgb (B,S,3) raw colour, z (B,S))}."""
+  seen = {}
+  key = {}
+  for lv in LEVELS:
+    key[id(params[f'nerf_mlps_{lv}']['MLP_2']['logit'])] = (lv, 'raw')
+    key[id(params[f'nerf_mlps_{lv}']['MLP_1']['logit'])] = (lv, 'rgb')
+
+  def hook(p, x):
+    y = x @ p['kernel'] + p['bias']
+    if id(p) in key:
+      seen[key[id(p)]] = y.detach()
+    return y
+  with torch.no_grad(), O.dense_hook(hook):
+    ret = O.nerf_model_apply(params, spec, batch)
+  out = {}
+  for lv in LEVELS:
+    z = ret[lv]['z_vals']
+    out[lv] = dict(raw=seen[(lv, 'raw')].reshape(z.shape), rgb=seen[(lv, 'rgb')].reshape(*z.shape, 3), z=z)
+  return out
+
+
+def _dists(spec, z, directions):
+  last = 1e10 if spec.use_sample_at_infinity else 1e-19
+  d = torch.cat([z[..., 1:] - z[..., :-1], torch.full_like(z[..., :1], last)], -1)
+  return d * torch.linalg.norm(directions, dim=-1, keepdim=True)
+
+
+def regime_stats(spec, head, directions):
+  """What the regime conditions are stated on, from one level's float64 raw density / colour / depths."""
+  raw, z = head['raw'], head['z']
+  sigma = O._sigma_act(spec.sigma_activation, raw)
+  dist = _dists(spec, z, directions)
+  alpha = 1.0 - torch.exp(-sigma * dist)
+  T = torch.cat([torch.ones_like(alpha[..., :1]), torch.cumprod(1.0 - alpha[..., :-1] + 1e-10, -1)], -1)
+  a32 = 1.0 - torch.exp(-sigma.float() * dist.float())
+  T32 = torch.cumprod(1.0 - a32 + 1e-10, -1)   # float32, inclusive: what the transmittance ends at
+  rgb = torch.sigmoid(head['rgb'])
+  n = float(sigma.numel())
+  return dict(
+      raw_min=raw.min().item(), raw_max=raw.max().item(), sigma_min=sigma.min().item(), sigma_max=sigma.max().item(),
+      sigma_zero=(sigma == 0).sum().item() / n, sigma_lt_1e6=(sigma < 1e-6).sum().item() / n, sigma_lt_1e4=(sigma < 1e-4).sum().item() / n,
+      tau_gt_5=(sigma * dist > 5).sum().item() / n, alpha_gt_099=(alpha > 0.99).sum().item() / n,
+      rays_T_lt_1e3=(T[..., -1] < 1e-3).sum().item() / T.shape[0], rays_T_gt_half=(T.min(-1).values > 0.5).sum().item(),
+      rays_T32_zero=(T32[..., -1] == 0).sum().item() / T.shape[0], T_min=T.min().item(),
+      rgb_saturated=((rgb < 1e-3) | (rgb > 1 - 1e-3)).sum().item() / float(rgb.numel()))
+
+
+def _quantile(x, q):
+  return torch.quantile(x.reshape(-1), q).item()
+
+
+def _density_head(spec, regime, head, bias, directions):
+  """(K, new bias) of one level's density head: with u = raw - bias the head's bias-free output, the new raw density is K u + b."""
+  u = head['raw'] - bias
+  dist = _dists(spec, head['z'], directions)
+  finite = torch.ones_like(u, dtype=torch.bool)
+  finite[..., -1] = False   # the last distance (1e10 |d| or 1e-19 |d|) says nothing about the ray's extent
+  relu = spec.sigma_activation == 'relu'
+  if regime == 'empty':      # median at -15 (sigma 3e-7), everything inside [-29, -6.5]
+    lo, med, hi = u.min().item(), _quantile(u, 0.5), u.max().item()
+    K = min(8.5 / max(hi - med, 1e-30), 14.0 / max(med - lo, 1e-30))
+    return K, -15.0 - K * med
+  if regime == 'surface':
+    # anchor: the larger of the emptiest ray's largest value (the last sample apart: at infinity any density is opaque, and the
+    # transmittance never sees it) and the 32 % quantile goes to -17.5 (softplus: sigma 2.5e-8, where 1 - expf(-sigma) is exactly 0; relu: -0.5, sigma 0),
+    # so one whole ray and a third of the samples stay empty; K puts the 85 % quantile of (u - anchor) dist at an optical depth of 8
+    # and the optical depth of the median ray (the sum of its positive (u - anchor) dist) at 16 or more (T = 1e-7)
+    anchor, low = max(u[..., :-1].max(-1).values.min().item(), _quantile(u, 0.32)), -0.5 if relu else -17.5
+    tau = (u - anchor) * dist * finite
+    ray = tau.clamp(min=0).sum(-1).sort(descending=True).values[(u.shape[0] + 1) // 2 - 1].item()
+    K = max(8.0 / max(_quantile(tau[finite], 0.85), 1e-30), 16.0 / max(ray, 1e-30))
+    return K, low - K * anchor
+  if regime == 'opaque':
+    # the 25 % quantile at raw 0; the 40 % quantile of (u - anchor) dist at an optical depth of 6 (alpha 0.9975), and every ray's
+    # optical depth (the sum of its positive (u - anchor) dist) at 120 or more: exp(-120) is below float32's smallest denormal
+    anchor = _quantile(u, 0.25)
+    tau = (u - anchor) * dist * finite
+    K = max(6.0 / max(_quantile(tau[finite], 0.40), 1e-30), 120.0 / max(tau.clamp(min=0).sum(-1).min().item(), 1e-30))
+    return K, -K * anchor
+  raise ValueError(regime)
+
+
+def density_regime(params, spec, batch, regime, saturated_rgb=False):
+  """(tree, stats): `params` (a float64 oracle tree, left untouched) with both levels' density heads rewritten into `regime`, and
+  {level: regime_stats} of the result.  The coarse head goes first: the fine depths follow the coarse weights, so the fine head is
+  placed on the raw density it has at the depths the rewritten coarse level sends it.  No random numbers are drawn."""
+  tree = O.tree_map(lambda t: t.clone(), params)
+  d = batch['directions']
+  for lv in LEVELS:
+    head = _heads(tree, spec, batch)[lv]
+    lg = tree[f'nerf_mlps_{lv}']['MLP_2']['logit']
+    K, b = _density_head(spec, regime, head, lg['bias'], d)
+    lg['kernel'], lg['bias'] = lg['kernel'] * K, torch.full_like(lg['bias'], b)
+    if saturated_rgb:   # the 85 % quantile of |raw colour| at 7 (sigmoid within 9e-4 of 0 or 1)
+      cg = tree[f'nerf_mlps_{lv}']['MLP_1']['logit']
+      k = 7.0 / _quantile(head['rgb'].abs(), 0.85)
+      cg['kernel'], cg['bias'] = cg['kernel'] * k, cg['bias'] * k
+  heads = _heads(tree, spec, batch)
+  stats = {lv: regime_stats(spec, heads[lv], d) for lv in LEVELS}
+  assert_regime(spec, regime, stats, saturated_rgb)
+  return tree, stats
+
+
+def assert_regime(spec, regime, stats, saturated_rgb=False):
+  """The regime's defining conditions, on the float64 oracle's values."""
+  relu = spec.sigma_activation == 'relu'
+  for lv in LEVELS:
+    s = stats[lv]
+    if regime == 'empty':
+      assert not relu and -30 <= s['raw_min'] and s['raw_max'] <= -6 and s['sigma_lt_1e6'] >= 0.5, (lv, s)
+      assert 9e-14 <= s['sigma_min'] and s['sigma_max'] <= 2.5e-3, (lv, s)
+    elif regime == 'surface':
+      assert (s['sigma_zero'] if relu else s['sigma_lt_1e4']) >= 0.30 and s['tau_gt_5'] >= 0.10, (lv, s)
+      assert s['rays_T_lt_1e3'] >= 0.5 and s['rays_T_gt_half'] >= 1, (lv, s)
+    elif regime == 'opaque':
+      if lv == 'coarse':
+        assert s['alpha_gt_099'] > 0.5, (lv, s)
+      assert s['rays_T32_zero'] == 1.0, (lv, s)
+    if saturated_rgb:
+      assert s['rgb_saturated'] >= 0.10, (lv, s)
+
+
+def cotangents(spec, nrays, keys, seed):
+  """{level: {key: float64 tensor}}: seeded normals in the shapes of NerfModel.apply's outputs."""
+  g = torch.Generator().manual_seed(seed)
+  S = {'coarse': spec.num_coarse_samples, 'fine': spec.num_coarse_samples + spec.num_fine_samples}
+  shape = lambda lv: {'rgb': (nrays, 3), 'depth': (nrays,), 'acc': (nrays,), 'weights': (nrays, S[lv])}
+  return {lv: {k: torch.randn(*shape(lv)[k], generator=g, dtype=torch.float64) for k in keys} for lv in LEVELS}
+
+
+def render_raw(spec, raw4, z, directions):
+  """model_utils.py:104-126 behind models.py:276-277 in the dtype of `raw4` (B,S,4) = raw colour, raw density, restated in plain torch
+  operations for torch.autograd: softplus differentiates as sigmoid(x); the exclusive cumprod of :112-115 is written as the running
+  product it is, so that its reverse pass is the division-free recurrence and not torch.cumprod's own backward formula."""
+  rgb, sigma = torch.sigmoid(raw4[..., :3]), O._sigma_act(spec.sigma_activation, raw4[..., 3])
+  last = 1e10 if spec.use_sample_at_infinity else 1e-19
+  dists = torch.cat([z[..., 1:] - z[..., :-1], torch.full_like(z[..., :1], last)], -1) * torch.linalg.norm(directions[..., None, :], dim=-1)
+  alpha = 1.0 - torch.exp(-sigma * dists)
+  t = 1.0 - alpha + 1e-10
+  T = [torch.ones_like(alpha[..., 0])]
+  for i in range(alpha.shape[-1] - 1):
+    T.append(T[-1] * t[..., i])
+  weights = alpha * torch.stack(T, -1)
+  out_rgb = (weights[..., None] * rgb).sum(-2)
+  acc = weights.sum(-1)
+  if spec.use_white_background:
+    out_rgb = out_rgb + (1. - acc[..., None])
+  if spec.use_sample_at_infinity:
+    acc = weights[..., :-1].sum(-1)
+  return {'rgb': out_rgb, 'depth': (weights * z).sum(-1), 'acc': acc, 'weights': weights}
+
+
+def d_raw_autograd(spec, raw4, z, directions, cot):
+  """d <cot, outputs> / d raw4 by torch.autograd over render_raw, in raw4's dtype."""
+  x = raw4.detach().clone().requires_grad_(True)
+  out = render_raw(spec, x, z.to(x.dtype), directions.to(x.dtype))
+  return torch.autograd.grad(sum((out[k] * t.to(x.dtype)).sum() for k, t in cot.items()), x)[0], out
+
+
+def composite_vjp(spec, out4, z, directions, cot, target=None):
+  """float64 compositing of ACTIVATED values out4 (B,S,4) = sigmoid colour, sigma, and its VJP carried to the raw heads through
+  derivatives that are functions of the activated values alone: sigmoid' = c (1 - c), softplus' = -expm1(-sigma), relu' =
+  [sigma > 0].  `target` (B,3): the rgb cotangent is that of mean((rgb - target)^2).  Returns (outputs, d_raw4)."""
+  a = out4.double().detach().clone().requires_grad_(True)
+  out = O.volumetric_rendering(a[..., :3], a[..., 3], z.double(), directions.double(), spec.use_white_background,
+                               spec.use_sample_at_infinity)
+  cot = dict(cot)
+  if target is not None:
+    cot['rgb'] = 2.0 * (out['rgb'].detach() - target.double()) / target.numel()
+  g = torch.autograd.grad(sum((out[k] * t.double()).sum() for k, t in cot.items()), a)[0]
+  c, sigma = a.detach()[..., :3], a.detach()[..., 3]
+  dact = -torch.expm1(-sigma) if spec.sigma_activation == 'softplus' else (sigma > 0).double()
+  return {k: v.detach() for k, v in out.items()}, torch.cat([g[..., :3] * c * (1 - c), (g[..., 3] * dact)[..., None]], -1)
+
+
+# Behind a hard surface a whole ray's density gradient is a product of exp(-optical depth) factors that float64 still holds (1e-60,
+# 1e-150) and no float32 evaluation can (normal floats end at 1.2e-38): with cotangents of order 1, a ray whose largest reference entry
+# is below RAY_FLOOR counts as having RAY_FLOOR for its largest entry, which holds the kernel to an absolute 1e-30 there.
+RAY_FLOOR = 1e-30
+# alpha = 1 - exp(-sigma dist) is a multiple of 2^-24 in float32 (model_utils.py:110 as written), so every weight carries an absolute
+# error of up to 2^-24 in any float32 evaluation, the reference's own included, and a colour entry w_i g_k c (1 - c) one of up to
+# 2^-24 |g| / 4 <= 2^-24 for cotangents below 4: that much of a colour entry's error is not counted (on a ray through empty space
+# without the sample at infinity every weight is below 2^-24 and the whole ray would otherwise be its own rounding error).
+COLOUR_ATOL = 2.0 ** -24
+EXCLUDE_BELOW = 1e-5   # a density-component element may leave the elementwise criterion only with an error below this x the ray's largest
+EXCLUDE_SHARE = 0.02   # ... and at most this share of a case's elements may
+
+
+def d_raw_errors(got, ref, last_at_infinity=True):
+  """got, ref (B,S,4).  Density component: elementwise |delta| / (|ref| + 1e-6 ray max) and the mask of the elements whose error is
+  below EXCLUDE_BELOW x the ray's largest density entry; colour components: (|delta| - COLOUR_ATOL)+ over the ray's largest colour
+  entry (the reference's own 1 - exp(-sigma dist) has no relative precision, so the weights w_i that scale them have none either).
+  `last_at_infinity` (use_sample_at_infinity): dL/dsigma of the last sample carries its distance of 1e10 |d| and would be every ray's
+  largest entry by ten orders of magnitude, so the ray max of the other samples is taken without it, and the last sample is held
+  against the larger of that and its own magnitude."""
+  got, ref = got.double(), ref.double()
+  dw, rw = (got[..., 3] - ref[..., 3]).abs(), ref[..., 3].abs()
+  wmax = (rw[..., :-1] if last_at_infinity else rw).max(-1, keepdim=True).values.clamp(min=RAY_FLOOR).expand_as(rw).clone()
+  wmax[..., -1] = torch.maximum(wmax[..., -1], rw[..., -1])
+  w_rel = torch.where(dw == 0, torch.zeros_like(dw), dw / (rw + 1e-6 * wmax))
+  dc = ((got[..., :3] - ref[..., :3]).abs().flatten(1).max(-1).values - COLOUR_ATOL).clamp(min=0)
+  cmax = ref[..., :3].abs().flatten(1).max(-1).values
+  c_ray = torch.where(dc == 0, torch.zeros_like(dc), dc / cmax.clamp(min=1e-300))
+  return dict(w_rel=w_rel, w_small=dw < EXCLUDE_BELOW * wmax, w_ray=(dw / wmax).max().item(), c_ray=c_ray.max().item())
+
+
+def d_raw_summary(got, ref, w_tol, last_at_infinity=True):
+  """(worst elementwise density error among the elements held to the criterion, share of excluded elements, worst density error /
+  ray max, worst colour error / ray max) -- an element is excluded when it misses `w_tol` with an error below EXCLUDE_BELOW x ray max."""
+  e = d_raw_errors(got, ref, last_at_infinity)
+  excluded = (e['w_rel'] > w_tol) & e['w_small']
+  held = e['w_rel'][~excluded]
+  return held.max().item() if held.numel() else 0.0, excluded.sum().item() / float(e['w_rel'].numel()), e['w_ray'], e['c_ray']
+
+
+# ---- the cases of tests/test_gpu_density_regimes.py, shared with the host test that measures their float32 floor -------------
+REGIME_SHAPE = dict(num_coarse_samples=24, num_fine_samples=56, nerf_trunk_width=64, num_nerf_point_freqs=4, use_stratified_sampling=False)
+REGIME_SHAPE_3 = dict(REGIME_SHAPE, num_coarse_samples=64, num_fine_samples=128)   # three 64-sample chunks at the fine level
+REGIME_SEED = 31
+_REGIME_CACHE = {}
+
+
+def regime_batch(nrays, seed=REGIME_SEED + 1):
+  """oracle.synthetic_batch with unit viewdirs and directions of length 1.7: the |d| factor of the distances cannot go missing."""
+  b = O.synthetic_batch(nrays, seed=seed, dtype=torch.float64)
+  b['viewdirs'] = b['directions'].clone()
+  b['directions'] = b['directions'] * 1.7
+  return b
+
+
+def regime_case(regime, act='softplus', white=False, inf=True, sat=False, three=False, alpha_cond=False):
+  """(spec, B, float64 tree in `regime`, float64 batch, {level: regime_stats}); B = 7 rays of 24 + 56 samples, or 5 of 64 + 128."""
+  key = (regime, act, white, inf, sat, three, alpha_cond)
+  if key not in _REGIME_CACHE:
+    extra = dict(use_appearance_metadata=True, use_alpha_condition=True) if alpha_cond else {}
+    spec = O.ModelSpec(sigma_activation=act, use_white_background=white, use_sample_at_infinity=inf,
+                       **(REGIME_SHAPE_3 if three else REGIME_SHAPE), **extra)
+    B = 5 if three else 7
+    p64 = O.init_params(spec, seed=REGIME_SEED, trained_like=True, dtype=torch.float64)
+    b64 = regime_batch(B)
+    if regime == 'stock':
+      heads = _heads(p64, spec, b64)
+      tree, stats = p64, {lv: regime_stats(spec, heads[lv], b64['directions']) for lv in LEVELS}
+    else:
+      tree, stats = density_regime(p64, spec, b64, regime, saturated_rgb=sat)
+    _REGIME_CACHE[key] = (spec, B, tree, b64, stats)
+  return _REGIME_CACHE[key]
+
+
+# (id, regime_case arguments, mode).  Modes: 'plain' nrf_backward with rgb cotangents (composite_bwd_kernel<false, false>), 'extra'
+# nrf_backward_ex with rgb, depth, acc and weights cotangents (<true, false>), 'rays' / 'rays_extra' nrf_backward_rays (<false, true> /
+# <true, true>), 'loss' nrf_train_step_loss_grad (d_rgb == NULL, the target from the batch), 'bf16' the extra case under NRF_FLAG_BF16.
+D_RAW_CASES = [
+    ('empty-softplus-plain', dict(regime='empty'), 'plain'),
+    ('empty-softplus-extra', dict(regime='empty'), 'extra'),
+    ('empty-softplus-loss', dict(regime='empty'), 'loss'),
+    ('surface-softplus-plain', dict(regime='surface'), 'plain'),
+    ('surface-softplus-extra', dict(regime='surface'), 'extra'),
+    ('surface-softplus-white', dict(regime='surface', white=True), 'extra'),
+    ('surface-softplus-noinf', dict(regime='surface', inf=False), 'extra'),
+    ('surface-softplus-white-noinf', dict(regime='surface', white=True, inf=False), 'extra'),
+    ('surface-softplus-saturated', dict(regime='surface', sat=True), 'extra'),
+    ('surface-softplus-rays-extra', dict(regime='surface'), 'rays_extra'),
+    ('surface-softplus-loss', dict(regime='surface'), 'loss'),
+    ('surface-softplus-bf16', dict(regime='surface'), 'bf16'),
+    ('surface-softplus-three-chunks', dict(regime='surface', three=True), 'extra'),
+    ('surface-relu-extra', dict(regime='surface', act='relu'), 'extra'),
+    ('surface-relu-white-noinf', dict(regime='surface', act='relu', white=True, inf=False), 'extra'),
+    ('opaque-softplus-extra', dict(regime='opaque'), 'extra'),
+    ('opaque-relu-extra', dict(regime='opaque', act='relu'), 'extra'),
+    ('opaque-relu-saturated-plain', dict(regime='opaque', act='relu', sat=True), 'plain'),
+    ('opaque-relu-rays', dict(regime='opaque', act='relu'), 'rays'),
+]
+
+
+def case_cotangents(spec, B, mode):
+  return cotangents(spec, B, ('rgb',) if mode in ('plain', 'rays', 'loss') else OUTPUTS, seed=5)
+
+
+# The float32 floor of d raw per regime: the worst figures of tests/test_density_regimes_host.py::test_float32_floor_of_d_raw over the
+# regime's cases and both levels (the colour floor: over all regimes; plain float32 torch autograd of compositing + activations against the same in float64; the
+# figures per case are in profiles/density_regimes.md), rounded up.  w_rel: density component, elementwise |delta| / (|ref| + 1e-6 ray
+# max); w_ray / c_ray: density / colour error over the ray's largest entry.  The GPU tolerances are 4 x the floor: a different but
+# equally valid order of the float32 sums and products, as for grad_tol.
+D_RAW_FLOOR = {
+    'empty': dict(w_rel=7.7e-3, w_ray=1.4e-4, c_ray=4.0e-7),
+    # behind a sample with sigma dist in (16.6, 23) alpha rounds to 1 and t = 1 - alpha + 1e-10 is 1e-10 instead of up to 6e-8 (the
+    # reference's own float32 formula), so everything further along the ray is off by that factor: elementwise the density floor is
+    # 0.3 and says little there; the error over the ray's largest entry is what holds the kernel in this regime
+    'surface': dict(w_rel=0.31, w_ray=6.3e-4, c_ray=4.0e-7),
+    'opaque': dict(w_rel=9.1e-2, w_ray=6.8e-4, c_ray=4.0e-7),
+}
+D_RAW_TOL = {r: {k: 4.0 * v for k, v in f.items()} for r, f in D_RAW_FLOOR.items()}
+
+
+def assert_d_raw(got, ref, regime, label, last_at_infinity=True):
+  """d raw (B,S,4) of the HIP path against the float64 VJP `ref` at D_RAW_TOL[regime]; returns the figures."""
+  tol = D_RAW_TOL[regime]
+  held, share, w_ray, c_ray = d_raw_summary(got, ref, tol['w_rel'], last_at_infinity)
+  worst = d_raw_errors(got, ref, last_at_infinity)['w_rel'].max().item()
+  print(f'[{label}] density: elementwise worst {worst:.2e} (held to the criterion: {held:.2e}, tolerance {tol["w_rel"]:.1e}; excluded '
+        f'{share:.4f}), / ray max {w_ray:.2e} (tolerance {tol["w_ray"]:.1e}); colour / ray max {c_ray:.2e} (tolerance {tol["c_ray"]:.1e})')
+  assert torch.isfinite(got).all(), label
+  assert held <= tol['w_rel'] and share <= EXCLUDE_SHARE, (label, held, share)
+  assert w_ray <= tol['w_ray'], (label, w_ray)
+  assert c_ray <= tol['c_ray'], (label, c_ray)
+  return dict(w_rel=worst, held=held, excluded=share, w_ray=w_ray, c_ray=c_ray)

@@ -37,56 +37,7 @@ def _to_gpu(cot):
   return {lv: {k: t.float().to(H.DEV) for k, t in d.items()} for lv, d in cot.items()}
 
 
-class Pinned:
-  """One stashed training forward on the GPU and the float64 oracle pinned to its ReLU pattern and fine depths; `compare(cot)`
-  back-propagates the cotangents `cot` through both and returns the worst per-leaf error relative to the leaf's max-abs."""
-
-  def __init__(self, spec, nrays, seed, alpha=0.0, tile_rows=0, points=False):
-    self.spec, self.alpha = spec, alpha
-    self.p64 = O.init_params(spec, seed=seed, trained_like=True, dtype=torch.float64)
-    self.b64 = O.synthetic_batch(nrays, seed=seed + 1, dtype=torch.float64)
-    self.model, self.fp = H.gpu_model(spec, self.p64, nrays)
-    if tile_rows:
-      self.model.set_chain_tile_rows(tile_rows)
-    self.gb = H.gpu_batch(self.b64)
-    out = self.model.apply({'params': self.fp}, self.gb, {'alpha': alpha}, train=True, return_weights=True, return_z_vals=True)
-    torch.cuda.synchronize()
-    masks = H.gpu_relu_masks(self.model, spec, nrays)
-    z_fine = out['fine']['z_vals'].cpu().double()
-    leaves = list(O.tree_leaves_with_path(self.p64))
-    self.paths = [p for p, _ in leaves]
-    self.req = [t.detach().clone().requires_grad_(True) for _, t in leaves]
-    it = iter(self.req)
-    params_r = O.tree_map(lambda _: next(it), self.p64)
-    self.hook = H.PinnedRelu(masks)
-    with O.relu_hook(self.hook):
-      self.ret = O.nerf_model_apply(params_r, spec, self.b64, warp_alpha=alpha, fixed_fine_z=z_fine, return_points=points)
-    for lv in ('coarse', 'fine'):   # the two forwards agree, so the pinned comparison is of one function
-      for k in OUTPUTS:
-        np.testing.assert_allclose(out[lv][k].cpu().numpy(), self.ret[lv][k].detach().numpy(), atol=1e-4, err_msg=f'{lv}/{k}')
-    assert self.hook.flips <= H.FLIP_FRACTION * self.hook.total, (self.hook.flips, self.hook.total)
-
-  def oracle_grads(self, cot):
-    loss = sum((self.ret[lv][k] * t).sum() for lv, d in cot.items() for k, t in d.items())
-    grads = torch.autograd.grad(loss, self.req, allow_unused=True, retain_graph=True)
-    return {p: (g if g is not None else torch.zeros_like(t)) for p, g, t in zip(self.paths, grads, self.req)}
-
-  def gpu_grads(self, cot, **kw):
-    from nerfies_amd import params as P
-    grad = self.model.backward({'params': self.fp}, self.gb, d_out=_to_gpu(cot), **kw)
-    return P.tree_from_flat(grad.cpu(), self.model.layout)
-
-  def compare(self, cot, label):
-    want, got = self.oracle_grads(cot), self.gpu_grads(cot)
-    errs = {}
-    for path, og in want.items():
-      scale = max(og.abs().max().item(), 1e-30)
-      errs[path] = ((H.leaf(got, path).double() - og).abs().max().item() / scale, scale)
-    worst = max(errs.items(), key=lambda kv: kv[1][0])
-    print(f'[{label}] worst leaf {worst[0]} rel err {worst[1][0]:.2e} (max-abs {worst[1][1]:.2e}); tolerance {H.grad_tol(self.spec):.0e}')
-    for path, (err, scale) in errs.items():
-      assert err < H.grad_tol(self.spec), (label, path, err, scale)
-    return want, got
+Pinned = H.Pinned   # shared with tests/test_gpu_density_regimes.py
 
 
 @functools.lru_cache(maxsize=None)

@@ -71,11 +71,11 @@ class PinnedRays:
   """One stashed ray-gradient forward on the GPU and the float64 oracle pinned to its ReLU pattern and fine depths, the rays as
   requires_grad leaves next to the parameters."""
 
-  def __init__(self, spec, nrays, seed, alpha=0.0, time_alpha=0.0, tile_rows=0):
+  def __init__(self, spec, nrays, seed, alpha=0.0, time_alpha=0.0, tile_rows=0, params=None, batch=None):
     self.spec, self.nrays = spec, nrays
     self.warp_extra = {'alpha': alpha, 'time_alpha': time_alpha}
-    self.p64 = O.init_params(spec, seed=seed, trained_like=True, dtype=torch.float64)
-    self.b64 = _batch(nrays, seed + 1, torch.float64)
+    self.p64 = params if params is not None else O.init_params(spec, seed=seed, trained_like=True, dtype=torch.float64)
+    self.b64 = batch if batch is not None else _batch(nrays, seed + 1, torch.float64)
     self.model, self.fp = H.gpu_model(spec, self.p64, nrays)
     if tile_rows:
       self.model.set_chain_tile_rows(tile_rows)
