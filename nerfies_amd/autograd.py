@@ -9,7 +9,7 @@ stop_gradient, model_utils.py:187).  Out of scope: a cotangent of 'warp_jacobian
 regulariser of the fused train step) and extra cotangents through the fused `loss_and_grad`, whose loss is fixed.
 
 Rays: when rays['origins'], rays['directions'] or rays['viewdirs'] requires grad (camera pose / intrinsics refinement, per-frame pose
-deltas, a learned lens correction), the call goes through `RayRenderFunction` instead: the forward sets NRF_FLAG_RAY_GRADS and the
+deltas, a learned lens correction), they enter `RenderFunction` as inputs of their own: the forward sets NRF_FLAG_RAY_GRADS and the
 backward is ONE nrf_backward_rays call that returns the parameter gradient and the three (B,3) ray gradients (float32 mode only).
 viewdirs = d / |d| is the caller's own torch expression, so autograd carries d_viewdirs on to the directions.  The 'points' output
 stays non-differentiable: rebuild o + z d from 'z_vals' in torch; a cotangent on 'warped_points' does reach the rays.  With no
@@ -40,16 +40,22 @@ from nerfies_amd import params as P
 DIFFERENTIABLE = ('rgb', 'depth', 'acc', 'weights', 'warped_points')   # the rest: med_depth, points, z_vals
 
 
+RAY_KEYS = ('origins', 'directions', 'viewdirs')
+
+
 class RenderFunction(torch.autograd.Function):
   """forward: the rendered outputs of every level, flattened in the order of `ctx.keys`; backward: one nrf_backward_ex call on the
-  stash the forward left, with whatever cotangents autograd delivers."""
+  stash the forward left, with whatever cotangents autograd delivers.  `origins` / `directions` / `viewdirs` are the rays as
+  differentiable inputs, or None for what `rays` holds: when one of them needs a gradient the forward runs under NRF_FLAG_RAY_GRADS
+  and the backward is one nrf_backward_rays call instead."""
 
   @staticmethod
-  def forward(ctx, flat, model, rays, warp_extra, rngs, opts, keys):
+  def forward(ctx, flat, origins, directions, viewdirs, model, rays, warp_extra, rngs, opts, keys):
     fp = P.FlatParams(flat.detach(), model.layout)
-    out = model.apply({'params': fp}, rays, warp_extra, rngs=rngs, train=True, **opts)
+    rays = dict(rays, **{k: t.detach() for k, t in zip(RAY_KEYS, (origins, directions, viewdirs)) if t is not None})
+    out = model.apply({'params': fp}, rays, warp_extra, rngs=rngs, train=True, ray_grads=any(ctx.needs_input_grad[1:4]), **opts)
     ctx.model, ctx.rays, ctx.fp = model, rays, fp
-    ctx.stash = model._train_ws   # the stash this node differentiates: a later apply(train=True) replaces it
+    ctx.stash = model.stash   # the stash this node differentiates: a later apply(train=True) replaces it
     ctx.set_materialize_grads(False)   # an output the loss does not read stays NULL for the library, not a buffer of zeros
     keys.extend((lv, k) for lv, d in out.items() for k in d)   # handed back to the caller: the order of the returned tuple
     ctx.keys = list(keys)
@@ -61,44 +67,7 @@ class RenderFunction(torch.autograd.Function):
   @once_differentiable
   def backward(ctx, *grads):
     model = ctx.model
-    if model._train_ws is not ctx.stash:
-      raise L.NrfError('render_differentiable: another apply(train=True) / training step ran on this model since the forward; '
-                       'its activation stash is gone -- call backward() before the next training forward')
-    d_out = {}
-    for (lv, k), g in zip(ctx.keys, grads):
-      if g is not None and k in DIFFERENTIABLE:
-        d_out.setdefault(lv, {})[k] = g
-    grad = model.backward({'params': ctx.fp}, ctx.rays, d_out=d_out)
-    return grad, None, None, None, None, None, None
-
-
-RAY_KEYS = ('origins', 'directions', 'viewdirs')
-
-
-class RayRenderFunction(torch.autograd.Function):
-  """RenderFunction with the rays as differentiable inputs: forward under NRF_FLAG_RAY_GRADS, backward one nrf_backward_rays call."""
-
-  @staticmethod
-  def forward(ctx, flat, origins, directions, viewdirs, model, rays, warp_extra, rngs, opts, keys):
-    fp = P.FlatParams(flat.detach(), model.layout)
-    rays = dict(rays, origins=origins.detach(), directions=directions.detach())
-    if viewdirs is not None:
-      rays['viewdirs'] = viewdirs.detach()
-    out = model.apply({'params': fp}, rays, warp_extra, rngs=rngs, train=True, ray_grads=True, **opts)
-    ctx.model, ctx.rays, ctx.fp = model, rays, fp
-    ctx.stash = model._train_ws
-    ctx.set_materialize_grads(False)
-    keys.extend((lv, k) for lv, d in out.items() for k in d)
-    ctx.keys = list(keys)
-    tensors = tuple(out[lv][k] for lv, k in ctx.keys)
-    ctx.mark_non_differentiable(*(t for (lv, k), t in zip(ctx.keys, tensors) if k not in DIFFERENTIABLE))
-    return tensors
-
-  @staticmethod
-  @once_differentiable
-  def backward(ctx, *grads):
-    model = ctx.model
-    if model._train_ws is not ctx.stash:
+    if model.stash is not ctx.stash:
       raise L.NrfError('render_differentiable: another apply(train=True) / training step ran on this model since the forward; '
                        'its activation stash is gone -- call backward() before the next training forward')
     d_out = {}
@@ -111,11 +80,10 @@ class RayRenderFunction(torch.autograd.Function):
     if 'viewdirs' in want and not model.use_viewdirs:   # a model without viewdirs never reads them
       want.remove('viewdirs')
       rg['viewdirs'] = torch.zeros_like(ctx.rays['viewdirs'])
+    grad = model.backward({'params': ctx.fp}, ctx.rays, d_out=d_out, ray_grads=want)
     if want:
-      grad, got = model.backward({'params': ctx.fp}, ctx.rays, d_out=d_out, ray_grads=want)
+      grad, got = grad
       rg.update(got)
-    else:
-      grad = model.backward({'params': ctx.fp}, ctx.rays, d_out=d_out)
     return (grad if ctx.needs_input_grad[0] else None,) + tuple(rg.get(k) for k in RAY_KEYS) + (None,) * 6
 
 
@@ -135,6 +103,7 @@ def render_differentiable(model, flat_params, rays, warp_extra=None, rngs=None, 
   flat = flat_params.flat if isinstance(flat_params, P.FlatParams) else flat_params
   opts = dict(return_weights=return_weights, return_points=return_points, return_z_vals=return_z_vals, bf16=bf16)
   keys = []
+  ray_inputs = (None, None, None)
   if any(_requires_grad(rays.get(k)) for k in RAY_KEYS):
     if bf16:
       raise L.NrfError(f"render_differentiable(bf16={bf16!r}): gradients w.r.t. the rays (NRF_FLAG_RAY_GRADS) exist in the float32 mode only")
@@ -142,15 +111,12 @@ def render_differentiable(model, flat_params, rays, warp_extra=None, rngs=None, 
       # models.py:326-329: the condition then reads the directions themselves; named as the viewdirs input, their gradient
       # through the condition joins the one through the sample points in autograd's own sum
       rays = dict(rays, viewdirs=rays['directions'])
-    tensors = RayRenderFunction.apply(flat, rays['origins'], rays['directions'], rays.get('viewdirs'), model, rays, warp_extra, rngs,
-                                      opts, keys)
-  else:
-    tensors = RenderFunction.apply(flat, model, rays, warp_extra, rngs, opts, keys)
+    ray_inputs = tuple(rays.get(k) for k in RAY_KEYS)
+  tensors = RenderFunction.apply(flat, *ray_inputs, model, rays, warp_extra, rngs, opts, keys)
   out = {}
   for (lv, k), t in zip(keys, tensors):
     out.setdefault(lv, {})[k] = t
   return out
-
 
 
 _camera_ws = {}   # device -> the cached workspace of the camera-table reverse passes

@@ -34,7 +34,9 @@ class GraphedChunkRenderer:
     self.model = model
     self.use_warp = use_warp
     self.bf16 = bf16   # NRF_FLAG_BF16 inference mode (bfloat16 MLP operands)
-    self._slots = {}   # key -> (graph, static inputs, static outputs); insertion-ordered, oldest evicted
+    # key -> (graph, static inputs, static outputs, the call's CallRecord: its workspace lives as long as the graph that points into it)
+    self._slots = {}   # insertion-ordered, oldest evicted
+    self._generation = model.generation   # the model's workspace generation the slots were captured under
     self.captures = 0
 
   def _capture(self, fp, rays, warp_extra):
@@ -51,7 +53,7 @@ class GraphedChunkRenderer:
     with torch.cuda.graph(graph):
       call(outs)
     self.captures += 1
-    return graph, ins, outs
+    return graph, ins, outs, model.last_call
 
   def __call__(self, key_0, key_1, params, rays, warp_extra):
     # the static buffers are overwritten by the next replay: a plain model_fn caller gets copies
@@ -66,6 +68,9 @@ class GraphedChunkRenderer:
     # every scalar of lib.StepScalars is part of the key: a replay would otherwise render with the captured value
     scalars = tuple(float((warp_extra or {}).get(k, 0.0)) for k in ('alpha', 'time_alpha'))
     key = (n, params.flat.data_ptr(), scalars, 'viewdirs' in rays, tuple(sorted((rays.get('metadata') or {}).keys())))
+    if self._generation != self.model.generation:   # a workspace option replaced the plans: every captured one is stale
+      self._slots.clear()
+      self._generation = self.model.generation
     slot = self._slots.get(key)
     if slot is None:
       # every chunk size has its own workspace (descriptor tables included), so graphs of different sizes coexist

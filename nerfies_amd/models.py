@@ -10,7 +10,7 @@ library through the C-ABI (include/nerfies_amd.h).  Differences forced by the mi
 import ctypes as C
 import os
 import dataclasses
-from typing import Any, Dict, Mapping, Optional, Sequence, Tuple
+from typing import Any, Dict, Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -20,6 +20,15 @@ from nerfies_amd import params as P
 
 def _ptr(t: Optional[torch.Tensor]):
   return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _ref(struct):
+  return None if struct is None else C.byref(struct)
+
+
+def _stream(device):
+  """The current stream of `device`, as the `stream` argument of a library call."""
+  return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _f32(t, device):
@@ -48,6 +57,56 @@ def rng_seed_of(coarse_key: int, fine_key: int) -> int:
   for k in (coarse_key, fine_key):
     seed = (seed * 0x9E3779B97F4A7C15 + int(k)) & 0xFFFFFFFFFFFFFFFF
   return seed
+
+
+class CallRecord(NamedTuple):
+  """One library call's mode and memory: what `NerfModel.stash` holds for `backward`, and what a captured graph keeps so that the
+  workspace its launches point into lives as long as the graph."""
+  num_rays: int      # first, then the workspace: a record still indexes like the (B, ws) pair the stash used to be
+  ws: torch.Tensor   # the workspace the call ran in
+  flags: int         # the NRF_FLAG_* word of the call
+  generation: int    # NerfModel.generation at the call: it moves when a workspace option replaces the plans
+
+
+def _ray_grad_names(names, allowed, where, what):
+  names = tuple(names)
+  if set(names) - set(allowed):
+    raise L.NrfError(f"{where}(ray_grads=...): {sorted(names)} -- {what}")
+  return names
+
+
+def _background_struct(background, device):
+  """-> (lib.Background or None, its point count, the tensors it points into)."""
+  if background is None:
+    return None, 0, []
+  pts = _f32(background['points'], device).reshape(-1, 3)
+  head = (float(background.get('weight', 1.0)), float(background.get('alpha', -2.0)), float(background.get('scale', 0.001)))
+  if background.get('warp_ids') is not None:   # the caller drew ids and noise (parity runs)
+    ids = _ids(background['warp_ids'], device).reshape(-1)
+    return L.Background(pts.shape[0], _ptr(pts), _ptr(ids), *head, None, 0, 0.0), pts.shape[0], [pts, ids]
+  choices = _ids(background['id_choices'], device).reshape(-1)   # the library draws them (training.py:121-126)
+  bg = L.Background(pts.shape[0], _ptr(pts), None, *head, _ptr(choices), choices.numel(), float(background.get('noise_std', 0.001)))
+  return bg, pts.shape[0], [pts, choices]
+
+
+def _elastic_struct(elastic):
+  if elastic is None:
+    return None
+  method = elastic.get('reduce_method', 'weight')
+  if method not in L.ELASTIC_REDUCE:
+    raise L.NrfError(f'unknown elastic_reduce_method {method!r}')
+  ltype = elastic.get('loss_type', 'log_svals')
+  if ltype not in L.ELASTIC_TYPE:
+    raise L.NrfError(f"elastic_loss_type {ltype!r} is not built (one of {sorted(L.ELASTIC_TYPE)}; 'nr' produces NaNs in "
+                     'the reference itself, training.py:58)')
+  return L.Elastic(float(elastic.get('weight', 0.0)), L.ELASTIC_REDUCE[method], float(elastic.get('eps', 1e-6)),
+                   float(elastic.get('alpha', -2.0)), float(elastic.get('scale', 0.03)), L.ELASTIC_TYPE[ltype])
+
+
+def _warp_reg_struct(warp_reg):
+  if warp_reg is None:
+    return None
+  return L.WarpReg(float(warp_reg.get('weight', 0.0)), float(warp_reg.get('alpha', -2.0)), float(warp_reg.get('scale', 0.001)))
 
 
 def _act_name(a):
@@ -109,6 +168,9 @@ class NerfModel:
     self._layout = None
     self._ws = {}
     self._lib = None
+    self.stash = None      # the CallRecord of the last training forward / fused step: what `backward` differentiates
+    self.last_call = None  # the CallRecord of the last apply / loss_and_grad, training or not (what a graph capture keeps)
+    self.generation = 0    # bumped by every workspace option: records of an older generation describe plans that no longer exist
 
   # models.py:121-131
   @property
@@ -187,6 +249,7 @@ class NerfModel:
       'translation': dict(skips=(4,), min_freq_log2=0, max_freq_log2=None, use_identity_map=True, metadata_encoder_num_freqs=1),
   }
   _WARP_KW_TRUNK = {'se3': ('trunk_depth', 'trunk_width'), 'translation': ('depth', 'hidden_channels')}
+  _train_ws = property(lambda self: self.stash)   # the stash under its earlier, private name
 
   def _warp_trunk_shape(self):
     kw = dict(self.warp_kwargs or {})
@@ -248,8 +311,9 @@ class NerfModel:
     self._drop_workspaces()
 
   def _drop_workspaces(self):
+    self.generation += 1
     self._ws = {}
-    self._train_ws = None
+    self.stash = self.last_call = None
 
   @property
   def layout(self) -> P.ParamLayout:
@@ -278,30 +342,38 @@ class NerfModel:
       return L.NRF_FLAG_BF16 | L.NRF_FLAG_WARP_F32
     return L.NRF_FLAG_BF16
 
+  def flags(self, train=False, bf16=False, no_warp=False, jacobian=False, ray_grads=False) -> int:
+    """The NRF_FLAG_* word of a call: the one place where a mode becomes bits."""
+    return (L.NRF_FLAG_TRAIN if train else 0) | self.bf16_flags(bf16) | (L.NRF_FLAG_NO_WARP if no_warp else 0) | \
+        (L.NRF_FLAG_WARP_JACOBIAN if jacobian else 0) | (L.NRF_FLAG_RAY_GRADS if ray_grads else 0)
+
   def check_mode(self, bf16, train: bool = False):
     """Raises NrfError with the library's own message when this model cannot run in the `bf16` mode (a moved skip or an rgb
     branch deeper than one layer exist in the float32 chains only): what the drivers ask before they load data or capture a graph."""
     nbytes = C.c_size_t(0)
-    flags = (L.NRF_FLAG_TRAIN if train else 0) | self.bf16_flags(bf16)
-    L.check(self.lib.nrf_workspace_bytes(self.handle, 1, flags, C.byref(nbytes)), self.lib)
+    L.check(self.lib.nrf_workspace_bytes(self.handle, 1, self.flags(train, bf16), C.byref(nbytes)), self.lib)
 
   def workspace(self, num_rays: int, train: bool, device, num_background_points: int = 0, elastic: bool = False,
                 jacobian: bool = False, bf16=False, ray_grads: bool = False) -> torch.Tensor:
-    # the TRAINING layout depends on it (bf16 stashes instead of the fp32 ones); so does an 'x3' inference plan (its weight streams)
-    bf16 = 'x3' if bf16 in ('x3', 'x3mlp') else (bf16 if train else False)
-    key = (int(num_rays), bool(train), str(device), int(num_background_points), bool(elastic), bool(jacobian), bf16)
-    if ray_grads:   # NRF_FLAG_RAY_GRADS: a larger layout of its own; every other key stays what it was
-      key += ('ray_grads',)
+    return self._record(num_rays, self.flags(train, bf16, jacobian=jacobian, ray_grads=ray_grads), device, num_background_points,
+                        elastic).ws
+
+  def _record(self, num_rays, flags, device, num_background_points=0, elastic=False) -> CallRecord:
+    """The CallRecord of a call under `flags`, its workspace taken from the cache.  The cache is keyed by the word the workspace is
+    sized for: the call's, less the bits that change no layout -- adding a flag needs no second edit here unless it is one of those."""
+    plan = flags & ~L.NRF_FLAG_NO_WARP   # a call that skips the warp field runs in the workspace of one that does not
+    if plan & L.NRF_FLAG_BF16X3:   # an 'x3' inference plan has its own weight streams, with or without the float32 trunk
+      plan &= ~L.NRF_FLAG_WARP_F32
+    elif not plan & L.NRF_FLAG_TRAIN:   # only the TRAINING layout depends on bf16 (bf16 stashes instead of the fp32 ones)
+      plan &= ~(L.NRF_FLAG_BF16 | L.NRF_FLAG_WARP_F32)
+    key = (plan, int(num_rays), str(device), int(num_background_points), bool(elastic))
     ws = self._ws.get(key)
     if ws is None:
       nbytes = C.c_size_t(0)
-      flags = (L.NRF_FLAG_TRAIN if train else 0) | (L.NRF_FLAG_WARP_JACOBIAN if jacobian else 0) | self.bf16_flags(bf16) | \
-          (L.NRF_FLAG_RAY_GRADS if ray_grads else 0)
-      L.check(self.lib.nrf_workspace_bytes_ex(self.handle, num_rays, flags,
-                                              int(num_background_points), int(bool(elastic)), C.byref(nbytes)), self.lib)
-      ws = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=device)
-      self._ws[key] = ws
-    return ws
+      L.check(self.lib.nrf_workspace_bytes_ex(self.handle, num_rays, plan, int(num_background_points), int(bool(elastic)),
+                                              C.byref(nbytes)), self.lib)
+      ws = self._ws[key] = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=device)
+    return CallRecord(int(num_rays), ws, flags, self.generation)
 
   def flat_params(self, variables, device) -> P.FlatParams:
     params = variables['params'] if isinstance(variables, dict) and 'params' in variables else variables
@@ -423,14 +495,12 @@ class NerfModel:
         setattr(lo, k, _ptr(t))
       ret[name] = d
     scal = _scalars(warp_extra)
-    ws = self.workspace(B, train, device, jacobian=bool(jac_levels), bf16=bf16, ray_grads=ray_grads)
+    flags = self.flags(train, bf16, no_warp=self.use_warp and not warp_on, jacobian=bool(jac_levels), ray_grads=ray_grads)
+    rec = self.last_call = self._record(B, flags, device)
     if train:
-      self._train_ws = (B, ws)   # the stash `backward` differentiates (fp32 or bf16 layout), and the batch size it is for
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    flags = (L.NRF_FLAG_TRAIN if train else 0) | (L.NRF_FLAG_NO_WARP if self.use_warp and not warp_on else 0) | \
-        self.bf16_flags(bf16) | (L.NRF_FLAG_WARP_JACOBIAN if jac_levels else 0) | (L.NRF_FLAG_RAY_GRADS if ray_grads else 0)
+      self.stash = rec   # what `backward` differentiates (fp32 or bf16 layout), and the batch size it is for
     L.check(self.lib.nrf_forward(self.handle, _ptr(fp.flat), C.byref(rays), C.byref(scal), C.byref(rnd), C.byref(out),
-                                 flags, _ptr(ws), ws.numel() * 4, stream), self.lib)
+                                 flags, _ptr(rec.ws), rec.ws.numel() * 4, _stream(device)), self.lib)
     del keep, keep2
     return ret
 
@@ -443,41 +513,31 @@ class NerfModel:
     `ray_grads`: True, or an iterable of 'origins' / 'directions' / 'viewdirs' -- after `apply(..., train=True, ray_grads=True)`;
     returns (grad, {name: (B,3) gradient w.r.t. rays_dict[name]}) through nrf_backward_rays.  True asks for 'viewdirs' only where
     the model and the rays have them."""
+    stash = self.stash
+    if stash is None:
+      raise L.NrfError('backward() needs a preceding apply(..., train=True)')
     device = torch.as_tensor(rays_dict['origins']).device
     fp = self.flat_params(variables, device)
     rays, keep = self._rays_struct(rays_dict, device)
+    B = rays.num_rays
+    if stash.num_rays != B:
+      raise L.NrfError(f'backward(): the stashed forward was run on {stash.num_rays} rays, not {B}')
+    ws = stash.ws   # the library also refuses a stash whose workspace plan was replaced by another call (NRF_E_STATE)
     grad = grad_out if grad_out is not None else torch.empty_like(fp.flat)
-    dc = None if d_rgb_coarse is None else _f32(d_rgb_coarse, device)
-    df = None if d_rgb_fine is None else _f32(d_rgb_fine, device)
-    stash = getattr(self, '_train_ws', None)
-    if stash is None:
-      raise L.NrfError('backward() needs a preceding apply(..., train=True)')
-    if stash[0] != rays.num_rays:
-      raise L.NrfError(f'backward(): the stashed forward was run on {stash[0]} rays, not {rays.num_rays}')
-    ws = stash[1]   # the library also refuses a stash whose workspace plan was replaced by another call (NRF_E_STATE)
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    og, keep2 = self._output_grads(d_out or {}, {'coarse': d_rgb_coarse, 'fine': d_rgb_fine}, B, device)
+    tail = (_ptr(grad), _ptr(ws), ws.numel() * 4, _stream(device))
     if ray_grads:
-      has_vd = bool(self.use_viewdirs) and 'viewdirs' in rays_dict
-      names = (('origins', 'directions') + (('viewdirs',) if has_vd else ())) if ray_grads is True else tuple(ray_grads)
-      if set(names) - {'origins', 'directions', 'viewdirs'}:
-        raise L.NrfError(f"backward(ray_grads=...): {sorted(names)} -- the rays' differentiable entries are 'origins', 'directions', 'viewdirs'")
-      rg_out = {k: torch.empty(rays.num_rays, 3, device=device) for k in names}
+      if ray_grads is True:
+        ray_grads = ('origins', 'directions') + (('viewdirs',) if self.use_viewdirs and 'viewdirs' in rays_dict else ())
+      names = _ray_grad_names(ray_grads, ('origins', 'directions', 'viewdirs'), 'backward',
+                              "the rays' differentiable entries are 'origins', 'directions', 'viewdirs'")
+      rg_out = {k: torch.empty(B, 3, device=device) for k in names}
       rg = L.RayGrads(*(_ptr(rg_out.get(k)) for k in ('origins', 'directions', 'viewdirs')))
-      og, keep2 = self._output_grads(d_out or {}, {'coarse': dc, 'fine': df}, rays.num_rays, device)
-      L.check(self.lib.nrf_backward_rays(self.handle, _ptr(fp.flat), C.byref(rays), C.byref(og), C.byref(rg), _ptr(grad), _ptr(ws),
-                                         ws.numel() * 4, stream), self.lib)
-      del keep, keep2
-      return grad, rg_out
-    if d_out is None:
-      L.check(self.lib.nrf_backward(self.handle, _ptr(fp.flat), C.byref(rays), _ptr(dc), _ptr(df), _ptr(grad), _ptr(ws),
-                                    ws.numel() * 4, stream), self.lib)
+      L.check(self.lib.nrf_backward_rays(self.handle, _ptr(fp.flat), C.byref(rays), C.byref(og), C.byref(rg), *tail), self.lib)
     else:
-      og, keep2 = self._output_grads(d_out, {'coarse': dc, 'fine': df}, rays.num_rays, device)
-      L.check(self.lib.nrf_backward_ex(self.handle, _ptr(fp.flat), C.byref(rays), C.byref(og), _ptr(grad), _ptr(ws),
-                                       ws.numel() * 4, stream), self.lib)
-      del keep2
-    del keep
-    return grad
+      L.check(self.lib.nrf_backward_ex(self.handle, _ptr(fp.flat), C.byref(rays), C.byref(og), *tail), self.lib)
+    del keep, keep2
+    return (grad, rg_out) if ray_grads else grad
 
   def _output_grads(self, d_out, d_rgb, B, device):
     """lib.OutputGrads of a `backward(d_out=...)` dict.  Every buffer is read by the kernels at its full size, so the shapes are
@@ -533,40 +593,17 @@ class NerfModel:
     grad = grad_out if grad_out is not None else torch.empty_like(fp.flat)
     stats = stats_out if stats_out is not None else torch.empty(L.NRF_NUM_STATS, device=device)
     scal = _scalars(warp_extra, dynamic)
-    bg, nbg, keep3 = None, 0, []
-    if background is not None:
-      pts = _f32(background['points'], device).reshape(-1, 3)
-      nbg = pts.shape[0]
-      if background.get('warp_ids') is not None:   # the caller drew ids and noise (parity runs)
-        ids = _ids(background['warp_ids'], device).reshape(-1)
-        keep3 = [pts, ids]
-        bg = L.Background(nbg, _ptr(pts), _ptr(ids), float(background.get('weight', 1.0)), float(background.get('alpha', -2.0)),
-                          float(background.get('scale', 0.001)), None, 0, 0.0)
-      else:                                        # the library draws them (training.py:121-126)
-        choices = _ids(background['id_choices'], device).reshape(-1)
-        keep3 = [pts, choices]
-        bg = L.Background(nbg, _ptr(pts), None, float(background.get('weight', 1.0)), float(background.get('alpha', -2.0)),
-                          float(background.get('scale', 0.001)), _ptr(choices), choices.numel(), float(background.get('noise_std', 0.001)))
-    el = None
-    if elastic is not None:
-      method = elastic.get('reduce_method', 'weight')
-      if method not in L.ELASTIC_REDUCE:
-        raise L.NrfError(f'unknown elastic_reduce_method {method!r}')
-      ltype = elastic.get('loss_type', 'log_svals')
-      if ltype not in L.ELASTIC_TYPE:
-        raise L.NrfError(f"elastic_loss_type {ltype!r} is not built (one of {sorted(L.ELASTIC_TYPE)}; 'nr' produces NaNs in "
-                         'the reference itself, training.py:58)')
-      el = L.Elastic(float(elastic.get('weight', 0.0)), L.ELASTIC_REDUCE[method], float(elastic.get('eps', 1e-6)),
-                     float(elastic.get('alpha', -2.0)), float(elastic.get('scale', 0.03)), L.ELASTIC_TYPE[ltype])
-    wr = None
-    if warp_reg is not None:
-      wr = L.WarpReg(float(warp_reg.get('weight', 0.0)), float(warp_reg.get('alpha', -2.0)), float(warp_reg.get('scale', 0.001)))
-    ws = self.workspace(rays.num_rays, True, device, nbg, el is not None, bf16=bf16, ray_grads=ray_grads is not None)
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    if ray_grads is not None:
-      names = tuple(ray_grads)
-      if set(names) - {'origins', 'directions'}:
-        raise L.NrfError(f"loss_and_grad(ray_grads=...): {sorted(names)} -- the fused step returns 'origins' and 'directions'")
+    bg, nbg, keep3 = _background_struct(background, device)
+    el, wr = _elastic_struct(elastic), _warp_reg_struct(warp_reg)
+    flags = self.flags(True, bf16, ray_grads=ray_grads is not None)
+    rec = self.stash = self.last_call = self._record(rays.num_rays, flags, device, nbg, el is not None)
+    head = (self.handle, _ptr(fp.flat), C.byref(rays), _ptr(target), C.byref(scal), C.byref(rnd), _ref(bg), _ref(el), _ref(wr))
+    tail = (_ptr(grad), _ptr(stats), _ptr(rec.ws), rec.ws.numel() * 4, _stream(device))
+    # each entry takes the word without the bits its ABI implies: _ex the bf16 bits, _rays (float32 only) none
+    if ray_grads is None:
+      L.check(self.lib.nrf_train_step_loss_grad_ex(*head, flags & ~L.NRF_FLAG_TRAIN, *tail), self.lib)
+    else:
+      names = _ray_grad_names(ray_grads, ('origins', 'directions'), 'loss_and_grad', "the fused step returns 'origins' and 'directions'")
       rg_out = {k: (ray_grads_out or {}).get(k) for k in names}
       for k in names:
         if rg_out[k] is None:
@@ -574,20 +611,9 @@ class NerfModel:
         elif tuple(rg_out[k].shape) != (rays.num_rays, 3) or rg_out[k].dtype != torch.float32 or not rg_out[k].is_contiguous():
           raise L.NrfError(f'loss_and_grad(ray_grads_out=...): {k!r} must be a contiguous float32 ({rays.num_rays}, 3) tensor')
       rg = L.RayGrads(_ptr(rg_out.get('origins')), _ptr(rg_out.get('directions')), None)
-      L.check(self.lib.nrf_train_step_loss_grad_rays(self.handle, _ptr(fp.flat), C.byref(rays), _ptr(target), C.byref(scal),
-                                                     C.byref(rnd), C.byref(bg) if bg is not None else None,
-                                                     C.byref(el) if el is not None else None,
-                                                     C.byref(wr) if wr is not None else None, 0, C.byref(rg),
-                                                     _ptr(grad), _ptr(stats), _ptr(ws), ws.numel() * 4, stream), self.lib)
-      del keep, keep2, keep3
-      return grad, stats, rg_out
-    L.check(self.lib.nrf_train_step_loss_grad_ex(self.handle, _ptr(fp.flat), C.byref(rays), _ptr(target), C.byref(scal),
-                                                 C.byref(rnd), C.byref(bg) if bg is not None else None,
-                                                 C.byref(el) if el is not None else None,
-                                                 C.byref(wr) if wr is not None else None, self.bf16_flags(bf16),
-                                                 _ptr(grad), _ptr(stats), _ptr(ws), ws.numel() * 4, stream), self.lib)
+      L.check(self.lib.nrf_train_step_loss_grad_rays(*head, flags & ~(L.NRF_FLAG_TRAIN | L.NRF_FLAG_RAY_GRADS), C.byref(rg), *tail), self.lib)
     del keep, keep2, keep3
-    return grad, stats
+    return (grad, stats) if ray_grads is None else (grad, stats, rg_out)
 
   def warp_points(self, variables, points, warp_ids, warp_extra):
     """model.create_warp_field(model, num_batch_dims=1).apply(points, ids, warp_extra, False, False)
@@ -602,9 +628,8 @@ class NerfModel:
     ws = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=device)
     out = torch.empty(n, 3, device=device)
     scal = _scalars(warp_extra)
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     L.check(self.lib.nrf_warp_points(self.handle, _ptr(fp.flat), _ptr(pts), _ptr(ids), n, C.byref(scal), _ptr(out), _ptr(ws),
-                                     ws.numel() * 4, stream), self.lib)
+                                     ws.numel() * 4, _stream(device)), self.lib)
     return out.reshape(torch.as_tensor(points).shape)
 
   def profile_enable(self, on=True):

@@ -51,19 +51,17 @@ class Optimizer:
     bumps self.step."""
     lib = L.load_library()
     p = self.target.flat
-    stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
     L.check(lib.nrf_adam_step_dynamic(C.c_void_p(p.data_ptr()), C.c_void_p(self.m.data_ptr()), C.c_void_p(self.v.data_ptr()),
                                       C.c_void_p(grad.data_ptr()), p.numel(), self.beta1, self.beta2, self.eps,
-                                      C.c_void_p(dynamic.dev.data_ptr()), stream), lib)
+                                      C.c_void_p(dynamic.dev.data_ptr()), models._stream(p.device)), lib)
     return self
 
   def apply_gradient(self, grad: torch.Tensor, learning_rate: float, grad_scale: float = 1.0):
     lib = L.load_library()
     p = self.target.flat
-    stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
     L.check(lib.nrf_adam_step(C.c_void_p(p.data_ptr()), C.c_void_p(self.m.data_ptr()), C.c_void_p(self.v.data_ptr()),
                               C.c_void_p(grad.data_ptr()), p.numel(), float(learning_rate), self.beta1, self.beta2,
-                              self.eps, int(self.step), float(grad_scale), stream), lib)
+                              self.eps, int(self.step), float(grad_scale), models._stream(p.device)), lib)
     self.step += 1
     return self
 
@@ -83,8 +81,7 @@ class DynamicScalars:
                          1.0 - beta1 ** t, 1.0 - beta2 ** t, float(grad_scale), 0.0, int(rng_seed) & 0xFFFFFFFFFFFFFFFF,
                          int(rng_offset) & 0xFFFFFFFFFFFFFFFF)
     lib = L.load_library()
-    stream = C.c_void_p(torch.cuda.current_stream(self.dev.device).cuda_stream)
-    L.check(lib.nrf_dynamic_scalars_write(C.c_void_p(self.dev.data_ptr()), C.byref(v), stream), lib)
+    L.check(lib.nrf_dynamic_scalars_write(C.c_void_p(self.dev.data_ptr()), C.byref(v), models._stream(self.dev.device)), lib)
 
 
 @dataclasses.dataclass
@@ -208,7 +205,7 @@ class CameraRefiner:
     self._ws = None
 
   def _stream(self):
-    return C.c_void_p(torch.cuda.current_stream(self.deltas.device).cuda_stream)
+    return models._stream(self.deltas.device)
 
   def compose(self) -> torch.Tensor:
     """The camera table of the current deltas (nrf_camera_table_compose), in the refiner's own buffer."""
@@ -387,6 +384,7 @@ class GraphedTrainStep:
       self.graph_adam = torch.cuda.CUDAGraph()
       with torch.cuda.graph(self.graph_adam):
         opt.apply_gradient_dynamic(self._grad, self.dyn)
+    self.record = model.stash   # the captured loss_and_grad: the graph's launches point into its workspace, so it lives with the graph
 
   @staticmethod
   def _static_copy(batch, dev):
@@ -434,6 +432,9 @@ class GraphedTrainStep:
     self.stats_static = stats
 
   def __call__(self, rng_key, scalar_params: Optional[ScalarParams] = None, warp_alpha=None, time_alpha=None, batch=None):
+    if self.record.generation != self.model.generation:   # the captured plan no longer exists: nothing may be written or replayed
+      raise L.NrfError('GraphedTrainStep: a workspace option changed since the capture (set_chain_tile_rows / set_bf16_wgrad_merge); '
+                       'build a new GraphedTrainStep')
     sp = scalar_params or self.sp
     for name in ('background_loss_weight', 'background_noise_std', 'warp_reg_loss_weight', 'warp_reg_loss_alpha', 'warp_reg_loss_scale'):
       if getattr(sp, name) != getattr(self.sp, name):   # by-value arguments of the captured launches

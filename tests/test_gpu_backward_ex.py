@@ -91,11 +91,23 @@ def _nocond():
 
 
 def test_rgb_only_is_bit_identical_with_nrf_backward():
+  import ctypes as C
+  from nerfies_amd import lib as L
   spec, model, fp, gb = _nocond()
   model.apply({'params': fp}, gb, {}, train=True)
   cot = _to_gpu(_cotangents(spec, B, ('rgb',), seed=7))
   dc, df = cot['coarse']['rgb'], cot['fine']['rgb']
-  old = model.backward({'params': fp}, gb, dc, df).clone()
+
+  def nrf_backward():
+    """The rgb-only export, which NerfModel.backward no longer goes through: a direct call on the model's stash."""
+    rays, keep = model._rays_struct(gb, H.DEV)
+    grad, ws = torch.empty_like(fp.flat), model.stash.ws
+    L.check(model.lib.nrf_backward(model.handle, fp.flat.data_ptr(), C.byref(rays), dc.data_ptr(), df.data_ptr(), grad.data_ptr(),
+                                   ws.data_ptr(), ws.numel() * 4, torch.cuda.current_stream().cuda_stream), model.lib)
+    torch.cuda.synchronize()   # `keep` holds the rays' buffers until the launches are through
+    return grad
+
+  old = nrf_backward()
   assert old.abs().max().item() > 0
   assert torch.equal(model.backward({'params': fp}, gb, d_out=cot), old)
   assert torch.equal(model.backward({'params': fp}, gb, dc, d_out={'fine': {'rgb': df}}), old)   # positional and dict mixed
@@ -105,7 +117,8 @@ def test_rgb_only_is_bit_identical_with_nrf_backward():
   assert torch.equal(model.backward({'params': fp}, gb, d_out=zeros), old)
   # no cotangent at all: a zero gradient
   assert model.backward({'params': fp}, gb, d_out={}).abs().max().item() == 0.0
-  assert torch.equal(model.backward({'params': fp}, gb, dc, df), old)   # ... and the old entry is what it was, after all of it
+  assert torch.equal(model.backward({'params': fp}, gb, dc, df), old)   # the positional form is the same call
+  assert torch.equal(nrf_backward(), old)   # ... and the old entry is what it was, after all of it
 
 
 def test_bf16_training_mode_follows_the_float32_gradient():

@@ -46,7 +46,7 @@ def _run(kw, mode):
     ws = model.workspace(B, True, H.DEV)
   else:
     fwd = model.apply({'params': fp}, gb, {}, train=True, return_weights=True, bf16=mode == 'bf16', ray_grads=mode.startswith('rays'))
-    ws = model._train_ws[1]
+    ws = model.stash.ws
     if mode == 'plain':
       model.backward({'params': fp}, gb, gc['coarse']['rgb'], gc['fine']['rgb'])
     else:

@@ -176,3 +176,62 @@ def test_graph_replay_in_the_bf16_mode_with_warp_elastic_background():
     for dst, src in ((sg.optimizer.target.flat, se.optimizer.target.flat), (sg.optimizer.m, se.optimizer.m), (sg.optimizer.v, se.optimizer.v)):
       dst.copy_(src)
   assert sg.optimizer.step == se.optimizer.step == 3
+
+
+def _tiny_warp(seed, nbg=0):
+  """The smallest model with a warp field (tests/test_ray_grads_host.py::_model) and 37 rays: no multiple of the 32- or 64-row tiles."""
+  from nerfies_amd import models, training
+
+  class Cfg:
+    num_coarse_samples, num_fine_samples, num_nerf_point_freqs, use_stratified_sampling = 8, 6, 4, False
+    use_warp, warp_field_type, num_warp_freqs = True, 'se3', 4
+  B = 37
+  model, fp = models.construct_nerf(11, Cfg, B, [0], [0], [0, 1], 0.1, 1.0, device=DEV)
+  batch = _batch(B, seed, nbg=nbg)
+  batch['metadata'] = {'warp': torch.randint(0, 2, (B, 1), generator=torch.Generator().manual_seed(seed)).to(DEV)}
+  return model, training.TrainState(optimizer=training.Optimizer(fp), warp_alpha=1.5), batch
+
+
+def test_renderer_recaptures_after_a_workspace_option():
+  """set_chain_tile_rows replaces the plans and drops the cached workspaces: the renderer's slot owns the workspace its graph points
+  into, and a slot of an older generation is captured again instead of replayed."""
+  from nerfies_amd import evaluation
+  model, state, batch = _tiny_warp(80)
+  fp, we = state.optimizer.target, state.warp_extra
+  rays = {k: batch[k] for k in ('origins', 'directions', 'metadata')}
+  renderer = evaluation.GraphedChunkRenderer(model)
+  renderer(0, 1, fp, rays, we)
+  assert renderer.captures == 1
+  model.set_chain_tile_rows(32)
+  got = renderer(0, 1, fp, rays, we)
+  assert renderer.captures == 2
+  eager = model.apply({'params': fp}, rays, we)
+  again = renderer(0, 1, fp, rays, we)
+  assert renderer.captures == 2   # a replay
+  for lv, d in eager.items():
+    for k, t in d.items():
+      assert torch.equal(got[lv][k], t) and torch.equal(again[lv][k], t), (lv, k)
+  (slot,) = renderer._slots.values()
+  assert slot[3].ws is model.workspace(37, False, DEV) and slot[3].generation == model.generation
+
+
+def test_train_step_refuses_to_replay_after_a_workspace_option():
+  """The captured step is not replayed in a plan that no longer exists, and nothing is written before the refusal."""
+  from nerfies_amd import lib as L, training
+  model, state, batch = _tiny_warp(81, nbg=5)
+  sp = training.ScalarParams(learning_rate=1e-3, background_loss_weight=1.0)
+  gstep = training.GraphedTrainStep(model, state, batch, sp, use_background_loss=True)
+  gstep(3)
+  opt = state.optimizer
+  torch.cuda.synchronize()
+  before, step = [t.clone() for t in (opt.target.flat, opt.m, opt.v)], opt.step
+  model.set_chain_tile_rows(32)
+  with pytest.raises(L.NrfError, match='a workspace option changed since the capture .*set_chain_tile_rows'):
+    gstep(4)
+  torch.cuda.synchronize()
+  assert opt.step == step == 1
+  for t, b in zip((opt.target.flat, opt.m, opt.v), before):
+    assert torch.equal(t, b)
+  stats = training.GraphedTrainStep(model, state, batch, sp, use_background_loss=True)(4)   # a new capture on the same state runs
+  assert np.isfinite(stats['fine']['loss/rgb'].item()) and np.isfinite(stats['background_loss'].item()) and opt.step == 2
+  assert not torch.equal(opt.target.flat, before[0])

@@ -2,7 +2,7 @@
 outputs w.r.t. the ray origins, directions and viewdirs (NRF_FLAG_RAY_GRADS, float32 mode).
 
 The float64 reference is torch.autograd over oracle.nerf_model_apply with requires_grad rays, on the HIP path's own ReLU pattern and
-fine depths (the masks are read from the stash of the ray-gradient forward itself, model._train_ws).  Each of the three tensors has to
+fine depths (the masks are read from the stash of the ray-gradient forward itself, model.stash).  Each of the three tensors has to
 lie within helpers.grad_tol of its oracle max-abs.  The directions are 1.7 x a unit vector while the viewdirs stay unit, so the |d|
 factor of the compositing distances (model_utils.py:104-110) cannot go missing; shapes as tests/test_gpu_backward_ex.py: B = 7 leaves
 a 4-rays-per-block remainder, 80 fine samples are two 64-lane chunks per ray, 16 + 16 samples with the warp keep the tangent pass small."""
@@ -48,7 +48,7 @@ def _to_gpu(cot):
 def _stash_masks(model, spec, num_rays):
   """helpers.gpu_relu_masks on the stash of the last training forward, whatever flags it ran under (that helper looks the workspace
   up by the key of a plain training call)."""
-  ws = model._train_ws[1]
+  ws = model.stash.ws
   torch.cuda.synchronize()
   masks = {}
   for name, lv, rows in (('coarse', 0, num_rays * spec.num_coarse_samples),
