@@ -37,7 +37,11 @@
 extern "C" {
 #endif
 
-#define NRF_VERSION 650 /* 0.6.5: nrf_train_step_loss_grad_rays (the fused train step with ray gradients; nrf_workspace_bytes_ex accepts
+#define NRF_VERSION 660 /* 0.6.6: NRF_FLAG_FROZEN + nrf_loss_grad_rays: ray gradients with the field's parameters fixed (aligning a camera
+                           against a trained field).  A frozen stash keeps what nrf_backward_rays reads and nothing of the parameter
+                           gradient; nrf_backward_rays accepts grad_params == NULL on such a stash.  Plans without the flag, and every
+                           entry point that existed, are unchanged.
+                           0.6.5: nrf_train_step_loss_grad_rays (the fused train step with ray gradients; nrf_workspace_bytes_ex accepts
                            NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS together with the regularisers) and camera delta tables
                            (NRF_CAMERA_DELTA_ROW): nrf_camera_table_compose / _compose_backward.  Plans without the flag, and plans
                            with the flag but without regularisers, are unchanged.
@@ -260,6 +264,19 @@ typedef struct nrf_outputs {
                                      under the flag it is followed by the forward chain only, as on a model with a warp field (the 32-row
                                      reverse chain has no d-points section, so the reverse pass runs on 64-row tiles over the same stash) */
 
+#define NRF_FLAG_FROZEN 128u       /* since 0.6.6, only as NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS | NRF_FLAG_FROZEN (float32 mode) on nrf_forward /
+                                     nrf_workspace_bytes[_ex]: the field's parameters are constants of this call, its stash serves
+                                     nrf_backward_rays ONLY.  The plan keeps what the forward itself uses, the rendered outputs, the ReLU
+                                     sign words and the posenc stash of the NeRF chains, d raw / d points / the per-ray sums, the transposed
+                                     weight images of the d-points section, and -- with a warp field -- the primal trunk input, sign words
+                                     and (w, v) rows, the tangent (dw, dv) rows and the warp Jacobians.  It holds NO activation stash, dY
+                                     image, SE3 reverse stash, wgrad slab / group / segment, reduce table or padded gradient image, and the
+                                     chains store none of them.  Any other word that carries the flag -- without NRF_FLAG_TRAIN or
+                                     NRF_FLAG_RAY_GRADS, with NRF_FLAG_BF16 / NRF_FLAG_BF16X3 / NRF_FLAG_WARP_JACOBIAN -- and nrf_workspace_bytes_ex
+                                     with background points or the elastic switch: NRF_E_UNSUPPORTED.  On a frozen stash nrf_backward /
+                                     nrf_backward_ex return NRF_E_STATE; nrf_backward_rays takes grad_params == NULL (see there).
+                                     NRF_OPT_CHAIN_TILE_ROWS is followed by the forward chain only, as under NRF_FLAG_RAY_GRADS */
+
 int nrf_version(void);
 const char* nrf_last_error(void);
 
@@ -330,7 +347,13 @@ typedef struct nrf_ray_grads {
  * stashed forward must have run with NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS (NRF_E_STATE otherwise); ray_grads NULL -> NRF_E_NULL; d_viewdirs for
  * a model without viewdirs, or with rays->viewdirs NULL -> NRF_E_UNSUPPORTED: all decided before any launch.  One wave per ray, no atomics:
  * d_origins / d_directions of two calls on one stash agree bit for bit (d_viewdirs reads the per-ray sums the reverse chain accumulates).
- * A cotangent on warped_points reaches the rays through g_s; `points` carries none (rebuild o + z d from z_vals in the caller). */
+ * A cotangent on warped_points reaches the rays through g_s; `points` carries none (rebuild o + z d from z_vals in the caller).
+ *
+ * Since 0.6.6, on a stash written under NRF_FLAG_FROZEN: grad_params must be NULL (a non-NULL pointer: NRF_E_STATE -- nothing of the
+ * parameter gradient was kept).  The call then runs composite_bwd, ONE 64-row NeRF data-gradient launch that writes d points and the
+ * per-ray sums and no dY image, the warped-point cotangent add and the ray stage -- no SE3 reverse chain (the warp Jacobians come from
+ * the forward's tangent passes), no condition / GLO / time-encoder gradient, no wgrad, no reduce pass.  grad_params == NULL on a stash
+ * that is not frozen stays NRF_E_NULL. */
 int nrf_backward_rays(nrf_handle h, const float* params, const nrf_rays* rays, const nrf_output_grads* grads,
                       const nrf_ray_grads* ray_grads, float* grad_params, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -427,6 +450,20 @@ int nrf_train_step_loss_grad_rays(nrf_handle h, const float* params, const nrf_r
                                   const nrf_step_scalars* scalars, const nrf_rand* rnd, const nrf_background* bg,
                                   const nrf_elastic* el, const nrf_warp_reg* wr, uint32_t flags, const nrf_ray_grads* ray_grads,
                                   float* grad_params, float* stats, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Since 0.6.6: the fused FROZEN step -- the gradients of MSE_coarse + MSE_fine (training.py:172, 261) w.r.t. the rays with the field's
+ * parameters fixed: what aligning a camera against a trained field needs (test-time pose alignment of a held-out frame).  One call:
+ * nrf_forward under NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS | NRF_FLAG_FROZEN, the fixed loss, then the reverse pass nrf_backward_rays runs on
+ * a frozen stash.  ray_grads->d_origins / d_directions / d_viewdirs (B,3) are OVERWRITTEN (any may be NULL, which skips it; ray_grads NULL
+ * -> NRF_E_NULL).  stats[NRF_NUM_STATS] (device, may be NULL): {mse_coarse, mse_fine, psnr_coarse, psnr_fine, loss_total, 0...} -- no
+ * regulariser is applied (they act on the field and never reach the rays), their entries are 0.  rays->viewdirs == NULL on a
+ * use_viewdirs model: the view term is folded into d_directions exactly as in nrf_train_step_loss_grad_rays (d_viewdirs then stays
+ * NRF_E_UNSUPPORTED).  The workspace comes from nrf_workspace_bytes(NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS | NRF_FLAG_FROZEN).  No
+ * allocation, no synchronisation, every launch on `stream`: capturable into a hipGraph.  The ray gradients agree with those of
+ * nrf_train_step_loss_grad_rays to the order of the float atomics behind dray and the rounding of d_rgb. */
+int nrf_loss_grad_rays(nrf_handle h, const float* params, const nrf_rays* rays, const float* target_rgb,
+                       const nrf_step_scalars* scalars, const nrf_rand* rnd, const nrf_ray_grads* ray_grads, float* stats,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* warping.SE3Field on arbitrary points with one warp id per point: model.create_warp_field(num_batch_dims=1)
  * .apply(points, metadata, warp_extra, False, False) (models.py:165-184, warping.py:355-389). */

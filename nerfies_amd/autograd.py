@@ -13,7 +13,9 @@ deltas, a learned lens correction), they enter `RenderFunction` as inputs of the
 backward is ONE nrf_backward_rays call that returns the parameter gradient and the three (B,3) ray gradients (float32 mode only).
 viewdirs = d / |d| is the caller's own torch expression, so autograd carries d_viewdirs on to the directions.  The 'points' output
 stays non-differentiable: rebuild o + z d from 'z_vals' in torch; a cotangent on 'warped_points' does reach the rays.  With no
-requires_grad ray the call is the one above: same flag word, same launches.
+requires_grad ray the call is the one above: same flag word, same launches.  When a ray requires grad and `flat_params` does not
+(test-time pose alignment against a trained field), the forward runs under NRF_FLAG_FROZEN: no activation stash is written and the
+backward stops at the rays (training.align_step / align_cameras are the fused form of that loop).
 
 Cameras: the rays themselves come differentiably from a camera table (nerfies_amd.camera.pack_cameras, (C, 24) on the device) through
 `CameraRaysFunction` (nrf_camera_table_rays / _rays_backward), world points go to pixels through `CameraProjectFunction`.  The
@@ -47,13 +49,17 @@ class RenderFunction(torch.autograd.Function):
   """forward: the rendered outputs of every level, flattened in the order of `ctx.keys`; backward: one nrf_backward_ex call on the
   stash the forward left, with whatever cotangents autograd delivers.  `origins` / `directions` / `viewdirs` are the rays as
   differentiable inputs, or None for what `rays` holds: when one of them needs a gradient the forward runs under NRF_FLAG_RAY_GRADS
-  and the backward is one nrf_backward_rays call instead."""
+  and the backward is one nrf_backward_rays call instead; when `flat` needs none, under NRF_FLAG_FROZEN as well."""
 
   @staticmethod
   def forward(ctx, flat, origins, directions, viewdirs, model, rays, warp_extra, rngs, opts, keys):
     fp = P.FlatParams(flat.detach(), model.layout)
     rays = dict(rays, **{k: t.detach() for k, t in zip(RAY_KEYS, (origins, directions, viewdirs)) if t is not None})
-    out = model.apply({'params': fp}, rays, warp_extra, rngs=rngs, train=True, ray_grads=any(ctx.needs_input_grad[1:4]), **opts)
+    ray_grads = any(ctx.needs_input_grad[1:4])
+    # a ray needs a gradient and the parameters do not (aligning a camera against a trained field): the forward runs frozen
+    # (NRF_FLAG_FROZEN, no activation stash) and the backward asks for no parameter gradient
+    out = model.apply({'params': fp}, rays, warp_extra, rngs=rngs, train=True, ray_grads=ray_grads,
+                      frozen=ray_grads and not ctx.needs_input_grad[0], **opts)
     ctx.model, ctx.rays, ctx.fp = model, rays, fp
     ctx.stash = model.stash   # the stash this node differentiates: a later apply(train=True) replaces it
     ctx.set_materialize_grads(False)   # an output the loss does not read stays NULL for the library, not a buffer of zeros

@@ -371,7 +371,10 @@ struct Tile64 {
 // read from bits_wave (tangent pass: the ReLU derivative of the primal pass, warping.py:385-387 jacfwd; 64-row tiles).
 // T: which half of the 64-row stash tile a 32-row workgroup owns.
 enum { EPI_LINEAR = 0, EPI_RELU = 1, EPI_MASK = 2 };
-template <int NCB, int MODE, bool STASH, class G = Tile64>
+// STASH: what a training forward keeps of a layer.  STASH_FULL (= true): the activations and the sign words; STASH_BITS: the sign
+// words only -- a frozen-field plan (NRF_FLAG_FROZEN), whose reverse pass runs the data-gradient chain and no weight gradient.
+enum { STASH_NONE = 0, STASH_FULL = 1, STASH_BITS = 2 };
+template <int NCB, int MODE, int STASH, class G = Tile64>
 __device__ __forceinline__ void fwd_epilogue(f32x16 (&acc)[G::RB][NCB], int ncol0, float* act,
                                              __amdgpu_buffer_rsrc_t stash, int stash_soff, uint32_t* bits_wave,
                                              int lane, int T = 0) {
@@ -393,7 +396,7 @@ __device__ __forceinline__ void fwd_epilogue(f32x16 (&acc)[G::RB][NCB], int ncol
         v = mask4(v, (mb[cb] >> (4 * q)) & 15u);
       }
       *reinterpret_cast<float4*>(act + G::addr(n, G::granule(q, h))) = v;
-      if (STASH) buf_store4(v, stash, G::frag_voff(lane, q), stash_soff + cb * 8 * 1024 + G::frag_slot(T, q));
+      if (STASH == STASH_FULL) buf_store4(v, stash, G::frag_voff(lane, q), stash_soff + cb * 8 * 1024 + G::frag_slot(T, q));
     }
     if (STASH && MODE == EPI_RELU) G::template bits_store<NCB>(mb, cb, bits_wave, lane, T);
   }

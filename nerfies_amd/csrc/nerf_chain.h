@@ -256,8 +256,9 @@ __device__ __forceinline__ float sigma_activation(float x, int kind) {
 struct ChainFwdArgs1 { ChainFwdArgs a[1]; };
 
 // One tile of the forward chain: 64-row tile `tile`, or its half T on 32-row tiles.  STAMP() marks a phase boundary for the
-// in-kernel timeline of the 64-row kernel (a no-op otherwise).
-template <class G, bool STASH, class Stamp>
+// in-kernel timeline of the 64-row kernel (a no-op otherwise).  STASH (chain_common.h): STASH_BITS keeps the posenc stash and the
+// sign words and stores no activation.
+template <class G, int STASH, class Stamp>
 __device__ __forceinline__ void fwd_tile(const ChainFwdArgs& A, const int tile, const int T, float* smem, const int tid0, const int wave,
                                          Stamp& STAMP) {
   constexpr int ROWS = G::ROWS;
@@ -341,7 +342,7 @@ __device__ __forceinline__ void fwd_tile(const ChainFwdArgs& A, const int tile, 
     STAMP();   // k loop of layer l issued
     fwd_epilogue<2, EPI_RELU, STASH, G>(
         acc, wave * 64, act,
-        make_rsrc(STASH ? A.st_h + l * st_h_layer + (size_t)tile * FRAG_TILE_256 : nullptr, FRAG_TILE_256 * 4), wv_soff,
+        make_rsrc(STASH == STASH_FULL ? A.st_h + l * st_h_layer + (size_t)tile * FRAG_TILE_256 : nullptr, FRAG_TILE_256 * 4), wv_soff,
         STASH ? A.bits_trunk + (((size_t)l * A.ntiles + tile) * 4 + wave) * 128 : nullptr, lane, T);
     STAMP();   // epilogue of layer l done
   }
@@ -384,9 +385,9 @@ __device__ __forceinline__ void fwd_tile(const ChainFwdArgs& A, const int tile, 
   const float4* wrgb = wpk4 + (A.pk.fwd_rgbh / 4) + wave * 32 * 64;
   const WQuad<1> wrgb0 = prefetch_quad<1>(wrgb, lane);
   __builtin_amdgcn_sched_barrier(0);
-  fwd_epilogue<2, EPI_LINEAR, STASH, G>(
+  fwd_epilogue<2, EPI_LINEAR, STASH == STASH_FULL ? STASH_FULL : STASH_NONE, G>(
       acc, wave * 64, act,
-      make_rsrc(STASH ? A.st_bn + (size_t)tile * FRAG_TILE_256 : nullptr, FRAG_TILE_256 * 4), wv_soff, nullptr, lane, T);
+      make_rsrc(STASH == STASH_FULL ? A.st_bn + (size_t)tile * FRAG_TILE_256 : nullptr, FRAG_TILE_256 * 4), wv_soff, nullptr, lane, T);
   if (A.alpha_ct) {
     alpha_head();   // the scratch is next written by the rgb logits, two barriers further on
     if (part == 0) sigma_raw += A.alpha_ct[min((row0 + p) / A.S, A.B - 1)];
@@ -405,7 +406,7 @@ __device__ __forceinline__ void fwd_tile(const ChainFwdArgs& A, const int tile, 
     int nextb = (ray + 1) * A.S - row0;   // first tile row of the next ray
     float ct = A.condterm[(size_t)min(ray, A.B - 1) * RGB_W + n];
     G::template k_loop<1, true>(acc1, act, 16, wrgb, lane, wrgb0);
-    const __amdgpu_buffer_rsrc_t st = make_rsrc(STASH ? A.st_rgbh + (size_t)tile * FRAG_TILE_128 : nullptr, FRAG_TILE_128 * 4);
+    const __amdgpu_buffer_rsrc_t st = make_rsrc(STASH == STASH_FULL ? A.st_rgbh + (size_t)tile * FRAG_TILE_128 : nullptr, FRAG_TILE_128 * 4);
     __syncthreads();
     uint32_t mb[1] = {0u};
 #pragma unroll
@@ -424,7 +425,7 @@ __device__ __forceinline__ void fwd_tile(const ChainFwdArgs& A, const int tile, 
       if (STASH) mb[0] |= sign_nibble(v4) << (4 * q);
       v4.x = relu(v4.x); v4.y = relu(v4.y); v4.z = relu(v4.z); v4.w = relu(v4.w);
       *reinterpret_cast<float4*>(act + G::addr(n, g)) = v4;
-      if (STASH) buf_store4(v4, st, G::frag_voff(lane, q), wave * 8 * 1024 + G::frag_slot(T, q));
+      if (STASH == STASH_FULL) buf_store4(v4, st, G::frag_voff(lane, q), wave * 8 * 1024 + G::frag_slot(T, q));
     }
     if (STASH) G::template bits_store<1>(mb, 0, A.bits_rgbh + ((size_t)tile * 4 + wave) * 64, lane, T);
     __syncthreads();
@@ -442,7 +443,7 @@ __device__ __forceinline__ void fwd_tile(const ChainFwdArgs& A, const int tile, 
       const float bx = prm[A.po.rgbx_b[x] + n];
       G::template k_loop<1, true>(acc1, act, 8, wx, lane, prefetch_quad<1>(wx, lane));
       const __amdgpu_buffer_rsrc_t st =
-          make_rsrc(STASH ? A.st_rgbx + ((size_t)x * A.ntiles + tile) * FRAG_TILE_128 : nullptr, FRAG_TILE_128 * 4);
+          make_rsrc(STASH == STASH_FULL ? A.st_rgbx + ((size_t)x * A.ntiles + tile) * FRAG_TILE_128 : nullptr, FRAG_TILE_128 * 4);
       __syncthreads();
       uint32_t mb[1] = {0u};
 #pragma unroll
@@ -453,7 +454,7 @@ __device__ __forceinline__ void fwd_tile(const ChainFwdArgs& A, const int tile, 
         if (STASH) mb[0] |= sign_nibble(v4) << (4 * q);
         v4.x = relu(v4.x); v4.y = relu(v4.y); v4.z = relu(v4.z); v4.w = relu(v4.w);
         *reinterpret_cast<float4*>(act + G::addr(n, g)) = v4;
-        if (STASH) buf_store4(v4, st, G::frag_voff(lane, q), wave * 8 * 1024 + G::frag_slot(T, q));
+        if (STASH == STASH_FULL) buf_store4(v4, st, G::frag_voff(lane, q), wave * 8 * 1024 + G::frag_slot(T, q));
       }
       if (STASH) G::template bits_store<1>(mb, 0, A.bits_rgbx + (((size_t)x * A.ntiles + tile) * 4 + wave) * 64, lane, T);
       __syncthreads();
@@ -544,8 +545,8 @@ __device__ __forceinline__ void rgbx_bias_add(const ChainBwdArgs& A, int x, int 
 }
 
 // Reverse epilogue of one column block of a lane: piece q = src(q, g) [+ ds (x) wa, the alpha head's d sigma_raw term]
-// [* ReLU mask] -> LDS tile (the next step's A operand) and the dY image; returns bsum + the column sum of what was written.
-template <class G, class Src, class Msk>
+// [* ReLU mask] -> LDS tile (the next step's A operand) and (DY) the dY image; returns bsum + the column sum of what was written.
+template <class G, bool DY, class Src, class Msk>
 __device__ __forceinline__ float bwd_epilogue(Src src, bool add_ds, const float* ds_row, float wa, Msk mask, float bsum, int n, float* act,
                                               __amdgpu_buffer_rsrc_t dy, int soff, int lane, int T) {
   const int h = lane >> 5;
@@ -560,15 +561,19 @@ __device__ __forceinline__ float bwd_epilogue(Src src, bool add_ds, const float*
     v = mask(v, q);
     bsum += (v.x + v.y) + (v.z + v.w);
     *reinterpret_cast<float4*>(act + G::addr(n, g)) = v;
-    buf_store4(v, dy, G::frag_voff(lane, q), soff + G::frag_slot(T, q));
+    if constexpr (DY) buf_store4(v, dy, G::frag_voff(lane, q), soff + G::frag_slot(T, q));
   }
   return bsum;
 }
 
 // One tile of level A (tile = index inside the level; T = its half on 32-row tiles).  C: BwdAcc on 64-row tiles.
-template <class G, class Acc>
+// DY = false (frozen-field plans, NRF_FLAG_FROZEN: the reverse pass stops at the rays): the chain still forms every dpre tile in
+// LDS, accumulates dray and writes d_points, but stores no dY image and keeps no bias column sum (C: NoBwdAcc; small_part unused).
+template <class G, class Acc, bool DY = true>
 __device__ __forceinline__ void bwd_tile(const ChainBwdArgs& A, const int tile, const int T, float* smem, Acc& C) {
   constexpr int ROWS = G::ROWS;
+  constexpr bool REGS = G::BIAS_IN_REGS && DY;    // bias column sums in the workgroup's registers ...
+  constexpr bool ATOM = !G::BIAS_IN_REGS && DY;   // ... or added to its small_part slice
   float* act = smem;                    // [256][ROWS] swizzled: current dpre tile
   float* dr = smem + TRUNK_W * ROWS;    // [4][ROWS]: d raw rgb (3) and d raw sigma of the tile rows
   int tid = threadIdx.x;
@@ -586,8 +591,8 @@ __device__ __forceinline__ void bwd_tile(const ChainBwdArgs& A, const int tile, 
   if (tid < ROWS) {
     const float4 d = A.d_raw4[(size_t)row0 + tid];
     dr[tid] = d.x; dr[ROWS + tid] = d.y; dr[2 * ROWS + tid] = d.z; dr[3 * ROWS + tid] = d.w;
-    if constexpr (G::BIAS_IN_REGS) { C.dsum[0] += d.x; C.dsum[1] += d.y; C.dsum[2] += d.z; C.dsum[3] += d.w; }
-  } else if (!G::BIAS_IN_REGS && tid >= 64 && tid < 64 + ROWS) {   // wave 1, lanes 0..31 sum the columns
+    if constexpr (REGS) { C.dsum[0] += d.x; C.dsum[1] += d.y; C.dsum[2] += d.z; C.dsum[3] += d.w; }
+  } else if (ATOM && tid >= 64 && tid < 64 + ROWS) {   // wave 1, lanes 0..31 sum the columns
     const float4 d = A.d_raw4[(size_t)row0 + tid - 64];
     float s0 = d.x, s1 = d.y, s2 = d.z, s3 = d.w;
 #pragma unroll
@@ -613,8 +618,8 @@ __device__ __forceinline__ void bwd_tile(const ChainBwdArgs& A, const int tile, 
     const __amdgpu_buffer_rsrc_t dy =
         make_rsrc(nx ? A.dy_rgbx + xt * FRAG_TILE_128 : A.dy_rgbh + (size_t)tile * FRAG_TILE_128, FRAG_TILE_128 * 4);
     float bsum = 0.f;
-    if constexpr (G::BIAS_IN_REGS) bsum = nx ? 0.f : C.db_rgbh;
-    bsum = bwd_epilogue<G>(
+    if constexpr (REGS) bsum = nx ? 0.f : C.db_rgbh;
+    bsum = bwd_epilogue<G, DY>(
         [&](int, int g) {
           const float4 d0 = *reinterpret_cast<const float4*>(dr + 4 * g);
           const float4 d1 = *reinterpret_cast<const float4*>(dr + ROWS + 4 * g);
@@ -626,10 +631,10 @@ __device__ __forceinline__ void bwd_tile(const ChainBwdArgs& A, const int tile, 
         },
         false, nullptr, 0.f, [&](const float4& v, int q) { return mask4(v, G::template mask_nibble<1>(mb, 0, T, q, h)); }, bsum, n, act, dy,
         wave * 8 * 1024, lane, T);
-    if constexpr (G::BIAS_IN_REGS) {
+    if constexpr (REGS) {
       if (nx) rgbx_bias_add(A, nx - 1, n, h, bsum);
       else C.db_rgbh = bsum;
-    } else {
+    } else if constexpr (ATOM) {
       bias32_add(sp + SP_DB_RGBH + n, bsum, h);
     }
   }
@@ -655,11 +660,13 @@ __device__ __forceinline__ void bwd_tile(const ChainBwdArgs& A, const int tile, 
       const int lane = le & 63, j = lane & 31, h = lane >> 5;
       const int n = wave * 32 + j;
       const auto mb = G::template mask_load<1>(x > 1 ? A.bits_rgbx + (xt * 4 + wave) * 64 : A.bits_rgbh + ((size_t)tile * 4 + wave) * 64, lane);
-      const float bsum = bwd_epilogue<G>(
+      [[maybe_unused]] const float bsum = bwd_epilogue<G, DY>(
           [&](int q, int) { return G::template piece<1>(acc1, 0, q); }, false, nullptr, 0.f,
           [&](const float4& v, int q) { return mask4(v, G::template mask_nibble<1>(mb, 0, T, q, h)); }, 0.f, n, act, dy, wave * 8 * 1024, lane, T);
-      if (x > 1) rgbx_bias_add(A, x - 2, n, h, bsum);
-      else C.db_rgbh += bsum;
+      if constexpr (REGS) {
+        if (x > 1) rgbx_bias_add(A, x - 2, n, h, bsum);
+        else C.db_rgbh += bsum;
+      }
       __syncthreads();
     }
   }
@@ -710,10 +717,10 @@ __device__ __forceinline__ void bwd_tile(const ChainBwdArgs& A, const int tile, 
     for (int cb = 0; cb < 2; ++cb) {
       const int n = wave * 64 + 32 * cb + j;
       const float wab = A.alpha_on_bn ? prm[A.po.alpha_k + n] : 0.f;   // use_alpha_condition: the alpha head reads the bottleneck
-      const float bsum = bwd_epilogue<G>([&](int q, int) { return G::template piece<2>(acc, cb, q); }, A.alpha_on_bn, dr + 3 * ROWS, wab,
+      [[maybe_unused]] const float bsum = bwd_epilogue<G, DY>([&](int q, int) { return G::template piece<2>(acc, cb, q); }, A.alpha_on_bn, dr + 3 * ROWS, wab,
                                          no_mask, 0.f, n, act, dy, wv + cb * 8 * 1024, lane, T);
-      if constexpr (G::BIAS_IN_REGS) C.db_bn[cb] += bsum;
-      else bias32_add(sp + SP_DB_BN + n, bsum, h);
+      if constexpr (REGS) C.db_bn[cb] += bsum;
+      else if constexpr (ATOM) bias32_add(sp + SP_DB_BN + n, bsum, h);
     }
     __syncthreads();
   }
@@ -740,12 +747,12 @@ __device__ __forceinline__ void bwd_tile(const ChainBwdArgs& A, const int tile, 
     for (int cb = 0; cb < 2; ++cb) {
       const int n = wave * 64 + 32 * cb + j;
       const float wa = (l == TRUNK_DEPTH && !A.alpha_on_bn) ? prm[A.po.alpha_k + n] : 0.f;
-      bs[cb] = bwd_epilogue<G>([&](int q, int) { return G::template piece<2>(acc, cb, q); }, l == TRUNK_DEPTH, dr + 3 * ROWS, wa,
+      bs[cb] = bwd_epilogue<G, DY>([&](int q, int) { return G::template piece<2>(acc, cb, q); }, l == TRUNK_DEPTH, dr + 3 * ROWS, wa,
                                [&](const float4& v, int q) { return mask4(v, G::template mask_nibble<2>(mb, cb, T, q, h)); }, 0.f, n, act, dy,
                                wv + cb * 8 * 1024, lane, T);
-      if constexpr (!G::BIAS_IN_REGS) bias32_add(sp + SP_DB_TRUNK + (l - 1) * TRUNK_W + n, bs[cb], h);
+      if constexpr (ATOM) bias32_add(sp + SP_DB_TRUNK + (l - 1) * TRUNK_W + n, bs[cb], h);
     }
-    if constexpr (G::BIAS_IN_REGS) {
+    if constexpr (REGS) {
       // runtime layer index -> static register: add into the matching accumulator
 #pragma unroll
       for (int q = 0; q < TRUNK_DEPTH; ++q)

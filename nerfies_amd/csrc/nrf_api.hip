@@ -141,8 +141,16 @@ int nrf_param_layout(nrf_handle h, nrf_tensor_info* out, int32_t* n) {
 // workspace for a plan no call can run).
 static int check_flags(const nrf_handle_s* h, uint32_t flags) {
   const uint32_t known = NRF_FLAG_TRAIN | NRF_FLAG_NO_WARP | NRF_FLAG_BF16 | NRF_FLAG_WARP_JACOBIAN | NRF_FLAG_WARP_F32 | NRF_FLAG_BF16X3 |
-                         NRF_FLAG_RAY_GRADS;
+                         NRF_FLAG_RAY_GRADS | NRF_FLAG_FROZEN;
   if (flags & ~known) return fail(NRF_E_UNSUPPORTED, "unknown bits in flags");
+  if (flags & NRF_FLAG_FROZEN) {   // one valid word: TRAIN | RAY_GRADS | FROZEN (float32 mode)
+    if (!(flags & NRF_FLAG_TRAIN) || !(flags & NRF_FLAG_RAY_GRADS))
+      return fail(NRF_E_UNSUPPORTED, "NRF_FLAG_FROZEN narrows the stash of NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS to what nrf_backward_rays reads: "
+                                     "only together with both");
+    if (flags & (NRF_FLAG_BF16 | NRF_FLAG_BF16X3 | NRF_FLAG_WARP_JACOBIAN))
+      return fail(NRF_E_UNSUPPORTED, "NRF_FLAG_FROZEN is built for the float32 mode: not with NRF_FLAG_BF16 / NRF_FLAG_BF16X3 / "
+                                     "NRF_FLAG_WARP_JACOBIAN");
+  }
   if ((flags & NRF_FLAG_RAY_GRADS) && (flags & (NRF_FLAG_BF16 | NRF_FLAG_BF16X3)))
     return fail(NRF_E_UNSUPPORTED, "NRF_FLAG_RAY_GRADS is built for the float32 mode: not with NRF_FLAG_BF16 / NRF_FLAG_BF16X3");
   if ((flags & NRF_FLAG_RAY_GRADS) && !(flags & NRF_FLAG_TRAIN))
@@ -186,7 +194,10 @@ int nrf_forward(nrf_handle h, const float* params, const nrf_rays* rays, const n
 // nrf_backward / nrf_backward_ex: the state checks, the zero stand-in of a missing d_rgb, the reverse pass
 static int backward_checked(nrf_handle h, const float* params, const nrf_rays* rays, nrf_output_grads g, float* grad_params,
                             void* workspace, size_t workspace_bytes, void* stream, const nrf_ray_grads* rg = nullptr) {
-  if (!h || !params || !rays || !grad_params || !workspace) return fail(NRF_E_NULL, "null argument");
+  if (!h || !params || !rays || !workspace) return fail(NRF_E_NULL, "null argument");
+  // a frozen stash (NRF_FLAG_FROZEN) is the one case without a parameter gradient: nrf_backward_rays with grad_params NULL
+  const bool frozen = h->stashed_ws == workspace && h->stashed_modes.frozen;
+  if (!grad_params && !frozen) return fail(NRF_E_NULL, "null argument");
   if (h->stashed_ws != workspace || h->stashed_B != rays->num_rays)
     return fail(NRF_E_STATE, rg ? "nrf_backward_rays needs a preceding nrf_forward(NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS) on this workspace"
                                 : "nrf_backward needs a preceding nrf_forward(NRF_FLAG_TRAIN) on this workspace");
@@ -200,6 +211,12 @@ static int backward_checked(nrf_handle h, const float* params, const nrf_rays* r
     return fail(NRF_E_STATE, "nrf_backward: the workspace layout changed since the stashed nrf_forward (an intervening call with "
                              "another num_rays / flags); run nrf_forward(NRF_FLAG_TRAIN) again");
   if (workspace_bytes < h->plan.total_floats * sizeof(float)) return fail(NRF_E_WORKSPACE, "workspace too small");
+  if (frozen && !rg)
+    return fail(NRF_E_STATE, "nrf_backward: the stashed nrf_forward ran under NRF_FLAG_FROZEN (nothing of the parameter gradient was "
+                             "kept); call nrf_backward_rays with grad_params NULL, or run nrf_forward without the flag");
+  if (frozen && grad_params)
+    return fail(NRF_E_STATE, "nrf_backward_rays: the stashed nrf_forward ran under NRF_FLAG_FROZEN (nothing of the parameter gradient "
+                             "was kept): grad_params must be NULL");
   if (h->nlevels < 2) g.fine = nrf_level_grads{};   // no fine level: nothing to read
   if ((g.coarse.d_warped_points || g.fine.d_warped_points) && !h->stashed_modes.warp_on)
     return fail(NRF_E_STATE, "nrf_backward_ex: d_warped_points given, but the stashed nrf_forward ran without the warp field "
@@ -213,6 +230,7 @@ static int backward_checked(nrf_handle h, const float* params, const nrf_rays* r
   }
   if (!g.coarse.d_rgb) g.coarse.d_rgb = zero;
   if (!g.fine.d_rgb) g.fine.d_rgb = zero;
+  if (frozen) return backward_rays_frozen_impl(h, params, rays, &g, nullptr, rg, nullptr, ws, st);
   return backward_impl(h, params, rays, &g, nullptr, grad_params, nullptr, ws, st, nullptr, nullptr, nullptr, nullptr, false, rg);
 }
 
@@ -307,6 +325,20 @@ int nrf_train_step_loss_grad_rays(nrf_handle h, const float* params, const nrf_r
                        grad_params, stats, workspace, workspace_bytes, stream);
 }
 
+int nrf_loss_grad_rays(nrf_handle h, const float* params, const nrf_rays* rays, const float* target_rgb, const nrf_step_scalars* scalars,
+                       const nrf_rand* rnd, const nrf_ray_grads* ray_grads, float* stats, void* workspace, size_t workspace_bytes,
+                       void* stream) {
+  if (!h || !target_rgb) return fail(NRF_E_NULL, "null argument");
+  if (!ray_grads) return fail(NRF_E_NULL, "nrf_ray_grads is null (the frozen step returns nothing else)");
+  if (ray_grads->d_viewdirs && rays && (!h->d.use_viewdirs || !rays->viewdirs || h->V > 64))
+    return fail(NRF_E_UNSUPPORTED, "nrf_ray_grads.d_viewdirs needs a model with use_viewdirs (at most 64 encoded columns) and rays->viewdirs "
+                                   "(without them the view term is part of d_directions)");
+  const uint32_t flags = NRF_FLAG_TRAIN | NRF_FLAG_RAY_GRADS | NRF_FLAG_FROZEN;
+  CK(check_flags(h, flags));
+  CK(forward_impl(h, params, rays, scalars, rnd, nullptr, flags, (float*)workspace, workspace_bytes, (hipStream_t)stream));
+  return backward_rays_frozen_impl(h, params, rays, nullptr, target_rgb, ray_grads, stats, (float*)workspace, (hipStream_t)stream, scalars);
+}
+
 int nrf_workspace_bytes_ex(nrf_handle h, int32_t num_rays, uint32_t flags, int32_t num_background_points,
                            int32_t use_elastic_loss, size_t* bytes) {
   if (!h || !bytes) return fail(NRF_E_NULL, "null");
@@ -314,6 +346,8 @@ int nrf_workspace_bytes_ex(nrf_handle h, int32_t num_rays, uint32_t flags, int32
   if ((num_background_points > 0 || use_elastic_loss) && !h->warp)
     return fail(NRF_E_UNSUPPORTED, "the background / elastic regularisers need the warp field");
   CK(check_flags(h, flags));
+  if ((flags & NRF_FLAG_FROZEN) && (num_background_points > 0 || use_elastic_loss))
+    return fail(NRF_E_UNSUPPORTED, "NRF_FLAG_FROZEN: the frozen step applies no regulariser (no background points, no elastic loss)");
   query_device(h);
   const bool tr = flags & NRF_FLAG_TRAIN;
   build_plan(h, num_rays, flags, tr ? num_background_points : 0, tr && use_elastic_loss ? 1 : 0);

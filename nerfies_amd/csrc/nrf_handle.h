@@ -143,6 +143,7 @@ struct Modes {
   bool bf16 = false, x3 = false;         // NeRF chains on bf16 operands (mlp_bf16.hip) / in split-bf16 arithmetic (mlp_bf16x3.hip)
   bool jac = false;                      // NRF_FLAG_WARP_JACOBIAN: the tangent pass of an inference call
   bool ray_grads = false;                // NRF_FLAG_RAY_GRADS: the stash holds what nrf_backward_rays reads
+  bool frozen = false;                   // NRF_FLAG_FROZEN: ... and nothing else (no activation stash: nrf_backward_rays without grad_params only)
   WarpTrunk trunk = WarpTrunk::F32;
 };
 
@@ -273,6 +274,10 @@ int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, con
                   float* grad_x, float* stats, float* ws, hipStream_t stream, const nrf_background* bg = nullptr,
                   const nrf_step_scalars* scalars = nullptr, const nrf_elastic* el = nullptr, const nrf_warp_reg* wr = nullptr,
                   bool bg_forward_done = false, const nrf_ray_grads* rg = nullptr);
+// the reverse pass of a frozen stash (NRF_FLAG_FROZEN): composite_bwd, the NeRF data-gradient chain, the ray stage; og / target as above
+int backward_rays_frozen_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, const nrf_output_grads* og, const float* target,
+                              const nrf_ray_grads* rg, float* stats, float* ws, hipStream_t stream,
+                              const nrf_step_scalars* scalars = nullptr);
 
 }  // namespace api
 }  // namespace nrf

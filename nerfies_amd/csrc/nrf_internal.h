@@ -431,9 +431,13 @@ void launch_chain_bwd(const ChainBwdArgs& a0, const ChainBwdArgs* a1, int grid, 
 // the same chains (nerf_chain.h: one tile body for both tilings) on 32-row tiles, four workgroups per CU (mlp_chain32.hip); same
 // arguments, same HBM images.  The d-points path is compiled for 64-row tiles only: warp-on plans keep the 64-row reverse pass
 void launch_chain_fwd32(const ChainFwdArgs& a, bool stash, int grid, hipStream_t stream);
+// chain_frozen.hip: the chains of a frozen-field plan (NRF_FLAG_FROZEN) -- forward with sign words and posenc stash only (64- or
+// 32-row tiles), reverse (64-row tiles, both levels) with d_points / dray and no dY image or bias partial
+void launch_chain_fwd_frozen(const ChainFwdArgs& a, bool tile32, int grid, hipStream_t stream);
+void launch_chain_bwd_frozen(const ChainBwdArgs& a0, const ChainBwdArgs* a1, int grid, hipStream_t stream);
 void launch_chain_bwd32(const ChainBwdArgs& a0, const ChainBwdArgs* a1, int grid, hipStream_t stream);
 // a1 (optional): a second level in the same launch (background points behind the coarse samples)
-void launch_warp_fwd(const WarpFwdArgs& a, const WarpFwdArgs* a1, bool stash, int grid, hipStream_t stream);
+void launch_warp_fwd(const WarpFwdArgs& a, const WarpFwdArgs* a1, bool stash, int grid, hipStream_t stream, bool frozen = false);   // frozen: no activation stash
 // a1, a2 (optional): further levels in the same launch; bias partials of all levels go to a.small_part
 void launch_warp_bwd(const WarpBwdArgs& a, const WarpBwdArgs* a1, const WarpBwdArgs* a2, int grid, hipStream_t stream);
 void launch_elastic(const ElasticArgs& a, hipStream_t stream);

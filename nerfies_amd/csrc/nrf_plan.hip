@@ -217,6 +217,7 @@ uint32_t plan_flags(uint32_t flags) {
   if ((flags & NRF_FLAG_TRAIN) && (flags & NRF_FLAG_BF16)) f |= NRF_FLAG_BF16 | (flags & NRF_FLAG_WARP_F32);
   if (!(flags & NRF_FLAG_TRAIN) && (flags & NRF_FLAG_BF16X3)) f |= NRF_FLAG_BF16X3;   // its own (tripled) weight streams
   if ((flags & NRF_FLAG_TRAIN) && (flags & NRF_FLAG_RAY_GRADS)) f |= NRF_FLAG_RAY_GRADS;   // float32 training only (check_flags)
+  if ((f & NRF_FLAG_RAY_GRADS) && (flags & NRF_FLAG_FROZEN)) f |= NRF_FLAG_FROZEN;         // ... with both of them only (check_flags)
   return f;
 }
 
@@ -448,6 +449,7 @@ struct Planner {
   const bool bfw;      // ... and so does the SE3 trunk (warp_bf16.hip)
   const bool wstash;   // the fp32 warp kernels keep their input / sign-bit stash
   const bool rg;       // NRF_FLAG_RAY_GRADS: what nrf_backward_rays reads stays alive
+  const bool frozen;   // NRF_FLAG_FROZEN: ... and nothing else of the reverse pass: no activation stash, dY, wgrad slab or reduce entry
   std::vector<size_t> rg_packT[2];      // ... a model without a warp field: the level's pack descriptors that write into rg_wpkT
   const int G;
   std::vector<GroupSpec> specs;         // fp32 wgrad groups
@@ -460,7 +462,7 @@ struct Planner {
       : h(h_), p(h_->plan), d(h_->d), train(flags & NRF_FLAG_TRAIN), bft(train && (flags & NRF_FLAG_BF16)),
         x3(!train && (flags & NRF_FLAG_BF16X3)), jac((flags & NRF_FLAG_WARP_JACOBIAN) && h_->warp),
         bfw(bft && h_->warp && !(flags & NRF_FLAG_WARP_F32)), wstash((train && !bfw) || jac), rg(train && (flags & NRF_FLAG_RAY_GRADS)),
-        G(h_->num_cus) {}
+        frozen(rg && (flags & NRF_FLAG_FROZEN)), G(h_->num_cus) {}
   size_t take(size_t n) { size_t r = o; o = align_up(o + n, ALIGN_F); return r; }
   void add_reduce(const ReduceDesc& r) { by_pass[r.accumulate].push_back(r); }
   // fp32 groups: leaf [kvalid][cols] <- X^T dY; the narrow heads: leaf [kvalid][vec] <- X^T v
@@ -530,7 +532,7 @@ void Planner::shapes() {
 
 // ---- wgrad groups (training): what each multiplies, which leaves it feeds ----
 void Planner::wgrad_specs() {
-  if (!train) return;
+  if (!train || frozen) return;   // a frozen plan has no weight gradient: no group, segment or slab
   for (int lv = 0; lv < h->nlevels; ++lv) {
     if (bft) bf16_specs(lv);
     else fp32_specs(lv);
@@ -740,6 +742,13 @@ void Planner::take_warp_stash(LevelWs& L, size_t nt) {
 void Planner::alloc_warp(LevelWs& L, size_t nt) {
   L.wpoints = take(nt * TILE_ROWS * 3);
   L.points_raw = take(nt * TILE_ROWS * 3);
+  if (frozen) {   // the tangent pass and jacobian_kernel read the trunk input, the sign words and (w, v); the ray stage reads d_points
+    L.w_st_win = take(nt * ((h->PKw + 31) / 32 * 32) * TILE_ROWS);
+    L.w_st_wv = take(nt * TILE_ROWS * 8);
+    L.w_bits = take(nt * 4 * 64 * WARP_DEPTH);
+    L.d_points = take(nt * TILE_ROWS * 3);
+    return;
+  }
   if (wstash) {
     take_warp_stash(L, nt);
     L.w_bits = take(nt * 4 * 64 * WARP_DEPTH);
@@ -796,6 +805,12 @@ void Planner::buffers() {
       L.b_drgbh = take(ng * 4 * BF_BLOCK_DW);
       L.b_dsmall = take(ng * 2 * BF_BLOCK_DW);
       L.d_raw4 = take(nt * TILE_ROWS * 4);
+    } else if (frozen) {   // the data-gradient chain reads the sign words and the posenc stash, not the activations
+      L.st_pe = take(nt * ((h->PK + 31) / 32 * 32) * TILE_ROWS);
+      L.bits_trunk = take(nt * 4 * 128 * TRUNK_DEPTH);
+      L.bits_rgbh = take(nt * 4 * 64);
+      L.d_raw4 = take(nt * TILE_ROWS * 4);
+      if (const size_t nx = d.nerf_rgb_branch_depth - 1) L.bits_rgbx = take(nx * nt * 4 * 64);
     } else if (train) {
       L.st_pe = take(nt * ((h->PK + 31) / 32 * 32) * TILE_ROWS);
       L.st_h = take(nt * FRAG_TILE_256 * TRUNK_DEPTH);
@@ -813,7 +828,9 @@ void Planner::buffers() {
         L.dy_rgbx = take(nx * nt * FRAG_TILE_128);
       }
     }
-    if (train) {
+    if (frozen) {
+      L.dray = take((size_t)B * RGB_W);
+    } else if (train) {
       L.dray = take((size_t)B * RGB_W);
       L.small_part = take((size_t)4 * G * SMALL_PART);   // up to four workgroups per CU (32-row reverse chain)
       L.cond_grad = take((size_t)(h->R > 0 ? h->R : 1) * RGB_W);
@@ -828,7 +845,7 @@ void Planner::buffers() {
   }
   if (h->time_enc) {
     p.t_codes = take((size_t)B * h->G);
-    if (train) {
+    if (train && !frozen) {
       p.t_dcodes = take((size_t)B * h->G);
       p.t_in = take((size_t)B * TIME_MAX_IN);
       p.t_h = take((size_t)B * TIME_DEPTH * TIME_W);
@@ -836,7 +853,7 @@ void Planner::buffers() {
     }
   }
   if (jac && !train) alloc_warp(p.L[TG], p.ntiles[TG]);
-  if (h->warp && train) p.wr_sums = take(64);
+  if (h->warp && train && !frozen) p.wr_sums = take(64);
   if (h->warp && p.key.elastic && train) {
     alloc_warp(p.L[TG], p.ntiles[TG]);
     p.L[0].el_dw4 = take((size_t)p.ntiles[0] * TILE_ROWS * 4);
@@ -879,6 +896,10 @@ void Planner::ray_grad_buffers() {
   // the tangent pass of one level at a time (as the inference Jacobian plan): its input / activation / (w, v) stash
   LevelWs& T = p.L[TG];
   const size_t nt = p.ntiles[TG];
+  if (frozen) {   // jacobian_kernel reads the tangent (dw, dv) rows; nothing reads the tangent inputs or activations
+    T.w_st_wv = take(nt * TILE_ROWS * 8);
+    return;
+  }
   T.wpoints = take(nt * TILE_ROWS * 3);
   take_warp_stash(T, nt);
 }
@@ -923,7 +944,7 @@ void Planner::pack_descs() {
     }
   }
   // fp32 fragment images of the SE3 trunk (a bf16-trunk training plan reads only its bf16 streams)
-  if (h->warp && !bfw) warp_pack_descs(h, h->wpo, (int64_t)p.warp_wpk, true, p.pack);
+  if (h->warp && !bfw) warp_pack_descs(h, h->wpo, (int64_t)p.warp_wpk, !frozen, p.pack);   // frozen: no SE3 reverse chain, no W^T images
 }
 
 // ---- fp32 wgrad groups: slabs (taken in group order) + reduce descriptors ----
@@ -1080,7 +1101,7 @@ void build_plan(nrf_handle h, int B, uint32_t flags, int bgN, int elastic) {
   s.cut_wgrad();
   if (h->embed) {
     h->plan.iparams = s.take((size_t)h->nparams);
-    if (s.train) h->plan.igrad = s.take((size_t)h->nparams);
+    if (s.train && !s.frozen) h->plan.igrad = s.take((size_t)h->nparams);
   }
   // The bf16 / x3 chains have their layer list compiled in: a handle with a deeper rgb branch builds none of their stream
   // descriptors (check_flags refuses those modes for it)
@@ -1088,7 +1109,7 @@ void build_plan(nrf_handle h, int B, uint32_t flags, int bgN, int elastic) {
   else if (!s.train || s.bft) s.weight_streams();
   s.buffers();
   s.pack_descs();
-  if (s.train) {
+  if (s.train && !s.frozen) {
     s.fp32_groups();
     s.bf16_groups();
     s.bias_reduces();

@@ -80,6 +80,7 @@ Modes forward_modes(const nrf_handle_s* h, uint32_t flags) {
   m.bf16 = flags & NRF_FLAG_BF16; m.x3 = flags & NRF_FLAG_BF16X3;   // x3: inference only (check_flags)
   m.jac = flags & NRF_FLAG_WARP_JACOBIAN;
   m.ray_grads = m.train && (flags & NRF_FLAG_RAY_GRADS);
+  m.frozen = m.ray_grads && (flags & NRF_FLAG_FROZEN);
   // the SE3 trunk follows the MLPs into bf16 / split-bf16 unless the caller opts out (NRF_FLAG_WARP_F32) or asks for the Jacobian
   // output (inference tangent pass: fp32 kernels, their input stash); a training plan has decided already (its stash layout depends on it)
   const bool follows = m.train ? h->plan.bfw : !(flags & NRF_FLAG_WARP_F32) && !m.jac;
@@ -127,7 +128,7 @@ struct Run {
     TimeEncArgs a;
     memset(&a, 0, sizeof(a));
     a.params = params; a.po = h->tpo; a.time = rays->time; a.B = B; a.F = h->Ft; a.Tin = h->Tin; a.G = h->G;
-    if (m.train) { a.st_in = ws + p.t_in; a.st_h = ws + p.t_h; }
+    if (m.train && !m.frozen) { a.st_in = ws + p.t_in; a.st_h = ws + p.t_h; }
     if (reverse) { a.d_codes = ws + p.t_dcodes; a.st_dpre = ws + p.t_dpre; }
     else { a.alpha = sc->time_alpha; a.dyn = dyn(); a.codes = ws + p.t_codes; }
     return a;
@@ -169,7 +170,19 @@ struct Forward : Run {
         hipMemsetAsync(ws + p.counters, 0, 64 * sizeof(int), stream) != hipSuccess) return fail(NRF_E_HIP, "zero tile counters");
     params = params_x;
     if (h->embed) {   // narrower model: run on its zero-padded image
-      if (hipMemsetAsync(ws + p.iparams, 0, (size_t)h->nparams * sizeof(float), stream) != hipSuccess) return fail(NRF_E_HIP, "zero padded params");
+      if (m.frozen) {
+        // the frozen step is made to be captured and replayed many times (one alignment step per replay): its image is cleared by a
+        // kernel, not by a memset node.  Observed on an MI355X: from the SECOND replay of a captured step on, the image behind the
+        // replayed memset node is no longer the eager one and the step returns NaN once the host has allocated in between, on the
+        // non-frozen plans as well; with a full-width model (no padded image, no memset) every replay is exact.  The other plans
+        // keep hipMemsetAsync as they were.
+        ZeroArgs z;
+        memset(&z, 0, sizeof(z));
+        z.add(ws + p.iparams, h->nparams);
+        launch_zero_ranges(z, stream);
+      } else if (hipMemsetAsync(ws + p.iparams, 0, (size_t)h->nparams * sizeof(float), stream) != hipSuccess) {
+        return fail(NRF_E_HIP, "zero padded params");
+      }
       launch_embed(table<EmbedDesc>(p.emb_off_b), (int)h->emb.size(), params_x, ws + p.iparams, true, stream);
       params = ws + p.iparams;
     }
@@ -212,7 +225,7 @@ struct Forward : Run {
   }
   // the fp32 stash of a pass over level L (a training plan, or an inference plan that returns the Jacobian)
   void keep_warp_stash(WarpFwdArgs& a, const LevelWs& L) const {
-    a.st_win = ws + L.w_st_win; a.st_h = ws + L.w_st_h; a.st_wv = f4(L.w_st_wv); a.bits = u32(L.w_bits);
+    a.st_win = ws + L.w_st_win; a.st_h = m.frozen ? nullptr : ws + L.w_st_h; a.st_wv = f4(L.w_st_wv); a.bits = u32(L.w_bits);
   }
 
   WarpFwdArgs warp_fwd_args(int lv) const {
@@ -246,7 +259,7 @@ struct Forward : Run {
     pf.begin(lv == 0 ? "warp_fwd_coarse" : "warp_fwd_fine", warp_fwd_flops_row(h) * (p.rows[lv] + (with_bg ? p.key.bgN : 0)), stream);
     if (m.trunk == WarpTrunk::X3) launch_warp_fwd_x3(wa, h->num_cus, stream);   // split-bf16 arithmetic (warp_bf16x3.hip)
     else if (bf16_trunk()) launch_warp_fwd_bf16(wa, bgp, stash, h->num_cus, stream);   // one workgroup per CU, 256 rows per iteration
-    else launch_warp_fwd(wa, bgp, stash, tile_grid(p.ntiles[lv] + (with_bg ? p.ntiles[BG] : 0), warp_grid_mul(), h->num_cus), stream);
+    else launch_warp_fwd(wa, bgp, stash, tile_grid(p.ntiles[lv] + (with_bg ? p.ntiles[BG] : 0), warp_grid_mul(), h->num_cus), stream, m.frozen);
     pf.end(stream);
   }
   // forward-mode pass of the warp Jacobian of level lv (warping.py:385-387): 3 tangent tiles per primal tile
@@ -260,11 +273,12 @@ struct Forward : Run {
     ta.ntiles = 3 * p.ntiles[lv]; ta.rows = ta.ntiles * TILE_ROWS;
     keep_warp_stash(ta, T);
     ta.bits = nullptr; ta.points_out = ws + T.wpoints; ta.points_raw = nullptr;
+    if (m.frozen) { ta.st_win = nullptr; ta.points_out = nullptr; }   // a frozen plan's tangent level is its (dw, dv) rows alone
     ta.tile_counter = tile_counter_or_null(ws + p.counters, CT_TAN_FWD);
     add_bf16_trunk(ta, p.bfw_wpk, TG, true, lv);
     pf.begin("warp_tangent_fwd", 3.0 * warp_fwd_flops_row(h) * p.rows[lv], stream);
     if (bf16_trunk()) launch_warp_fwd_bf16(ta, nullptr, true, h->num_cus, stream);
-    else launch_warp_fwd(ta, nullptr, true, tile_grid(ta.ntiles, warp_grid_mul(), h->num_cus), stream);
+    else launch_warp_fwd(ta, nullptr, true, tile_grid(ta.ntiles, warp_grid_mul(), h->num_cus), stream, m.frozen);
     pf.end(stream);
   }
   // forward-mode Jacobian of the warp: on the coarse samples for the elastic regulariser (models.py:345), per level
@@ -304,6 +318,8 @@ struct Forward : Run {
     }
     if (m.train && m.bf16) {
       a.bst = bf_stash(lv);
+    } else if (m.frozen) {   // posenc stash and sign words only (nerf_chain.h STASH_BITS)
+      a.st_pe = ws + L.st_pe; a.bits_trunk = u32(L.bits_trunk); a.bits_rgbh = u32(L.bits_rgbh); a.bits_rgbx = u32(L.bits_rgbx);
     } else if (m.train) {
       a.st_pe = ws + L.st_pe; a.st_h = ws + L.st_h; a.st_bn = ws + L.st_bn; a.st_rgbh = ws + L.st_rgbh;
       a.bits_trunk = u32(L.bits_trunk); a.bits_rgbh = u32(L.bits_rgbh); a.st_rgbx = ws + L.st_rgbx; a.bits_rgbx = u32(L.bits_rgbx);
@@ -321,6 +337,7 @@ struct Forward : Run {
     if (m.bf16 || m.x3) a.wpk = ws + p.L[lv].bf_wpk;
     if (m.bf16) launch_chain_fwd_bf16(a, h->num_cus, stream);   // one workgroup per CU (90 KiB of weight staging), 256 samples per workgroup iteration
     else if (m.x3) launch_chain_fwd_x3(a, h->num_cus, stream);   // one four-wave workgroup per CU (150 KiB ring), 128 samples per workgroup iteration
+    else if (m.frozen) launch_chain_fwd_frozen(a, c32, grid, stream);
     else if (c32) launch_chain_fwd32(a, m.train, grid, stream);
     else launch_chain_fwd(a, m.train, grid, stream);
     pf.end(stream);
@@ -367,8 +384,8 @@ struct Backward : Run {
   int zero() const {   // everything that is accumulated into, zeroed by one launch
     ZeroArgs z;
     memset(&z, 0, sizeof(z));
-    z.add(grad, h->nparams);
-    if (m.warp_on && h->time_enc) z.add(ws + p.t_dcodes, (long long)B * h->G);
+    if (!m.frozen) z.add(grad, h->nparams);   // a frozen stash has no parameter gradient: dray is all its reverse pass adds into
+    if (m.warp_on && h->time_enc && !m.frozen) z.add(ws + p.t_dcodes, (long long)B * h->G);
     if (wr_on) z.add(ws + p.wr_sums, 64);
     if (bg_on) z.add(ws + p.bg_loss, 64);
     for (int lv = 0; lv < h->nlevels; ++lv) z.add(ws + p.L[lv].dray, (long long)B * RGB_W);
@@ -409,6 +426,7 @@ struct Backward : Run {
     a.S = p.S[lv]; a.B = B; a.rows = p.rows[lv]; a.ntiles = p.ntiles[lv];
     a.d_raw4 = f4(L.d_raw4); a.bits_trunk = u32(L.bits_trunk); a.bits_rgbh = u32(L.bits_rgbh);
     a.dy_trunk = ws + L.dy_trunk; a.dy_bn = ws + L.dy_bn; a.dy_rgbh = ws + L.dy_rgbh; a.dray = ws + L.dray; a.small_part = ws + L.small_part;
+    if (m.frozen) a.dy_trunk = a.dy_bn = a.dy_rgbh = a.small_part = nullptr;   // not in the plan, not written (bwd_tile<., ., false>)
     if (m.warp_on) { a.d_points = ws + L.d_points; a.st_pe = ws + L.st_pe; }
     else if (rg && (rg->d_origins || rg->d_directions)) {   // no warp field: d points only for the ray stage, W^T images of their own
       a.d_points = ws + L.d_points; a.st_pe = ws + L.st_pe;
@@ -416,7 +434,7 @@ struct Backward : Run {
     if (m.ray_grads && !h->warp) { a.wpk = ws + L.rg_wpkT; a.pk.bwd_L0T = p.rg_L0T; a.pk.bwd_L4bT = p.rg_L4bT; }
     a.F = d.num_nerf_point_freqs; a.P = h->P; a.PK = h->PK; a.skip = d.nerf_skip_layer;
     a.alpha_on_bn = h->A > 0 ? 1 : 0;
-    a.nx = d.nerf_rgb_branch_depth - 1; a.bits_rgbx = u32(L.bits_rgbx); a.dy_rgbx = ws + L.dy_rgbx;
+    a.nx = d.nerf_rgb_branch_depth - 1; a.bits_rgbx = u32(L.bits_rgbx); a.dy_rgbx = m.frozen ? nullptr : ws + L.dy_rgbx;
     return a;
   }
   // ONE NeRF-MLP dgrad launch over the tiles of both levels, on the grid the plan's reduce table was built for
@@ -427,7 +445,8 @@ struct Backward : Run {
       ChainBwdArgs ca[2];
       for (int lv = 0; lv < h->nlevels; ++lv) ca[lv] = chain_bwd_args(lv);
       pf.begin("mlp_dgrad", flops, stream);
-      (p.bwd32 ? launch_chain_bwd32 : launch_chain_bwd)(ca[0], h->nlevels > 1 ? &ca[1] : nullptr, p.grid_mlp_bwd, stream);
+      if (m.frozen) launch_chain_bwd_frozen(ca[0], h->nlevels > 1 ? &ca[1] : nullptr, p.grid_mlp_bwd, stream);   // 64-row tiles always
+      else (p.bwd32 ? launch_chain_bwd32 : launch_chain_bwd)(ca[0], h->nlevels > 1 ? &ca[1] : nullptr, p.grid_mlp_bwd, stream);
       pf.end(stream);
       return;
     }
@@ -602,21 +621,22 @@ struct Backward : Run {
       if (e != hipSuccess) return fail_hip(e, "zero grad");
       launch_embed(table<EmbedDesc>(p.emb_off_b), (int)h->emb.size(), grad, grad_x, false, stream);
     }
-    if (stats) {
-      StatsArgs sa;
-      memset(&sa, 0, sizeof(sa));
-      sa.mse_ray = ws + p.mse; sa.B = B; sa.nlevels = h->nlevels;
-      if (bg_on) { sa.bg_sum = ws + p.bg_loss; sa.bgN = p.key.bgN; sa.bg_weight = bg->loss_weight; }
-      if (el_on) {
-        sa.el_part = ws + p.el_sums; sa.el_nwg = (rows_pad(0) + 255) / 256; sa.el_jac_rows = p.rows[0]; sa.el_weight = el->loss_weight;
-        sa.el_rows = el->reduce_method == NRF_ELASTIC_MEDIAN ? B : p.rows[0];
-      }
-      if (wr_on) { sa.wr_sums = ws + p.wr_sums; sa.wr_weight = wr->loss_weight; }
-      sa.stats = stats; sa.dyn = dyn();
-      launch_finish_stats(sa, stream);
-    }
+    if (stats) finish_stats(stats);
     pf.end(stream);
     return NRF_OK;
+  }
+  void finish_stats(float* stats) {   // the step's statistics from the per-ray / per-workgroup sums the reverse kernels left
+    StatsArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.mse_ray = ws + p.mse; sa.B = B; sa.nlevels = h->nlevels;
+    if (bg_on) { sa.bg_sum = ws + p.bg_loss; sa.bgN = p.key.bgN; sa.bg_weight = bg->loss_weight; }
+    if (el_on) {
+      sa.el_part = ws + p.el_sums; sa.el_nwg = (rows_pad(0) + 255) / 256; sa.el_jac_rows = p.rows[0]; sa.el_weight = el->loss_weight;
+      sa.el_rows = el->reduce_method == NRF_ELASTIC_MEDIAN ? B : p.rows[0];
+    }
+    if (wr_on) { sa.wr_sums = ws + p.wr_sums; sa.wr_weight = wr->loss_weight; }
+    sa.stats = stats; sa.dyn = dyn();
+    launch_finish_stats(sa, stream);
   }
 };
 
@@ -687,6 +707,25 @@ int backward_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, con
   b.wgrad();
   CK(b.reduce_and_finish(grad_x, stats));
   return check_launch("nrf_backward");
+}
+
+// The reverse pass of a frozen stash (NRF_FLAG_FROZEN), which keeps what the rays' gradient reads and nothing else: composite_bwd,
+// ONE 64-row NeRF data-gradient launch without dY images or bias partials, the caller's warped-point cotangent, the ray stage.  No SE3
+// dgrad (the warp Jacobians were formed in the forward), no condition / GLO / time-encoder gradients, no wgrad, no reduce pass.
+int backward_rays_frozen_impl(nrf_handle h, const float* params_x, const nrf_rays* rays, const nrf_output_grads* og, const float* target,
+                              const nrf_ray_grads* rg, float* stats, float* ws, hipStream_t stream, const nrf_step_scalars* scalars) {
+  Backward b(Run(h, h->stashed_modes, ws, stream, rays, scalars, nullptr), nullptr, nullptr, og);
+  if (!b.m.frozen || b.p.bwd32) return fail(NRF_E_STATE, "the stashed forward did not run under NRF_FLAG_FROZEN");
+  if (rg->d_origins || rg->d_directions || rg->d_viewdirs) b.rg = rg;
+  b.fold_viewdirs = og == nullptr;   // the fused step: rays->viewdirs == NULL adds the view term to d_directions
+  b.params = h->embed ? ws + b.p.iparams : params_x;   // narrower model: the forward left its padded image in the workspace
+  CK(b.zero());
+  b.composite_bwd(target);
+  b.mlp_dgrad();
+  b.point_cotangents();
+  if (b.rg) b.ray_grads();
+  if (stats) b.finish_stats(stats);
+  return check_launch("nrf_backward_rays (frozen)");
 }
 
 }  // namespace api

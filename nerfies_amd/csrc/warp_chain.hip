@@ -37,7 +37,9 @@ __device__ unsigned long long g_warp_tl[4][4][64];
 // TANGENT: forward-mode pass of the warp Jacobian (warping.py:385-387): tile tt = c * nt_prim + t carries the
 // tangent of primal tile t along coordinate c through the trunk (no biases, ReLU derivative = the primal
 // sign bits) and emits (dw/dx_c, dv/dx_c) per row; exp_se3's part of the Jacobian is applied by elastic_kernel.
-template <bool STASH, bool TANGENT>
+// STASH (chain_common.h): STASH_BITS -- a frozen-field plan (NRF_FLAG_FROZEN) -- keeps the trunk input, the sign words and (w, v)
+// of the primal pass and no activation; its tangent pass runs with STASH_NONE and keeps the (dw, dv) rows alone.
+template <int STASH, bool TANGENT>
 __device__ __forceinline__ void warp_fwd_tile(const WarpFwdArgs& A, const int tile, float* smem) {
   float* act = smem;                  // [128][64] swizzled
   float* win = smem + WACT_FLOATS;    // [PKw][64] trunk input; reused as scratch after the skip layer
@@ -153,12 +155,12 @@ __device__ __forceinline__ void warp_fwd_tile(const WarpFwdArgs& A, const int ti
       if (TANGENT)
         fwd_epilogue<1, EPI_MASK, STASH>(
             acc, wave * 32, act,
-            make_rsrc(STASH ? A.st_h + l * st_layer + (size_t)tile * FRAG_TILE_128 : nullptr, FRAG_TILE_128 * 4), wave * 8 * 1024,
+            make_rsrc(STASH == STASH_FULL ? A.st_h + l * st_layer + (size_t)tile * FRAG_TILE_128 : nullptr, FRAG_TILE_128 * 4), wave * 8 * 1024,
             const_cast<uint32_t*>(A.prim_bits) + (((size_t)l * A.nt_prim + tprim) * 4 + wave) * 64, lane);
       else
         fwd_epilogue<1, EPI_RELU, STASH>(
             acc, wave * 32, act,
-            make_rsrc(STASH ? A.st_h + l * st_layer + (size_t)tile * FRAG_TILE_128 : nullptr, FRAG_TILE_128 * 4),
+            make_rsrc(STASH == STASH_FULL ? A.st_h + l * st_layer + (size_t)tile * FRAG_TILE_128 : nullptr, FRAG_TILE_128 * 4),
             wave * 8 * 1024, STASH ? A.bits + (((size_t)l * A.ntiles + tile) * 4 + wave) * 64 : nullptr, lane);
       WSTAMP();   // layer l: epilogue
     }
@@ -224,9 +226,31 @@ __global__ __launch_bounds__(256, NRF_WARP_WAVES) void se3_warp_fwd_kernel(const
   }
 }
 
-void launch_warp_fwd(const WarpFwdArgs& a, const WarpFwdArgs* a1, bool stash, int grid, hipStream_t stream) {
+// frozen-field plans (NRF_FLAG_FROZEN): kernels of their own, so that the three instantiations above stay what they were
+template <bool TANGENT>
+__global__ __launch_bounds__(256, NRF_WARP_WAVES) void se3_warp_fwd_frozen_kernel(const WarpFwdArgs2 P) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int nt0 = P.nt0, ntot = P.ntot;
+#pragma unroll 1
+  for (int g = blockIdx.x; g < ntot; g += gridDim.x) {
+    const int lv = g >= nt0 ? 1 : 0;
+    warp_fwd_tile<TANGENT ? STASH_NONE : STASH_BITS, TANGENT>(P.a[lv], g - (lv ? nt0 : 0), smem);
+  }
+}
+
+void launch_warp_fwd(const WarpFwdArgs& a, const WarpFwdArgs* a1, bool stash, int grid, hipStream_t stream, bool frozen) {
   const int pk = a.PKw < 32 ? 32 : a.PKw;   // the head scratch needs 24 rows
   const size_t lds = (size_t)(WACT_FLOATS + pk * TILE_ROWS) * sizeof(float);
+  if (frozen) {
+    const void* fz = a.prim_win ? (const void*)se3_warp_fwd_frozen_kernel<true> : (const void*)se3_warp_fwd_frozen_kernel<false>;
+    (void)hipFuncSetAttribute(fz, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    WarpFwdArgs2 q;
+    q.a[0] = a; q.a[1] = a1 ? *a1 : a;
+    q.nt0 = a.ntiles; q.ntot = q.nt0 + (a1 ? a1->ntiles : 0);
+    if (a.prim_win) hipLaunchKernelGGL((se3_warp_fwd_frozen_kernel<true>), dim3(grid), dim3(256), lds, stream, q);
+    else hipLaunchKernelGGL((se3_warp_fwd_frozen_kernel<false>), dim3(grid), dim3(256), lds, stream, q);
+    return;
+  }
   const void* fn = a.prim_win ? (const void*)se3_warp_fwd_kernel<true, true>
                               : stash ? (const void*)se3_warp_fwd_kernel<true, false> : (const void*)se3_warp_fwd_kernel<false, false>;
   (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -13,6 +13,8 @@ NRF_FLAG_WARP_JACOBIAN = 8
 NRF_FLAG_WARP_F32 = 16
 NRF_FLAG_BF16X3 = 32
 NRF_FLAG_RAY_GRADS = 64
+NRF_FLAG_FROZEN = 128      # with TRAIN | RAY_GRADS: the stash serves nrf_backward_rays only (no parameter gradient)
+NRF_VERSION = 660          # of include/nerfies_amd.h; tests hold it against the header and the library
 NRF_NUM_STATS = 16
 NRF_CAMERA_ROW = 24       # floats per row of a camera table
 NRF_CAMERA_NPARAMS = 22   # of which differentiable parameters (the rest: pads)
@@ -142,6 +144,7 @@ EXPORTS = [
     'nrf_camera_table_rays', 'nrf_camera_table_project', 'nrf_camera_table_workspace_bytes', 'nrf_camera_table_rays_backward',
     'nrf_camera_table_project_backward',
     'nrf_train_step_loss_grad_rays', 'nrf_camera_table_compose', 'nrf_camera_table_compose_backward',
+    'nrf_loss_grad_rays',
 ]
 
 _lib = None
@@ -195,6 +198,8 @@ def load_library(path=None):
       'nrf_train_step_loss_grad_rays': [vp, vp, C.POINTER(Rays), vp, C.POINTER(StepScalars), C.POINTER(Rand),
                                         C.POINTER(Background), C.POINTER(Elastic), C.POINTER(WarpReg), u32, C.POINTER(RayGrads),
                                         vp, vp, vp, C.c_size_t, vp],
+      'nrf_loss_grad_rays': [vp, vp, C.POINTER(Rays), vp, C.POINTER(StepScalars), C.POINTER(Rand), C.POINTER(RayGrads), vp, vp,
+                             C.c_size_t, vp],
       'nrf_workspace_bytes_ex': [vp, i32, u32, i32, i32, C.POINTER(C.c_size_t)],
       'nrf_warp_points_workspace_bytes': [vp, i32, C.POINTER(C.c_size_t)],
       'nrf_warp_points': [vp, vp, vp, vp, i32, C.POINTER(StepScalars), vp, vp, C.c_size_t, vp],

@@ -342,10 +342,11 @@ class NerfModel:
       return L.NRF_FLAG_BF16 | L.NRF_FLAG_WARP_F32
     return L.NRF_FLAG_BF16
 
-  def flags(self, train=False, bf16=False, no_warp=False, jacobian=False, ray_grads=False) -> int:
+  def flags(self, train=False, bf16=False, no_warp=False, jacobian=False, ray_grads=False, frozen=False) -> int:
     """The NRF_FLAG_* word of a call: the one place where a mode becomes bits."""
     return (L.NRF_FLAG_TRAIN if train else 0) | self.bf16_flags(bf16) | (L.NRF_FLAG_NO_WARP if no_warp else 0) | \
-        (L.NRF_FLAG_WARP_JACOBIAN if jacobian else 0) | (L.NRF_FLAG_RAY_GRADS if ray_grads else 0)
+        (L.NRF_FLAG_WARP_JACOBIAN if jacobian else 0) | (L.NRF_FLAG_RAY_GRADS if ray_grads else 0) | \
+        (L.NRF_FLAG_FROZEN if frozen else 0)
 
   def check_mode(self, bf16, train: bool = False):
     """Raises NrfError with the library's own message when this model cannot run in the `bf16` mode (a moved skip or an rgb
@@ -443,13 +444,15 @@ class NerfModel:
   def apply(self, variables, rays_dict: Dict[str, Any], warp_extra: Dict[str, Any] = None, metadata_encoded=False,
             use_warp=True, return_points=False, return_weights=False, return_warp_jacobian=False,
             deterministic=False, rngs=None, *, train=False, return_z_vals=False, out=None, bf16=False,
-            ray_grads=False):
+            ray_grads=False, frozen=False):
     """Returns {'coarse': {...}, 'fine': {...}} like the reference.  `train=True` keeps the
     activation stash so `backward` can follow (used by training.train_step / autograd).  `out`: a dict
     returned by an earlier call with the same shapes/flags, to be overwritten in place (fixed output
     addresses: what a captured hipGraph replay needs).  `bf16=True` (inference only, no reference counterpart): the NeRF
     MLPs take bfloat16 operands (NRF_FLAG_BF16), everything else stays fp32.  `ray_grads=True` (with train=True, float32 mode):
-    NRF_FLAG_RAY_GRADS, the stash also keeps what `backward(..., ray_grads=True)` needs for the gradients w.r.t. the rays."""
+    NRF_FLAG_RAY_GRADS, the stash also keeps what `backward(..., ray_grads=True)` needs for the gradients w.r.t. the rays.
+    `frozen=True` (with train=True, ray_grads=True): NRF_FLAG_FROZEN, the parameters are constants of the call -- the stash keeps ONLY
+    what the rays' gradient reads (no activation stash), and `backward(..., ray_grads=...)` returns (None, {name: grad})."""
     del deterministic   # accepted and unused, as in the reference (models.py:298)
     warp_on = bool(self.use_warp and use_warp)
     # models.py:345-346, 367-368: the coarse level carries the Jacobian when the model was built with use_warp_jacobian
@@ -495,7 +498,7 @@ class NerfModel:
         setattr(lo, k, _ptr(t))
       ret[name] = d
     scal = _scalars(warp_extra)
-    flags = self.flags(train, bf16, no_warp=self.use_warp and not warp_on, jacobian=bool(jac_levels), ray_grads=ray_grads)
+    flags = self.flags(train, bf16, no_warp=self.use_warp and not warp_on, jacobian=bool(jac_levels), ray_grads=ray_grads, frozen=frozen)
     rec = self.last_call = self._record(B, flags, device)
     if train:
       self.stash = rec   # what `backward` differentiates (fp32 or bf16 layout), and the batch size it is for
@@ -512,7 +515,8 @@ class NerfModel:
     'med_depth' is piecewise constant and has none.  `d_rgb_coarse` / `d_rgb_fine` are the 'rgb' entries, positionally.
     `ray_grads`: True, or an iterable of 'origins' / 'directions' / 'viewdirs' -- after `apply(..., train=True, ray_grads=True)`;
     returns (grad, {name: (B,3) gradient w.r.t. rays_dict[name]}) through nrf_backward_rays.  True asks for 'viewdirs' only where
-    the model and the rays have them."""
+    the model and the rays have them.  On a frozen stash (`apply(..., frozen=True)`) there is no parameter gradient: the call returns
+    (None, {name: grad}) and `ray_grads` is required (the library refuses nrf_backward_ex with NRF_E_STATE)."""
     stash = self.stash
     if stash is None:
       raise L.NrfError('backward() needs a preceding apply(..., train=True)')
@@ -523,7 +527,8 @@ class NerfModel:
     if stash.num_rays != B:
       raise L.NrfError(f'backward(): the stashed forward was run on {stash.num_rays} rays, not {B}')
     ws = stash.ws   # the library also refuses a stash whose workspace plan was replaced by another call (NRF_E_STATE)
-    grad = grad_out if grad_out is not None else torch.empty_like(fp.flat)
+    frozen = bool(stash.flags & L.NRF_FLAG_FROZEN)   # no parameter gradient: NULL (a grad_out is the library's to refuse, NRF_E_STATE)
+    grad = grad_out if grad_out is not None or frozen else torch.empty_like(fp.flat)
     og, keep2 = self._output_grads(d_out or {}, {'coarse': d_rgb_coarse, 'fine': d_rgb_fine}, B, device)
     tail = (_ptr(grad), _ptr(ws), ws.numel() * 4, _stream(device))
     if ray_grads:
@@ -614,6 +619,34 @@ class NerfModel:
       L.check(self.lib.nrf_train_step_loss_grad_rays(*head, flags & ~(L.NRF_FLAG_TRAIN | L.NRF_FLAG_RAY_GRADS), C.byref(rg), *tail), self.lib)
     del keep, keep2, keep3
     return (grad, stats) if ray_grads is None else (grad, stats, rg_out)
+
+  def loss_and_ray_grads(self, fp: P.FlatParams, batch, warp_extra=None, rngs=None, ray_grads=('origins', 'directions'),
+                         ray_grads_out=None, stats_out=None, dynamic=None):
+    """The fused FROZEN step (nrf_loss_grad_rays): forward + MSE_coarse + MSE_fine + the reverse pass down to the rays, with the
+    parameters fixed -- no parameter gradient, no regulariser, no activation stash.  Returns (stats, {name: (B,3) gradient w.r.t.
+    batch[name]}) for the names in `ray_grads` ('origins', 'directions', 'viewdirs'); stats as `loss_and_grad` with the regulariser
+    entries 0.  A batch without 'viewdirs' on a use_viewdirs model: the view term is part of 'directions'.  `ray_grads_out` /
+    `stats_out`: tensors to write into (fixed addresses for a captured graph); `dynamic`: as `loss_and_grad`.  Float32 only."""
+    device = fp.flat.device
+    rays, keep = self._rays_struct(batch, device)
+    rnd, keep2 = self._rand_struct(rngs, rays.num_rays, device)
+    target = _f32(batch['rgb'], device)[..., :3].contiguous()
+    stats = stats_out if stats_out is not None else torch.empty(L.NRF_NUM_STATS, device=device)
+    scal = _scalars(warp_extra, dynamic)
+    names = _ray_grad_names(ray_grads, ('origins', 'directions', 'viewdirs'), 'loss_and_ray_grads',
+                            "the rays' differentiable entries are 'origins', 'directions', 'viewdirs'")
+    rg_out = {k: (ray_grads_out or {}).get(k) for k in names}
+    for k in names:
+      if rg_out[k] is None:
+        rg_out[k] = torch.empty(rays.num_rays, 3, device=device)
+      elif tuple(rg_out[k].shape) != (rays.num_rays, 3) or rg_out[k].dtype != torch.float32 or not rg_out[k].is_contiguous():
+        raise L.NrfError(f'loss_and_ray_grads(ray_grads_out=...): {k!r} must be a contiguous float32 ({rays.num_rays}, 3) tensor')
+    rg = L.RayGrads(*(_ptr(rg_out.get(k)) for k in ('origins', 'directions', 'viewdirs')))
+    rec = self.stash = self.last_call = self._record(rays.num_rays, self.flags(True, ray_grads=True, frozen=True), device)
+    L.check(self.lib.nrf_loss_grad_rays(self.handle, _ptr(fp.flat), C.byref(rays), _ptr(target), C.byref(scal), C.byref(rnd), C.byref(rg),
+                                        _ptr(stats), _ptr(rec.ws), rec.ws.numel() * 4, _stream(device)), self.lib)
+    del keep, keep2
+    return stats, rg_out
 
   def warp_points(self, variables, points, warp_ids, warp_extra):
     """model.create_warp_field(model, num_batch_dims=1).apply(points, ids, warp_extra, False, False)

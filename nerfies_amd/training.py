@@ -336,6 +336,64 @@ def train_step(model: models.NerfModel, rng_key, state: TrainState, batch: Dict[
   return state, out, next_key
 
 
+def align_step(model: models.NerfModel, params, batch: Dict[str, Any], refiner: CameraRefiner, warp_extra=None, rng_key=0,
+               learning_rate: float = 2e-3):
+  """One step of camera alignment against a FROZEN field: the camera half of `train_step(cameras=...)` and nothing else.  The
+  batch's 'pixels' / 'item_index' are seen from the refiner's current cameras, the fused frozen step (NerfModel.loss_and_ray_grads,
+  nrf_loss_grad_rays) returns the gradients of MSE_coarse + MSE_fine w.r.t. the rays, they are carried into the delta table
+  (all-reduced when a process group is up) and the deltas take an Adam step of `learning_rate`.  `params` (a FlatParams) is read and
+  never written; no parameter gradient, activation stash or regulariser exists in this step, and no torch kernel runs on per-ray
+  data.  Returns (stats, next rng_key); stats as `NerfModel.loss_and_ray_grads`.  float32 mode only."""
+  next_key, fine_key, coarse_key, _ = _step_keys(rng_key)
+  refiner.compose()
+  origins, directions = refiner.rays(batch)
+  # a precomputed 'viewdirs' would be that of the unaligned camera: the condition reads the directions (models.py:326-329)
+  batch = {k: v for k, v in batch.items() if k != 'viewdirs'}
+  batch['origins'], batch['directions'] = origins, directions
+  stats, rg = model.loss_and_ray_grads(params, batch, warp_extra=warp_extra, rngs={'fine': fine_key, 'coarse': coarse_key},
+                                       ray_grads=('origins', 'directions'), ray_grads_out=refiner.ray_grad_buffers(origins.shape[0]))
+  d_deltas = refiner.backward(batch, rg['origins'], rg['directions'])
+  n = 1
+  if dist.is_available() and dist.is_initialized():
+    dist.all_reduce(d_deltas, op=dist.ReduceOp.SUM)
+    n = dist.get_world_size()
+  refiner.apply_gradient(learning_rate, grad_scale=1.0 / n)
+  return stats, next_key
+
+
+def align_cameras(model: models.NerfModel, params, table: torch.Tensor, frame_batches, groups='pose', steps: int = 100,
+                  learning_rate: float = 2e-3, rays_per_step: Optional[int] = None, seed: int = 0, warp_extra=None) -> CameraRefiner:
+  """Aligns the cameras of `table` ((C, 24), nerfies_amd.camera.pack_cameras) against their own pixels with the field frozen:
+  `steps` x `align_step` over seeded random subsets of `rays_per_step` rays.  `frame_batches`: one batch dict, or a list of them
+  (concatenated), with 'pixels' (N, 2) float32, 'item_index' (N,) / (N, 1) int32 rows of `table`, 'rgb' (N, 3) and 'metadata'.
+  rays_per_step None or >= N: every step sees all N rays.  `learning_rate` 2e-3 is the untuned default of `train_step(cameras=...)`.
+  Returns the CameraRefiner: `.compose()` is the aligned table, `.deltas` what moved."""
+  pool = frame_batches if isinstance(frame_batches, dict) else _concat_batches(list(frame_batches))
+  n = pool['pixels'].reshape(-1, 2).shape[0]
+  refiner = CameraRefiner(table, groups=groups)
+  gen = torch.Generator().manual_seed(int(seed))
+  key = int(seed)
+  for _ in range(int(steps)):
+    batch = pool
+    if rays_per_step is not None and rays_per_step < n:
+      sel = torch.randperm(n, generator=gen)[:int(rays_per_step)].to(table.device)
+      batch = _select_rows(pool, sel, n)
+    _, key = align_step(model, params, batch, refiner, warp_extra, key, learning_rate)
+  return refiner
+
+
+def _select_rows(batch, sel, n):
+  """Rows `sel` of every per-ray entry of a batch (tensors whose first dimension is n), 'metadata' included."""
+  pick = lambda v: v[sel].contiguous() if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == n else v
+  return {k: ({kk: pick(vv) for kk, vv in v.items()} if isinstance(v, dict) else pick(v)) for k, v in batch.items()}
+
+
+def _concat_batches(batches):
+  cat = lambda vs: torch.cat(vs, 0) if torch.is_tensor(vs[0]) else vs[0]
+  return {k: ({kk: cat([b[k][kk] for b in batches]) for kk in v} if isinstance(v, dict) else cat([b[k] for b in batches]))
+          for k, v in batches[0].items()}
+
+
 class GraphedTrainStep:
   """training.train_step captured ONCE into a hipGraph (torch.cuda.CUDAGraph over the library's launches, the RCCL all-reduce
   and the Adam kernel on the capture stream) and replayed per step: the reference jits the whole step into one XLA

@@ -13,6 +13,7 @@ import sys
 import tempfile
 import types
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,6 +26,10 @@ def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--steps', type=int, default=300)
   ap.add_argument('--lr', type=float, default=2e-3)
+  ap.add_argument('--frozen', action='store_true',
+                  help='the same recovery through training.align_cameras: the fused frozen step (nrf_loss_grad_rays) instead of autograd '
+                       'over render_differentiable.  Its loss is MSE_coarse + MSE_fine against one target, so the fine MLP is set to the '
+                       'coarse one (both terms then have their minimum at the true pose)')
   args = ap.parse_args()
   dev = torch.device('cuda:0')
   with tempfile.TemporaryDirectory() as d:
@@ -57,6 +62,9 @@ def main():
   offset[0, DL['rotation']], offset[0, DL['translation']] = w_off, p_off
   with torch.no_grad():
     start = compose_cameras(table0, offset)   # frame 0 turned by exp(hat w_off) and moved by p_off
+  if args.frozen:
+    frozen_demo(model, fp, table0, start, pixels, index, args)
+    return
   pose = torch.zeros(6, device=dev, requires_grad=True)   # frame 0's (rotation, translation) delta; the other columns stay 0
   opt = torch.optim.Adam([pose], lr=args.lr)
   print(f'frame 0 of {len(ids)}: {pixels.shape[0]} rays; start: position error {p_off.norm().item():.5f}, rotation error '
@@ -78,6 +86,30 @@ def main():
     opt.zero_grad()
     loss.backward()
     opt.step()
+
+
+def frozen_demo(model, fp, table0, start, pixels, index, args):
+  from nerfies_amd import training
+  off = {name: (o, int(np.prod(shape))) for name, o, shape in model.layout.entries}
+  for name, (o, n) in off.items():   # fine MLP := coarse MLP
+    if name.startswith('nerf_mlps_fine'):
+      oc, _ = off[name.replace('nerf_mlps_fine', 'nerf_mlps_coarse')]
+      fp.flat[o:o + n] = fp.flat[oc:oc + n]
+  with torch.no_grad():
+    o, d = rays_from_table(table0, pixels, index)
+    target = model.apply({'params': fp}, {'origins': o, 'directions': d, 'metadata': {}}, {})['fine']['rgb'].clone()
+  batch = {'pixels': pixels, 'item_index': index, 'rgb': target, 'metadata': {}}
+  R0, p0 = table0[0, SL['orientation']].reshape(3, 3).double(), table0[0, SL['position']]
+
+  def errors(table):   # the angle from |R - R0|_F = 2 sqrt(2) sin(angle / 2), in float64
+    half = ((table[0, SL['orientation']].reshape(3, 3).double() - R0).norm() / (2 * 2 ** 0.5)).clamp(max=1.0)
+    return (table[0, SL['position']] - p0).norm().item(), 2 * torch.asin(half).item()
+
+  pos0, rot0 = errors(start)
+  refiner = training.align_cameras(model, fp, start, batch, groups='pose', steps=args.steps, learning_rate=args.lr)
+  pos, rot = errors(refiner.compose())
+  print(f'frozen alignment, {pixels.shape[0]} rays, {args.steps} steps: position error {pos0:.5f} -> {pos:.3e}, rotation error '
+        f'{rot0:.5f} -> {rot:.3e} rad')
 
 
 if __name__ == '__main__':
