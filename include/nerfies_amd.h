@@ -471,6 +471,54 @@ int nrf_warp_points_workspace_bytes(nrf_handle h, int32_t num_points, size_t* by
 int nrf_warp_points(nrf_handle h, const float* params, const float* points, const int32_t* warp_ids, int32_t num_points,
                     const nrf_step_scalars* scalars, float* warped, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Field queries: the NeRF field at arbitrary points (float32 mode) ----
+ * render_samples up to the activations (models.py:230-277): condition inputs, SE3Field warp (unless NRF_FLAG_NO_WARP), posenc,
+ * the NerfMLP of `level`, sigmoid(rgb), sigma_activation(raw) -- no noise term, no compositing.  What a flax user gets from
+ * apply(method=...): a density grid for a mesh or a point cloud, the canonical volume next to a frame's, the SfM points of a
+ * capture against the learnt density.  The entries keep a plan of their own: the handle's ray plan, its stash and the digests
+ * of nrf_debug_plan_digest do not move.  Announced by NRF_HAS_FIELD_QUERY (NRF_VERSION is unchanged). */
+#define NRF_HAS_FIELD_QUERY 1
+#define NRF_QUERY_MAX_POINTS (1 << 24) /* points of one call; more is NRF_E_SHAPE (the caller loops over chunks) */
+#define NRF_GRID_MAX_POINTS (1LL << 40) /* points of a whole nrf_grid (dims[0] * dims[1] * dims[2]); more is NRF_E_SHAPE */
+
+/* Device outputs of a query, N = num_groups * points_per_group rows each; any may be NULL.  rgb == NULL is the density-only
+ * query: a kernel of its own that stops behind the alpha head (same sigma bits as the full query). */
+typedef struct nrf_field_out {
+  float* sigma;         /* (N,)   activated density: what the renderer composites (out4.w) */
+  float* rgb;           /* (N,3)  sigmoid(rgb logits) */
+  float* warped_points; /* (N,3)  the canonical points the MLP saw; needs the warp field on, else NRF_E_UNSUPPORTED */
+} nrf_field_out;
+
+/* A regular grid: point n has i = n % dims[0], j = (n / dims[0]) % dims[1], k = n / (dims[0] * dims[1]) and coordinate
+ * c = origin[c] + (float)idx_c * step[c] (one float32 product, then one float32 sum). */
+typedef struct nrf_grid {
+  float origin[3];
+  float step[3];
+  int32_t dims[3];
+  int32_t reserved;
+} nrf_grid;
+
+/* Workspace of a query of num_groups x points_per_group points; one answer whatever the outputs asked for.  Needs no GPU.
+ * flags: 0 or NRF_FLAG_NO_WARP, as the query itself. */
+int nrf_query_workspace_bytes(nrf_handle h, int32_t num_groups, int32_t points_per_group, uint32_t flags, size_t* bytes);
+
+/* The field at `points` (G,S,3), G = groups->num_rays groups of S = points_per_group points.  The points of group g share
+ * row g of groups->viewdirs, *_ids and *_codes (codes replace ids as in nrf_forward); groups->origins / directions are ignored
+ * and may be NULL.  viewdirs == NULL is NRF_E_UNSUPPORTED when out->rgb is asked for on a use_viewdirs model (a point has no
+ * direction to fall back on).  level: 0 coarse MLP, 1 fine MLP.  flags: 0 or NRF_FLAG_NO_WARP (the points are then canonical
+ * points); every other bit is refused.  A time-encoder model is refused with the warp on, as in nrf_warp_points.  Asynchronous
+ * on `stream`, no allocation; the workspace may be reused by the next query once this one has run. */
+int nrf_query_points(nrf_handle h, const float* params, const nrf_rays* groups, const float* points, int32_t points_per_group,
+                     int32_t level, const nrf_step_scalars* scalars, uint32_t flags, const nrf_field_out* out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
+/* The same at points [first, first + count) of `grid`, formed on the device (no host or framework work per point);
+ * group->num_rays must be 1.  Workspace: nrf_query_workspace_bytes(h, 1, count, flags); a caller walks a large grid in chunks
+ * through one workspace. */
+int nrf_query_grid(nrf_handle h, const float* params, const nrf_rays* group, const nrf_grid* grid, int64_t first, int32_t count,
+                   int32_t level, const nrf_step_scalars* scalars, uint32_t flags, const nrf_field_out* out, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 /* flax.optim.Adam.apply_gradient (training.py:268-269; flax 0.3.4 optim/adam.py):
  * g = grad*grad_scale (grad_scale = 1/world_size folds lax.pmean, training.py:266),
  * m,v updated in place, step = number of updates already applied.  Hyper-parameters are doubles

@@ -244,6 +244,8 @@ struct nrf_handle_s {
   nrf::api::Modes stashed_modes;
   std::vector<nrf::PackDesc> wp_pack;   // pack table of nrf_warp_points (kept alive for the async upload)
   int64_t wp_pack_base = -1;
+  std::vector<nrf::PackDesc> q_pack;    // pack table of nrf_query_points / nrf_query_grid, as wp_pack
+  int q_pack_level = -1;
 };
 
 namespace nrf {

@@ -436,6 +436,16 @@ void launch_chain_fwd32(const ChainFwdArgs& a, bool stash, int grid, hipStream_t
 void launch_chain_fwd_frozen(const ChainFwdArgs& a, bool tile32, int grid, hipStream_t stream);
 void launch_chain_bwd_frozen(const ChainBwdArgs& a0, const ChainBwdArgs* a1, int grid, hipStream_t stream);
 void launch_chain_bwd32(const ChainBwdArgs& a0, const ChainBwdArgs* a1, int grid, hipStream_t stream);
+// chain_query.hip: the kernels of a field query (nrf_query_points / nrf_query_grid).  Density-only chain: prologue, trunk, alpha
+// head (behind the bottleneck on a use_alpha_condition model), one float per row into sigma[rows]; `a` as for launch_chain_fwd
+// (a.out4 / a.condterm unread), 64-row tiles, the same bits as out4.w of the full chain under either tiling
+void launch_chain_density(const ChainFwdArgs& a, float* sigma, int grid, hipStream_t stream);
+// ids[r] = group_ids ? group_ids[r / S] : r / S -- the per-point rows of the SE3 forward's code table
+void launch_field_ids(const int32_t* group_ids, int rows, int S, int32_t* ids, hipStream_t stream);
+// out4[rows] -> sigma[rows], rgb[rows][3] (either may be nullptr)
+void launch_field_unpack(const float4* out4, int rows, float* sigma, float* rgb, hipStream_t stream);
+// points [first, first + count) of a grid -> out[count][3]
+void launch_grid_points(const nrf_grid& g, long long first, int count, float* out, hipStream_t stream);
 // a1 (optional): a second level in the same launch (background points behind the coarse samples)
 void launch_warp_fwd(const WarpFwdArgs& a, const WarpFwdArgs* a1, bool stash, int grid, hipStream_t stream, bool frozen = false);   // frozen: no activation stash
 // a1, a2 (optional): further levels in the same launch; bias partials of all levels go to a.small_part

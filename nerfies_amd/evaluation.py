@@ -238,6 +238,41 @@ def rays_from_camera(camera, metadata: Optional[Dict[str, int]] = None, device='
   return rays
 
 
+def grid_chunks(total: int, chunk: int):
+  """(first, count) pieces that cover [0, total) exactly once, in order, `chunk` points at most each."""
+  return [(first, min(chunk, total - first)) for first in range(0, total, chunk)]
+
+
+def density_grid(model, params, bbox_min, bbox_max, resolution, level='fine', warp_id=None, appearance_id=None, warp_extra=None,
+                 chunk=1 << 21, device=None):
+  """Activated density of the field on a regular grid over the box [bbox_min, bbox_max]: an (X, Y, Z) float32 device tensor, `x`
+  fastest in memory, sampled at the voxel centres.  `resolution`: voxels per axis (an int, or (X, Y, Z)).  `warp_id=None` queries the
+  canonical (template) volume (NRF_FLAG_NO_WARP); an id queries that frame's observation volume through the warp field.
+  `appearance_id`: the appearance code of a use_alpha_condition model (its density depends on it).  The points are formed on the
+  device by nrf_query_grid, `chunk` of them per call through one workspace; the density-only kernel runs (no colour is computed)."""
+  res = (int(resolution),) * 3 if isinstance(resolution, int) else tuple(int(r) for r in resolution)
+  if len(res) != 3 or min(res) <= 0:
+    raise ValueError(f'resolution must be a positive int or (X, Y, Z), got {resolution!r}')
+  lo = [float(v) for v in bbox_min]
+  hi = [float(v) for v in bbox_max]
+  step = [(h - l) / r for l, h, r in zip(lo, hi, res)]
+  origin = [l + 0.5 * s for l, s in zip(lo, step)]
+  if device is None:
+    device = params.flat.device if hasattr(params, 'flat') else 'cuda'
+  metadata = {}
+  if warp_id is not None:
+    metadata['warp'] = torch.tensor([[int(warp_id)]], dtype=torch.int32, device=device)
+  if appearance_id is not None:
+    metadata['appearance'] = torch.tensor([[int(appearance_id)]], dtype=torch.int32, device=device)
+  total = res[0] * res[1] * res[2]
+  chunk = max(1, min(int(chunk), total, 1 << 24))
+  sigma = torch.empty(total, dtype=torch.float32, device=device)
+  for first, count in grid_chunks(total, chunk):
+    model.query_grid(params, origin, step, res, first, count, {'sigma': sigma[first:first + count]}, metadata=metadata,
+                     warp_extra=warp_extra, level=level, use_warp=warp_id is not None, workspace_points=chunk)
+  return sigma.view(res[2], res[1], res[0]).permute(2, 1, 0)
+
+
 def compute_psnr(mse):
   """utils.compute_psnr (utils.py:283-293): -10 log10(mse)."""
   return -10.0 * torch.log10(torch.as_tensor(mse))

@@ -129,6 +129,18 @@ class ProfileEntry(C.Structure):
               ('flops_per_launch', C.c_double)]
 
 
+class FieldOut(C.Structure):
+  """nrf_field_out: the device outputs of a field query, N rows each; a NULL pointer skips that output (rgb NULL: density only)."""
+  _fields_ = [('sigma', C.c_void_p), ('rgb', C.c_void_p), ('warped_points', C.c_void_p)]
+
+
+class Grid(C.Structure):
+  """nrf_grid: point n = (i, j, k) with x fastest, coordinate c = origin[c] + idx_c * step[c]."""
+  _fields_ = [('origin', C.c_float * 3), ('step', C.c_float * 3), ('dims', C.c_int32 * 3), ('reserved', C.c_int32)]
+
+
+NRF_QUERY_MAX_POINTS = 1 << 24   # points of one nrf_query_points / nrf_query_grid call
+NRF_GRID_MAX_POINTS = 1 << 40    # points of a whole nrf_grid
 NRF_OPT_CHAIN_TILE_ROWS = 1
 NRF_OPT_BF16_WGRAD_MERGE = 2
 
@@ -145,6 +157,7 @@ EXPORTS = [
     'nrf_camera_table_project_backward',
     'nrf_train_step_loss_grad_rays', 'nrf_camera_table_compose', 'nrf_camera_table_compose_backward',
     'nrf_loss_grad_rays',
+    'nrf_query_workspace_bytes', 'nrf_query_points', 'nrf_query_grid',
 ]
 
 _lib = None
@@ -203,6 +216,10 @@ def load_library(path=None):
       'nrf_workspace_bytes_ex': [vp, i32, u32, i32, i32, C.POINTER(C.c_size_t)],
       'nrf_warp_points_workspace_bytes': [vp, i32, C.POINTER(C.c_size_t)],
       'nrf_warp_points': [vp, vp, vp, vp, i32, C.POINTER(StepScalars), vp, vp, C.c_size_t, vp],
+      'nrf_query_workspace_bytes': [vp, i32, i32, u32, C.POINTER(C.c_size_t)],
+      'nrf_query_points': [vp, vp, C.POINTER(Rays), vp, i32, i32, C.POINTER(StepScalars), u32, C.POINTER(FieldOut), vp, C.c_size_t, vp],
+      'nrf_query_grid': [vp, vp, C.POINTER(Rays), C.POINTER(Grid), i64, i32, i32, C.POINTER(StepScalars), u32, C.POINTER(FieldOut), vp,
+                         C.c_size_t, vp],
       'nrf_camera_pixels_to_rays': [C.POINTER(CameraDesc), vp, i64, vp, vp, vp, vp],
       'nrf_camera_pixels_to_points': [C.POINTER(CameraDesc), vp, vp, i64, vp, vp],
       'nrf_camera_project': [C.POINTER(CameraDesc), vp, i64, vp, vp],

@@ -393,6 +393,11 @@ class NerfModel:
     r = L.Rays()
     r.num_rays = origins.shape[0]
     r.origins, r.directions, r.viewdirs = _ptr(origins), _ptr(directions), _ptr(viewdirs)
+    self._metadata_into(r, md, device, metadata_encoded, keep)
+    return r, keep
+
+  def _metadata_into(self, r, md, device, metadata_encoded, keep):
+    """The ids / codes / time stamps of `md`, one row per ray (or per group of a field query), into the lib.Rays `r`."""
     time_enc = self.use_warp and self.warp_metadata_encoder_type == 'time'
     for field, cfield, key, width in (('warp_ids', 'warp_codes', 'warp', self.num_warp_features),
                                       ('appearance_ids', 'appearance_codes', 'appearance', self.num_appearance_features),
@@ -412,7 +417,6 @@ class NerfModel:
         t = _ids(src, device)
         setattr(r, field, _ptr(t))
       keep.append(t)
-    return r, keep
 
   def _rand_struct(self, rngs, num_rays, device):
     rnd = L.Rand()
@@ -506,6 +510,95 @@ class NerfModel:
                                  flags, _ptr(rec.ws), rec.ws.numel() * 4, _stream(device)), self.lib)
     del keep, keep2
     return ret
+
+  # ---- field queries: render_samples up to the activations (models.py:230-277) at the caller's points ----
+  QUERY_OUTPUTS = ('sigma', 'rgb', 'warped_points')
+
+  def _query_record(self, num_groups, points_per_group, flags, device) -> CallRecord:
+    """The CallRecord of a field query, its workspace from the cache of `_record` (its own keys: a query has a plan of its own)."""
+    key = ('query', int(num_groups), int(points_per_group), str(device))
+    ws = self._ws.get(key)
+    if ws is None:
+      nbytes = C.c_size_t(0)
+      L.check(self.lib.nrf_query_workspace_bytes(self.handle, int(num_groups), int(points_per_group), flags, C.byref(nbytes)), self.lib)
+      ws = self._ws[key] = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=device)
+    return CallRecord(int(num_groups), ws, flags, self.generation)
+
+  def _query_setup(self, variables, num_groups, viewdirs, metadata, warp_extra, level, use_warp, metadata_encoded, outputs, device):
+    if level not in ('coarse', 'fine'):
+      raise L.NrfError(f"level must be 'coarse' or 'fine', got {level!r}")
+    outputs = tuple(outputs)
+    if not outputs or set(outputs) - set(self.QUERY_OUTPUTS):
+      raise L.NrfError(f'outputs must be a non-empty selection of {self.QUERY_OUTPUTS}, got {outputs}')
+    fp = self.flat_params(variables, device)
+    groups, keep = L.Rays(), []
+    groups.num_rays = int(num_groups)
+    if viewdirs is not None:
+      vd = _f32(viewdirs, device).reshape(-1, 3)
+      if vd.shape[0] != num_groups:
+        raise L.NrfError(f'viewdirs must have one row per group ({num_groups}), got {vd.shape[0]}')
+      groups.viewdirs = _ptr(vd)
+      keep.append(vd)
+    md = {}
+    for k, v in (metadata or {}).items():   # one row per group, whatever leading dimensions the caller's points had
+      v = torch.as_tensor(v, device=device)
+      if v.numel() % num_groups or v.numel() == 0:
+        raise L.NrfError(f'metadata[{k!r}] must have one row per group ({num_groups}), got shape {tuple(v.shape)}')
+      md[k] = v.reshape(num_groups, -1)
+    self._metadata_into(groups, md, device, metadata_encoded, keep)
+    flags = self.flags(no_warp=self.use_warp and not use_warp)
+    return fp, groups, keep, _scalars(warp_extra), flags, 1 if level == 'fine' else 0, outputs
+
+  def query_points(self, variables, points, viewdirs=None, metadata=None, warp_extra=None, level='fine', use_warp=True,
+                   metadata_encoded=False, outputs=('sigma', 'rgb')):
+    """The field at arbitrary points (nrf_query_points): condition inputs, the warp (unless use_warp=False: the points are then
+    canonical points), posenc, the NeRF MLP of `level`, sigmoid(rgb), sigma_activation -- no noise, no compositing.
+    `points`: (..., S, 3); the leading dimensions are flattened into G groups (an (N, 3) input is one group) whose S points share a
+    row of `viewdirs` (G, 3) and of every `metadata` entry ((G, 1) ids, or (G, features) codes with metadata_encoded).  `outputs`
+    selects among 'sigma' (activated density), 'rgb' and 'warped_points'; without 'rgb' the density-only kernel runs.  Returns a
+    dict of device tensors shaped like points[..., 0] (with a trailing 3 for 'rgb' / 'warped_points')."""
+    device = torch.as_tensor(points).device
+    if device.type != 'cuda':
+      raise L.NrfError('points must live on the GPU: the hot path has no CPU fallback')
+    pts = _f32(points, device)
+    if pts.dim() < 2 or pts.shape[-1] != 3:
+      raise L.NrfError(f'points must be (..., S, 3), got {tuple(pts.shape)}')
+    lead, S = tuple(pts.shape[:-2]), pts.shape[-2]
+    G = 1
+    for n in lead:
+      G *= n
+    fp, groups, keep, scal, flags, lv, outputs = self._query_setup(variables, G, viewdirs, metadata, warp_extra, level, use_warp,
+                                                                  metadata_encoded, outputs, device)
+    ret = {k: torch.empty(*lead, S, *(() if k == 'sigma' else (3,)), dtype=torch.float32, device=device) for k in outputs}
+    fo = L.FieldOut(*(_ptr(ret.get(k)) for k in self.QUERY_OUTPUTS))
+    rec = self._query_record(G, S, flags, device)
+    L.check(self.lib.nrf_query_points(self.handle, _ptr(fp.flat), C.byref(groups), _ptr(pts), S, lv, C.byref(scal), flags, C.byref(fo),
+                                      _ptr(rec.ws), rec.ws.numel() * 4, _stream(device)), self.lib)
+    del keep
+    return ret
+
+  def query_grid(self, variables, origin, step, dims, first, count, out, viewdirs=None, metadata=None, warp_extra=None, level='fine',
+                 use_warp=True, metadata_encoded=False, workspace_points=None):
+    """Points [first, first + count) of a regular grid (nrf_query_grid: point n = (i, j, k) with x fastest, coordinate
+    origin + idx * step, formed on the device) into the preallocated tensors of `out` ({'sigma': (count,), 'rgb': (count, 3), ...}).
+    One condition for the whole grid: `viewdirs` (3,) and the metadata rows of ONE group.  `workspace_points`: size the workspace
+    for this many points (a caller that walks a grid in chunks passes its chunk size: one workspace serves every chunk)."""
+    device = next(iter(out.values())).device
+    fp, groups, keep, scal, flags, lv, outputs = self._query_setup(variables, 1, viewdirs, metadata, warp_extra, level, use_warp,
+                                                                  metadata_encoded, tuple(out), device)
+    for k in outputs:
+      want = (count,) if k == 'sigma' else (count, 3)
+      if tuple(out[k].shape) != want or out[k].dtype != torch.float32 or not out[k].is_contiguous():
+        raise L.NrfError(f'query_grid: out[{k!r}] must be a contiguous float32 tensor of shape {want}')
+    grid = L.Grid((C.c_float * 3)(*[float(v) for v in origin]), (C.c_float * 3)(*[float(v) for v in step]),
+                  (C.c_int32 * 3)(*[int(v) for v in dims]), 0)
+    fo = L.FieldOut(*(_ptr(out.get(k)) for k in self.QUERY_OUTPUTS))
+    rec = self._query_record(1, max(int(workspace_points or 0), int(count)), flags, device)
+    stream = _stream(device) if device.type == 'cuda' else None
+    L.check(self.lib.nrf_query_grid(self.handle, _ptr(fp.flat), C.byref(groups), C.byref(grid), int(first), int(count), lv,
+                                    C.byref(scal), flags, C.byref(fo), _ptr(rec.ws), rec.ws.numel() * 4, stream), self.lib)
+    del keep
+    return out
 
   def backward(self, variables, rays_dict, d_rgb_coarse=None, d_rgb_fine=None, grad_out: torch.Tensor = None, d_out=None,
                ray_grads=False):

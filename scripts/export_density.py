@@ -1,0 +1,130 @@
+#!/usr/bin/env python
+"""Density grid of a trained field: loads the experiment's latest checkpoint, takes the box of the capture's scene points
+(points.npy, in the normalised scene frame) and queries the activated density on a regular grid through the library's field
+query (evaluation.density_grid -> nrf_query_grid: the points are formed on the device, the density-only kernel runs).
+
+  python scripts/export_density.py --base_folder EXP --data_dir CAPTURE --gin_configs EXP/config.gin \\
+      --resolution 128 --frame 000012            # the observation volume of frame 000012 (through the warp field)
+  python scripts/export_density.py ... --canonical   # the canonical (template) volume: the warp field is skipped
+
+Writes, next to the checkpoints' experiment directory:
+  density_<name>.npy   float32 (X, Y, Z) sigma at the voxel centres (<name> = the frame id, or 'canonical'), and
+  density_<name>.ply   ASCII point cloud of the voxel centres with sigma > --threshold, coloured by a full query along a fixed
+                       view direction.
+There is no mesh extraction: the .npy grid is what a marching-cubes tool reads."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import train as train_driver   # noqa: E402
+from nerfies_amd import checkpoints, configs, evaluation, models, training   # noqa: E402
+from nerfies_amd import gin_lite as gin   # noqa: E402
+
+VIEW_DIRECTION = (0.0, 0.0, 1.0)   # the direction every exported colour is queried along
+
+
+def parse_flags(argv=None):
+  """The drivers' flags (train.py) plus the export's own."""
+  p = argparse.ArgumentParser(add_help=False)
+  p.add_argument('--resolution', type=int, nargs='+', default=[64], help='voxels per axis: one number, or X Y Z')
+  which = p.add_mutually_exclusive_group(required=True)
+  which.add_argument('--frame', default=None, metavar='ITEM_ID', help="query that frame's observation volume (its warp / appearance / camera ids)")
+  which.add_argument('--canonical', action='store_true', help='query the canonical volume (NRF_FLAG_NO_WARP)')
+  p.add_argument('--threshold', type=float, default=10.0, help='voxels with sigma above it go into the PLY')
+  p.add_argument('--level', default='fine', choices=['coarse', 'fine'])
+  p.add_argument('--margin', type=float, default=0.0, help="grow the scene points' box by this fraction of its size on every side")
+  own, rest = p.parse_known_args(argv)
+  if len(own.resolution) not in (1, 3):
+    p.error('--resolution takes one number or three')
+  flags = train_driver.parse_flags(rest)
+  for k, v in vars(own).items():
+    setattr(flags, k, v)
+  return flags
+
+
+def write_ply(path, xyz, rgb):
+  """ASCII PLY of points (N, 3) with colours (N, 3) in [0, 1]."""
+  rgb8 = np.clip(np.rint(rgb * 255.0), 0, 255).astype(np.uint8)
+  with open(path, 'w') as f:
+    f.write('ply\nformat ascii 1.0\n')
+    f.write(f'element vertex {len(xyz)}\n')
+    f.write('property float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n')
+    for (x, y, z), (r, g, b) in zip(xyz, rgb8):
+      f.write(f'{x:.6f} {y:.6f} {z:.6f} {r} {g} {b}\n')
+
+
+def main(argv=None):
+  flags = parse_flags(argv)
+  if flags.bf16:
+    raise SystemExit('--bf16: a field query runs in the float32 mode')
+  gin.parse_config_files_and_bindings(config_files=flags.gin_configs, bindings=flags.gin_bindings, skip_unknown=True)
+  exp_config = configs.ExperimentConfig()
+  model_config = configs.ModelConfig(use_stratified_sampling=False)
+  _, _, device = train_driver.init_distributed()
+  exp_dir = flags.base_folder if not exp_config.subname else os.path.join(flags.base_folder, exp_config.subname)
+  checkpoint_dir = os.path.join(exp_dir, 'checkpoints')
+  datasource = train_driver.make_datasource(flags, exp_config, model_config)
+  model, params = models.construct_nerf(
+      20200823, model_config, batch_size=0, appearance_ids=datasource.appearance_ids, camera_ids=datasource.camera_ids,
+      warp_ids=datasource.warp_ids, near=datasource.near, far=datasource.far, device=device)
+  if checkpoints.latest_checkpoint(checkpoint_dir) is None:
+    raise FileNotFoundError(f'no checkpoint under {checkpoint_dir}')
+  state = checkpoints.restore_checkpoint(checkpoint_dir, training.TrainState(optimizer=training.Optimizer(params)))
+  target = state.optimizer.target
+
+  # the ids of the queried frame; the canonical volume borrows the first training frame's appearance / camera ids (its density
+  # does not depend on them unless the model conditions the alpha head, its colour does)
+  item = flags.frame if flags.frame is not None else datasource.train_ids[0]
+  if flags.frame is not None and flags.frame not in list(datasource.train_ids) + list(datasource.val_ids):
+    raise SystemExit(f'--frame {flags.frame}: not an item of the capture')
+  use_warp = bool(model.use_warp) and not flags.canonical
+  if use_warp and model.warp_metadata_encoder_type == 'time':
+    raise SystemExit('--frame: a field query takes warp ids, not the time encoder (use --canonical)')
+  warp_id = datasource.get_warp_id(item) if use_warp else None
+  app_id = datasource.get_appearance_id(item) if model.use_appearance_metadata else None
+  cam_id = datasource.get_camera_id(item) if model.use_camera_metadata else None
+  name = flags.frame if flags.frame is not None else 'canonical'
+
+  points = datasource.load_points()
+  lo, hi = points.min(0).astype(np.float64), points.max(0).astype(np.float64)
+  pad = flags.margin * (hi - lo)
+  lo, hi = lo - pad, hi + pad
+  res = tuple(flags.resolution * 3 if len(flags.resolution) == 1 else flags.resolution)
+  sigma = evaluation.density_grid(model, target, lo, hi, res, level=flags.level, warp_id=warp_id,
+                                  appearance_id=app_id if model.use_alpha_condition else None, warp_extra=state.warp_extra)
+  grid = sigma.cpu().numpy()
+  npy = os.path.join(exp_dir, f'density_{name}.npy')
+  np.save(npy, np.ascontiguousarray(grid))
+
+  # voxel centres over the threshold, coloured by a full query along one view direction
+  idx = torch.nonzero(sigma > flags.threshold)                       # (M, 3) voxel indices (i, j, k)
+  step = torch.tensor([(h - l) / r for l, h, r in zip(lo, hi, res)], dtype=torch.float64, device=sigma.device)
+  centres = (torch.tensor(lo, dtype=torch.float64, device=sigma.device) + (idx.double() + 0.5) * step).float()
+  rgb = torch.zeros(0, 3, device=sigma.device)
+  if idx.shape[0] > 0:
+    metadata = {}
+    for key, val in (('warp', warp_id), ('appearance', app_id), ('camera', cam_id)):
+      if val is not None:
+        metadata[key] = torch.tensor([[int(val)]], dtype=torch.int32, device=sigma.device)
+    view = torch.tensor([VIEW_DIRECTION], dtype=torch.float32, device=sigma.device)
+    parts = []
+    for first in range(0, centres.shape[0], 1 << 21):
+      out = model.query_points(target, centres[first:first + (1 << 21)], viewdirs=view, metadata=metadata, warp_extra=state.warp_extra,
+                               level=flags.level, use_warp=use_warp, outputs=('rgb',))
+      parts.append(out['rgb'])
+    rgb = torch.cat(parts, 0)
+  ply = os.path.join(exp_dir, f'density_{name}.ply')
+  write_ply(ply, centres.cpu().numpy(), rgb.cpu().numpy())
+  print(f'density_{name}: {res[0]} x {res[1]} x {res[2]} voxels over [{lo.round(4).tolist()}, {hi.round(4).tolist()}], sigma in '
+        f'[{grid.min():.4g}, {grid.max():.4g}], {idx.shape[0]} voxels over {flags.threshold:g} -> {npy}, {ply}', flush=True)
+  return {'npy': npy, 'ply': ply, 'resolution': res, 'num_vertices': int(idx.shape[0]), 'bbox': (lo, hi)}
+
+
+if __name__ == '__main__':
+  main(sys.argv[1:])
