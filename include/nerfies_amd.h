@@ -476,7 +476,9 @@ int nrf_warp_points(nrf_handle h, const float* params, const float* points, cons
  * the NerfMLP of `level`, sigmoid(rgb), sigma_activation(raw) -- no noise term, no compositing.  What a flax user gets from
  * apply(method=...): a density grid for a mesh or a point cloud, the canonical volume next to a frame's, the SfM points of a
  * capture against the learnt density.  The entries keep a plan of their own: the handle's ray plan, its stash and the digests
- * of nrf_debug_plan_digest do not move.  Announced by NRF_HAS_FIELD_QUERY (NRF_VERSION is unchanged). */
+ * of nrf_debug_plan_digest do not move -- unless a query (or nrf_warp_points) is handed the very workspace a ray plan's tables or
+ * stash live in: it writes over them, so the handle forgets that upload and stash (the next nrf_forward uploads its tables again,
+ * nrf_backward returns NRF_E_STATE until then).  Announced by NRF_HAS_FIELD_QUERY (NRF_VERSION is unchanged). */
 #define NRF_HAS_FIELD_QUERY 1
 #define NRF_QUERY_MAX_POINTS (1 << 24) /* points of one call; more is NRF_E_SHAPE (the caller loops over chunks) */
 #define NRF_GRID_MAX_POINTS (1LL << 40) /* points of a whole nrf_grid (dims[0] * dims[1] * dims[2]); more is NRF_E_SHAPE */

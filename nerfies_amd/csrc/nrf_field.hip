@@ -1,0 +1,284 @@
+// Stand-alone field entries of the C-ABI layer: parts of the field run outside the ray plan, on the ray path's own builders
+// (nrf_handle.h).  Each carves a small plan of its own: h->plan is neither read nor written, so a ray plan's digest and a pending
+// nrf_backward are as they were -- unless the entry is handed the very memory that plan's tables or stash live in (forget_workspace).
+#include "nrf_handle.h"
+
+using namespace nrf;
+using namespace nrf::api;
+
+namespace {
+// an entry writes over what a ray plan keeps in `ws`: its tables and stash are forgotten instead of left stale
+void forget_workspace(nrf_handle h, const void* ws) {
+  if (h->uploaded_ws == ws) h->uploaded_ws = nullptr;   // a following nrf_forward uploads its tables again
+  if (h->stashed_ws == ws) h->stashed_ws = nullptr;     // a following nrf_backward is refused (NRF_E_STATE)
+}
+// a model narrower than the kernels runs on its zero-padded image: the embed table to ws + emb_f, the image at ws + ip_f (as embed_params)
+const float* embed_side(nrf_handle h, const float* params_x, float* ws, size_t emb_f, size_t ip_f, hipStream_t st) {
+  const hipError_t e = hipMemcpyAsync(ws + emb_f, h->emb.data(), h->emb.size() * sizeof(EmbedDesc), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) { fail_hip(e, "upload embed table"); return nullptr; }
+  return embed_params(h, params_x, reinterpret_cast<const EmbedDesc*>(ws + emb_f), ws + ip_f, false, st);
+}
+// the entry's pack table, rebuilt when what it was built for changes
+template <class Build> void refresh(SidePack& c, int64_t key, Build build) {
+  if (c.key == key) return;
+  c.descs.clear();
+  build(c.descs);
+  c.key = key;
+}
+
+// ---- Stand-alone SE3 field on arbitrary points (create_warp_field(num_batch_dims=1), models.py:165-184; the field
+// training.compute_background_loss applies, training.py:127-130).  Workspace:
+// [pack descriptors | packed trunk weights | padded output | tile counter | embed table, padded params (narrow trunks)]
+struct WarpPointsPlan { size_t desc_f, wpk_f, out_f, ctr_f, emb_f = 0, ip_f = 0, total_f; int ntiles; };
+WarpPointsPlan warp_points_plan(nrf_handle h, int n) {
+  WarpPointsPlan q;
+  q.ntiles = (n + TILE_ROWS - 1) / TILE_ROWS;
+  Carve c;
+  q.desc_f = c.take(16 * sizeof(PackDesc) / 4);
+  q.wpk_f = c.take(h->wpk.total);
+  q.out_f = c.take((size_t)q.ntiles * TILE_ROWS * 3);
+  q.ctr_f = c.take(16);
+  if (h->d.warp_field_type == NRF_WARP_TRANSLATION || h->wxdepth != WARP_DEPTH || h->wxwidth != WARP_W) {
+    // no rotation head in the caller's tree, or a trunk shallower / narrower than the kernels': run on the padded image
+    q.emb_f = c.take((h->emb.size() + 1) * sizeof(EmbedDesc) / 4);
+    q.ip_f = c.take((size_t)h->nparams);
+  }
+  q.total_f = c.o;
+  return q;
+}
+
+// ---- Field queries (nrf_query_points / nrf_query_grid): render_samples up to the activations (models.py:230-277) at the
+// caller's points.  Workspace:
+// [pack descriptors | embed table | padded params | forward image of one MLP | SE3 trunk image | tile counters |
+//  cond, condterm, alpha_ct of G groups | grid points | per-point code rows | warped points | out4]
+struct QueryPlan { size_t desc_f, emb_f = 0, ip_f = 0, wpk_f, wwpk_f, ctr_f, cond_f, condterm_f, alpha_ct_f, points_f, ids_f = 0, wpoints_f = 0, out4_f, total_f; int N, ntiles; };
+constexpr int QUERY_MAX_DESCS = 32;   // 11 + rgb branch layers 1..3 + 7 of the SE3 trunk
+QueryPlan query_plan(const nrf_handle_s* h, int G, int S) {
+  QueryPlan q;
+  q.N = G * S;
+  q.ntiles = (q.N + TILE_ROWS - 1) / TILE_ROWS;
+  const size_t rows_pad = (size_t)q.ntiles * TILE_ROWS;
+  Carve c;
+  q.desc_f = c.take(QUERY_MAX_DESCS * sizeof(PackDesc) / 4);
+  if (h->embed) {   // a model narrower than the kernels runs on its zero-padded image
+    q.emb_f = c.take((h->emb.size() + 1) * sizeof(EmbedDesc) / 4);
+    q.ip_f = c.take((size_t)h->nparams);
+  }
+  q.wpk_f = c.take(h->pk.total);
+  q.wwpk_f = h->warp ? c.take(h->wpk.total) : 0;
+  q.ctr_f = c.take(16);
+  q.cond_f = c.take((size_t)G * (h->R > 0 ? h->R : 1));
+  q.condterm_f = c.take((size_t)G * RGB_W);
+  q.alpha_ct_f = c.take((size_t)G);
+  q.points_f = c.take(rows_pad * 3);   // nrf_query_grid forms its points here
+  if (h->warp) {
+    q.ids_f = c.take(rows_pad);
+    q.wpoints_f = c.take(rows_pad * 3);
+  }
+  q.out4_f = c.take(rows_pad * 4);
+  q.total_f = c.o;
+  return q;
+}
+
+// the flag word of a query: 0 or NRF_FLAG_NO_WARP; every other bit by its name
+int query_flags(uint32_t flags) {
+  for (const FlagName& f : FLAG_NAMES)
+    if (flags & f.bit & ~(uint32_t)NRF_FLAG_NO_WARP) {
+      snprintf(g_err, sizeof(g_err), "%s: a field query runs in the float32 mode without a stash; flags: 0 or NRF_FLAG_NO_WARP", f.name);
+      return NRF_E_UNSUPPORTED;
+    }
+  if (flags & ~(uint32_t)NRF_FLAG_NO_WARP) {
+    snprintf(g_err, sizeof(g_err), "unknown bits 0x%x in flags; a field query takes 0 or NRF_FLAG_NO_WARP", flags & ~(uint32_t)NRF_FLAG_NO_WARP);
+    return NRF_E_UNSUPPORTED;
+  }
+  return NRF_OK;
+}
+
+int query_shape(int G, int S) {
+  if (G <= 0) return fail(NRF_E_SHAPE, "num_groups (groups->num_rays) must be positive");
+  if (S <= 0) return fail(NRF_E_SHAPE, "points_per_group / count must be positive");
+  if ((int64_t)G * S > NRF_QUERY_MAX_POINTS) return fail(NRF_E_SHAPE, "a field query takes at most 1 << 24 points per call (NRF_QUERY_MAX_POINTS)");
+  return NRF_OK;
+}
+
+// both entries behind their own argument checks; points == nullptr: the grid's, already formed at q.points_f
+int query_impl(nrf_handle h, const float* params_x, const nrf_rays* groups, const float* points, int S, int level,
+               const nrf_step_scalars* sc, uint32_t flags, const nrf_field_out* out, float* ws, const QueryPlan& q, hipStream_t st) {
+  const int G = groups->num_rays, N = q.N;
+  const bool warp_on = h->warp && !(flags & NRF_FLAG_NO_WARP);
+  const bool full = out->rgb != nullptr;
+  Prof& pf = h->prof;
+  query_device(h);
+  forget_workspace(h, ws);
+  if (!points) points = ws + q.points_f;
+  const float* params = params_x;
+  if (h->embed && !(params = embed_side(h, params_x, ws, q.emb_f, q.ip_f, st))) return NRF_E_HIP;
+  // forward image of the asked level at the handle's PackOffsets (the transposed images' room stays unwritten and unread), and the
+  // SE3 trunk's.  The offsets do not depend on the number of points: the table is rebuilt when the level changes
+  SidePack& pack = h->q_pack;
+  refresh(pack, level, [&](std::vector<PackDesc>& v) {
+    mlp_pack_descs(h, level, (int64_t)q.wpk_f, false, v);
+    if (h->warp) warp_pack_descs(h, h->wpo, (int64_t)q.wwpk_f, false, v);
+  });
+  if ((int)pack.descs.size() > QUERY_MAX_DESCS) return fail(NRF_E_STATE, "field query: pack table larger than its workspace region");
+  hipError_t e = hipMemcpyAsync(ws + q.desc_f, pack.descs.data(), pack.descs.size() * sizeof(PackDesc), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return fail_hip(e, "upload query pack table");
+  if (tile_counter_or_null(ws + q.ctr_f, 0)) {   // NRF_DYNAMIC_TILES experiment only
+    e = hipMemsetAsync(ws + q.ctr_f, 0, 16 * sizeof(int), st);
+    if (e != hipSuccess) return fail_hip(e, "zero tile counters");
+  }
+  pf.begin("query_prep", 0, st);   // no return between a begin and its end
+  launch_pack(reinterpret_cast<const PackDesc*>(ws + q.desc_f), (int)pack.descs.size(), params, ws, st);
+  // per-group terms (models.py:186-228): the full query's condition term; the density-only query of a use_alpha_condition model
+  // needs the appearance code's term of the alpha head alone, so ray_prep runs on the appearance columns only (same kernel, same
+  // fmaf chain: the same alpha_ct bits) and no view direction or camera code is read
+  if (full || h->A > 0) {
+    const RayPrepLevel lv{level, ws + q.condterm_f, ws + q.alpha_ct_f};
+    launch_ray_prep(ray_prep_args(h, params, groups, groups->viewdirs, ws + q.cond_f, &lv, 1, !full), st);
+  }
+  pf.end(st);
+  if (warp_on) {
+    // per-point rows of the code table: group g's id, or row g of the caller's codes (metadata_encoded).  The SE3 kernel has two
+    // prologues: `row / S` ids together with x = o + z d formed from rays, or explicit points together with ONE ID PER POINT
+    // (warp_chain.hip: points_in -> point_ids[r]); explicit points with per-group ids is neither, and giving the kernel a third
+    // would change a kernel every plan runs.  So the ids are written out: 4 bytes per row next to a trunk of 1.6e5 MACs, below
+    // the resolution of the 128^3 measurement (profiles/field_query.md)
+    int32_t* ids = reinterpret_cast<int32_t*>(ws + q.ids_f);
+    launch_field_ids(groups->warp_codes ? nullptr : groups->warp_ids, N, S, ids, st);
+    WarpFwdArgs wa = warp_points_args(h, params, h->wpo, ws + q.wwpk_f, sc, points, ids, N, ws + q.wpoints_f);
+    if (groups->warp_codes) wa.embed_table = groups->warp_codes;
+    wa.tile_counter = tile_counter_or_null(ws + q.ctr_f, 0);
+    pf.begin("query_warp", warp_fwd_flops_row(h) * N, st);
+    launch_warp_fwd(wa, nullptr, false, tile_grid(wa.ntiles, warp_grid_mul(), h->num_cus), st);
+    pf.end(st);
+    points = ws + q.wpoints_f;
+  }
+  ChainFwdArgs a = chain_model_args(h, params, level, ws + q.alpha_ct_f);
+  a.wpk = ws + q.wpk_f; a.condterm = ws + q.condterm_f; a.points = points; a.out4 = reinterpret_cast<float4*>(ws + q.out4_f);
+  a.S = S; a.B = G; a.rows = N; a.ntiles = q.ntiles;
+  a.tile_counter = tile_counter_or_null(ws + q.ctr_f, 1);
+  const ChainTiling t = chain_fwd_tiling(h, q.ntiles, full);   // the density chain is built on 64-row tiles only (chain_query.hip)
+  a.k_old = t.k_old;
+  if (full) {
+    pf.begin("query_mlp", fwd_flops_row(h) * N, st);
+    if (t.c32) launch_chain_fwd32(a, false, t.grid, st);
+    else launch_chain_fwd(a, false, t.grid, st);
+    pf.end(st);
+    pf.begin("query_unpack", 0, st);
+    launch_field_unpack(a.out4, N, out->sigma, out->rgb, st);
+    pf.end(st);
+  } else if (out->sigma) {
+    pf.begin("query_density", density_flops_row(h) * N, st);
+    launch_chain_density(a, out->sigma, t.grid, st);
+    pf.end(st);
+  }
+  if (out->warped_points) {
+    e = hipMemcpyAsync(out->warped_points, ws + q.wpoints_f, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return fail_hip(e, "copy warped points");
+  }
+  return check_launch("nrf_query_points");
+}
+
+// what both entries check of everything but the points
+int query_args(nrf_handle h, const float* params, const nrf_rays* groups, int S, int level, const nrf_step_scalars* sc, uint32_t flags,
+               const nrf_field_out* out, const void* workspace) {
+  if (!h) return fail(NRF_E_NULL, "handle is null");
+  if (!params) return fail(NRF_E_NULL, "params is null");
+  if (!groups) return fail(NRF_E_NULL, "groups is null");
+  if (!sc) return fail(NRF_E_NULL, "scalars (nrf_step_scalars) is null");
+  if (!out) return fail(NRF_E_NULL, "out (nrf_field_out) is null");
+  if (!workspace) return fail(NRF_E_NULL, "workspace is null");
+  CK(query_flags(flags));
+  CK(query_shape(groups->num_rays, S));
+  if (level != 0 && level != 1) return fail(NRF_E_SHAPE, "level must be 0 (coarse) or 1 (fine)");
+  if (level >= h->nlevels) return fail(NRF_E_SHAPE, "level = 1: the model has no fine level (num_fine_samples == 0)");
+  const bool warp_on = h->warp && !(flags & NRF_FLAG_NO_WARP);
+  if (out->warped_points && !warp_on)
+    return fail(NRF_E_UNSUPPORTED, "the warped_points output needs the warp field (a model with use_warp, no NRF_FLAG_NO_WARP)");
+  if (warp_on && h->time_enc)
+    return fail(NRF_E_UNSUPPORTED, "a field query takes warp ids or codes: not built for the time encoder with the warp on (NRF_FLAG_NO_WARP runs)");
+  if (out->rgb && h->d.use_viewdirs && !groups->viewdirs)
+    return fail(NRF_E_UNSUPPORTED, "out->rgb on a use_viewdirs model needs groups->viewdirs (a point has no direction to fall back on)");
+  return require_ids_or_codes(h, groups, out->rgb != nullptr, out->rgb || out->sigma, warp_on);
+}
+}  // namespace
+
+extern "C" {
+
+int nrf_warp_points_workspace_bytes(nrf_handle h, int32_t num_points, size_t* bytes) {
+  if (!h || !bytes) return fail(NRF_E_NULL, "null");
+  if (!h->warp) return fail(NRF_E_UNSUPPORTED, "model has no warp field");
+  if (num_points <= 0) return fail(NRF_E_SHAPE, "num_points must be positive");
+  *bytes = warp_points_plan(h, num_points).total_f * sizeof(float);
+  return NRF_OK;
+}
+
+int nrf_warp_points(nrf_handle h, const float* params, const float* points, const int32_t* warp_ids, int32_t num_points,
+                    const nrf_step_scalars* scalars, float* warped, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!h || !params || !points || !warp_ids || !scalars || !warped || !workspace) return fail(NRF_E_NULL, "null argument");
+  if (!h->warp) return fail(NRF_E_UNSUPPORTED, "model has no warp field");
+  if (h->time_enc) return fail(NRF_E_UNSUPPORTED, "nrf_warp_points takes warp ids: not built for the time encoder");
+  if (num_points <= 0) return fail(NRF_E_SHAPE, "num_points must be positive");
+  query_device(h);
+  const WarpPointsPlan q = warp_points_plan(h, num_points);
+  if (workspace_bytes < q.total_f * sizeof(float)) return fail(NRF_E_WORKSPACE, "workspace too small (nrf_warp_points_workspace_bytes)");
+  float* ws = (float*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  forget_workspace(h, ws);
+  const bool padded = q.ip_f != 0;
+  if (padded && !(params = embed_side(h, params, ws, q.emb_f, q.ip_f, st))) return NRF_E_HIP;
+  const WarpParamOffsets& wo = padded ? h->wpo : h->xwpo;   // else the caller's buffer: external offsets
+  SidePack& pack = h->wp_pack;
+  refresh(pack, (int64_t)q.wpk_f, [&](std::vector<PackDesc>& v) { warp_pack_descs(h, wo, (int64_t)q.wpk_f, false, v); });
+  hipError_t e = hipMemcpyAsync(ws + q.desc_f, pack.descs.data(), pack.descs.size() * sizeof(PackDesc), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return fail_hip(e, "upload warp pack table");
+  launch_pack(reinterpret_cast<const PackDesc*>(ws + q.desc_f), (int)pack.descs.size(), params, ws, st);
+  WarpFwdArgs a = warp_points_args(h, params, wo, ws + q.wpk_f, scalars, points, warp_ids, num_points, ws + q.out_f);
+  e = hipMemsetAsync(ws + q.ctr_f, 0, 16 * sizeof(int), st);
+  if (e != hipSuccess) return fail_hip(e, "zero tile counter");
+  a.tile_counter = tile_counter_or_null(ws + q.ctr_f, 0);
+  launch_warp_fwd(a, nullptr, false, tile_grid(a.ntiles, 2, h->num_cus), st);
+  e = hipMemcpyAsync(warped, ws + q.out_f, (size_t)num_points * 3 * sizeof(float), hipMemcpyDeviceToDevice, st);
+  if (e != hipSuccess) return fail_hip(e, "copy warped points");
+  return check_launch("nrf_warp_points");
+}
+
+int nrf_query_workspace_bytes(nrf_handle h, int32_t num_groups, int32_t points_per_group, uint32_t flags, size_t* bytes) {
+  if (!h || !bytes) return fail(NRF_E_NULL, "handle / bytes is null");
+  CK(query_flags(flags));
+  CK(query_shape(num_groups, points_per_group));
+  *bytes = query_plan(h, num_groups, points_per_group).total_f * sizeof(float);
+  return NRF_OK;
+}
+
+int nrf_query_points(nrf_handle h, const float* params, const nrf_rays* groups, const float* points, int32_t points_per_group,
+                     int32_t level, const nrf_step_scalars* scalars, uint32_t flags, const nrf_field_out* out, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  if (h && !points) return fail(NRF_E_NULL, "points is null");
+  CK(query_args(h, params, groups, points_per_group, level, scalars, flags, out, workspace));
+  const QueryPlan q = query_plan(h, groups->num_rays, points_per_group);
+  if (workspace_bytes < q.total_f * sizeof(float)) return fail(NRF_E_WORKSPACE, "workspace too small (see nrf_query_workspace_bytes)");
+  return query_impl(h, params, groups, points, points_per_group, level, scalars, flags, out, (float*)workspace, q, (hipStream_t)stream);
+}
+
+int nrf_query_grid(nrf_handle h, const float* params, const nrf_rays* group, const nrf_grid* grid, int64_t first, int32_t count,
+                   int32_t level, const nrf_step_scalars* scalars, uint32_t flags, const nrf_field_out* out, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+  if (h && !grid) return fail(NRF_E_NULL, "grid is null");
+  CK(query_args(h, params, group, count, level, scalars, flags, out, workspace));
+  if (group->num_rays != 1) return fail(NRF_E_SHAPE, "nrf_query_grid: group->num_rays must be 1 (one condition for the whole grid)");
+  if (grid->dims[0] <= 0 || grid->dims[1] <= 0 || grid->dims[2] <= 0) return fail(NRF_E_SHAPE, "grid dims must be positive");
+  // at most 2^40 points in a grid: the product of three int32 extents cannot wrap int64 behind this
+  const int64_t plane = (int64_t)grid->dims[0] * grid->dims[1];
+  if (plane > NRF_GRID_MAX_POINTS || plane * grid->dims[2] > NRF_GRID_MAX_POINTS)
+    return fail(NRF_E_SHAPE, "grid dims: more than NRF_GRID_MAX_POINTS (1 << 40) points in dims[0] * dims[1] * dims[2]");
+  const int64_t total = plane * grid->dims[2];
+  if (first < 0 || first + count > total) return fail(NRF_E_SHAPE, "first + count runs beyond the grid (dims[0] * dims[1] * dims[2] points)");
+  const QueryPlan q = query_plan(h, 1, count);
+  if (workspace_bytes < q.total_f * sizeof(float)) return fail(NRF_E_WORKSPACE, "workspace too small (see nrf_query_workspace_bytes)");
+  query_device(h);
+  launch_grid_points(*grid, first, count, (float*)workspace + q.points_f, (hipStream_t)stream);
+  return query_impl(h, params, group, nullptr, count, level, scalars, flags, out, (float*)workspace, q, (hipStream_t)stream);
+}
+
+}  // extern "C"

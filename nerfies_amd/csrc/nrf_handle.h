@@ -1,6 +1,6 @@
-// Internal to the C-ABI layer (nrf_plan.hip / nrf_run.hip / nrf_api.hip): the handle, the workspace plan, the region profiler and the
-// functions the three translation units call across.  Round 6: csrc/nrf_api.hip (2,400 lines: plan building, descriptor tables, launch
-// sequences, every entry point, debug hooks) was cut along those lines, no behaviour change.
+// Internal to the C-ABI layer (nrf_plan.hip / nrf_run.hip / nrf_field.hip / nrf_api.hip): the handle, the workspace plan, the region
+// profiler and the functions the four translation units call across -- among them the builders the ray path (nrf_run.hip) and the
+// stand-alone field entries (nrf_field.hip) share, each defined in the unit that owns its concept.
 #pragma once
 #include "../../include/nerfies_amd.h"
 
@@ -42,6 +42,17 @@ inline int fail_hip(hipError_t e, const char* where) {
 
 constexpr size_t ALIGN_F = 64;   // workspace sub-buffers are aligned to 64 floats (256 B)
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+struct Carve {   // the one carving rule of every workspace plan (the ray plan's Planner, nrf_field.hip's side plans)
+  size_t o = 0;   // floats laid out
+  size_t take(size_t n) { size_t r = o; o = align_up(o + n, ALIGN_F); return r; }
+};
+// pack table of a stand-alone field entry, kept alive for its async upload, and what it was built for
+struct SidePack { std::vector<PackDesc> descs; int64_t key = -1; };
+// every bit of a flag word, by its name
+constexpr struct FlagName { uint32_t bit; const char* name; } FLAG_NAMES[] = {
+    {NRF_FLAG_TRAIN, "NRF_FLAG_TRAIN"}, {NRF_FLAG_NO_WARP, "NRF_FLAG_NO_WARP"}, {NRF_FLAG_BF16, "NRF_FLAG_BF16"},
+    {NRF_FLAG_WARP_JACOBIAN, "NRF_FLAG_WARP_JACOBIAN"}, {NRF_FLAG_WARP_F32, "NRF_FLAG_WARP_F32"}, {NRF_FLAG_BF16X3, "NRF_FLAG_BF16X3"},
+    {NRF_FLAG_RAY_GRADS, "NRF_FLAG_RAY_GRADS"}, {NRF_FLAG_FROZEN, "NRF_FLAG_FROZEN"}};
 // grid of a launch whose workgroups walk `ntiles` tiles: one workgroup per tile, at most `per_cu` on each CU
 inline int tile_grid(int ntiles, int per_cu, int num_cus) { return ntiles < per_cu * num_cus ? ntiles : per_cu * num_cus; }
 constexpr size_t TIMELINE_LEVEL_F = 2 * (256 + 512 + 4 * 2048);   // floats of one level's record in WsPlan::timeline (uint64 stamps)
@@ -134,7 +145,6 @@ struct WsPlan {
   std::vector<WgradGroup> groups;
   std::vector<ReduceDesc> reduce;
 };
-
 
 // What a call runs: forward_impl decides it once (nrf_run.hip forward_modes), backward_impl reads it back from the stash's handle
 enum class WarpTrunk { F32, BF16, X3 };   // warp_chain.hip / warp_bf16.hip / warp_bf16x3.hip
@@ -242,10 +252,7 @@ struct nrf_handle_s {
   uint64_t stashed_plan = 0;   // WsPlan::serial of the stashed forward
   int stashed_B = -1;
   nrf::api::Modes stashed_modes;
-  std::vector<nrf::PackDesc> wp_pack;   // pack table of nrf_warp_points (kept alive for the async upload)
-  int64_t wp_pack_base = -1;
-  std::vector<nrf::PackDesc> q_pack;    // pack table of nrf_query_points / nrf_query_grid, as wp_pack
-  int q_pack_level = -1;
+  nrf::api::SidePack wp_pack, q_pack;   // nrf_warp_points (key: its image's offset) / the field queries (key: the level)
 };
 
 namespace nrf {
@@ -254,18 +261,31 @@ namespace api {
 // nrf_plan.hip: parameter layout, pack tables, the workspace plan of (model, num_rays, flags), its descriptor tables
 void build_layout(nrf_handle h);
 void build_pack_offsets(nrf_handle h);
-int k_old_for(int ntiles, int grid, int num_cus, double dflt_share);
 int warp_grid_mul();
 int* tile_counter_or_null(float* base, int idx);
-uint32_t plan_flags(uint32_t flags);
-bool chain32_for(const nrf_handle_s* h, int ntiles, bool reverse = false);
+// tiling of a float32 forward chain launch over `ntiles` 64-row tiles; allow32 = false: a chain built on 64-row tiles only
+struct ChainTiling { bool c32; int grid, k_old; };
+ChainTiling chain_fwd_tiling(const nrf_handle_s* h, int ntiles, bool allow32);
 void build_plan(nrf_handle h, int B, uint32_t flags, int bgN = 0, int elastic = 0);
 void warp_pack_descs(const nrf_handle_s* h, const WarpParamOffsets& w, int64_t base, bool transposed, std::vector<PackDesc>& out);
+void mlp_pack_descs(const nrf_handle_s* h, int level, int64_t base, bool transposed, std::vector<PackDesc>& out);
 int upload_tables(nrf_handle h, float* ws, hipStream_t stream);
 void query_device(nrf_handle h);
 
 // nrf_run.hip: the launch sequences of NerfModel.apply (forward_impl) and of the gradient half of train_step (backward_impl)
 int check_launch(const char* where);
+// algorithmic flops per row (2 flop / MAC, dense layers only, unpadded): NeRF forward chain, its trunk + alpha head, SE3 forward
+double fwd_flops_row(const nrf_handle_s* h), density_flops_row(const nrf_handle_s* h), warp_fwd_flops_row(const nrf_handle_s* h);
+// the "ids or codes" a call reads of `r`, among those the model has
+int require_ids_or_codes(const nrf_handle_s* h, const nrf_rays* r, bool camera, bool appearance, bool warp);
+// narrow-model prologue: zero `image`, embed the caller's params into it through the uploaded `table`; the image, or nullptr (g_err)
+const float* embed_params(nrf_handle h, const float* params_x, const EmbedDesc* table, float* image, bool zero_by_kernel, hipStream_t stream);
+// ray_prep over r->num_rays rows for the listed levels' destinations; app_only: the appearance columns alone (alpha_ct)
+struct RayPrepLevel { int level; float *condterm, *alpha_ct; };
+RayPrepArgs ray_prep_args(const nrf_handle_s* h, const float* params, const nrf_rays* r, const float* viewdirs, float* cond,
+                          const RayPrepLevel* lv, int nlv, bool app_only);
+// the model's constants of a forward chain launch on `level`; alpha_ct: where ray_prep left the alpha head's code term
+ChainFwdArgs chain_model_args(const nrf_handle_s* h, const float* params, int level, const float* alpha_ct);
 // SE3 field on explicit points with one warp id per point (background batch of the train step, nrf_warp_points): `n` points -> out
 WarpFwdArgs warp_points_args(nrf_handle h, const float* params, const WarpParamOffsets& po, const float* wpk, const nrf_step_scalars* sc,
                              const float* points, const int32_t* ids, int n, float* out);

@@ -9,7 +9,6 @@ using namespace nrf::api;
 namespace nrf {
 namespace api {
 
-
 // Appends a leaf to the internal layout (rows x cols = what the kernels index) and to the external one
 // (xrows x xcols = what the model owns; defaults to the same).  External rows >= split sit `shift` rows lower inside.
 // xname: the leaf's path in the caller's tree when it differs from the internal one; "" = internal only (no external
@@ -188,7 +187,7 @@ void build_pack_offsets(nrf_handle h) {
 // Uneven static tile split of the NeRF chain kernels (chain_common.h tile_iter): tiles the older workgroup of a CU takes out
 // of the K = ceil(ntiles / CUs) of its CU, when the launch is exactly two workgroups per CU and K >= 4.  NRF_OLD_SHARE
 // overrides the share (0 = even split).
-int k_old_for(int ntiles, int grid, int num_cus, double dflt_share) {
+static int k_old_for(int ntiles, int grid, int num_cus, double dflt_share) {
   if (grid != 2 * num_cus) return 0;
   const int K = (ntiles + num_cus - 1) / num_cus;
   if (K < 4) return 0;
@@ -212,7 +211,7 @@ int* tile_counter_or_null(float* base, int idx) {
 constexpr int AUTO32_FWD_BELOW_TILES_PER_CU = 2;
 
 // the flags a workspace layout depends on: TRAIN, WARP_JACOBIAN, and BF16 together with TRAIN (bf16 stash instead of fp32)
-uint32_t plan_flags(uint32_t flags) {
+static uint32_t plan_flags(uint32_t flags) {
   uint32_t f = flags & (NRF_FLAG_TRAIN | NRF_FLAG_WARP_JACOBIAN);
   if ((flags & NRF_FLAG_TRAIN) && (flags & NRF_FLAG_BF16)) f |= NRF_FLAG_BF16 | (flags & NRF_FLAG_WARP_F32);
   if (!(flags & NRF_FLAG_TRAIN) && (flags & NRF_FLAG_BF16X3)) f |= NRF_FLAG_BF16X3;   // its own (tripled) weight streams
@@ -230,27 +229,56 @@ uint32_t plan_flags(uint32_t flags) {
 // chain never won (0.303 -> 0.327 ms at 512 tiles): its automatic choice stays 64.
 // An rgb branch deeper than one layer is compiled into the 64-row kernels only (nerf_chain.h Tile64::FULL): such a handle
 // never takes half tiles (nrf_set_option refuses 32 for it), whatever the launch size.
-bool chain32_for(const nrf_handle_s* h, int ntiles, bool reverse) {
+static bool chain32_for(const nrf_handle_s* h, int ntiles, bool reverse = false) {
   if (h->d.nerf_rgb_branch_depth > 1) return false;
   if (h->chain_rows_opt == 32) return true;
   if (h->chain_rows_opt == 64) return false;
   return !reverse && ntiles < AUTO32_FWD_BELOW_TILES_PER_CU * h->num_cus;
+}
+// 32-row half tiles, four workgroups per CU; else 64-row, two
+ChainTiling chain_fwd_tiling(const nrf_handle_s* h, int ntiles, bool allow32) {
+  const bool c32 = allow32 && chain32_for(h, ntiles);
+  const int grid = c32 ? tile_grid(2 * ntiles, 4, h->num_cus) : tile_grid(ntiles, knobs().grid_mul, h->num_cus);
+  return {c32, grid, k_old_for(ntiles, grid, h->num_cus, 0.0)};
 }
 
 // fp32 fragment images of the SE3 trunk (warp_chain.hip), packed from the leaves at `w` to base + h->wpk: the forward layers and,
 // with `transposed`, the reverse chain's W^T of layers 1..5
 void warp_pack_descs(const nrf_handle_s* h, const WarpParamOffsets& w, int64_t base, bool transposed, std::vector<PackDesc>& out) {
   const WarpPackOffsets& wk = h->wpk;
-  auto add = [&](int64_t src, int dst, int row0, int kvalid, int K, int tr) {
-    PackDesc q;
-    q.src_off = src; q.dst_off = base + dst; q.src_ld = WARP_W; q.src_row0 = row0; q.kvalid = kvalid; q.K = K; q.ncb = 1;
-    q.transposed = tr; q.nwaves = 4; q.nvalid = 1 << 30;
-    out.push_back(q);
+  auto add = [&](int64_t src, int dst, int row0, int kvalid, int K, int tr) {   // PackDesc: ..., ncb, transposed, nwaves, nvalid
+    out.push_back(PackDesc{src, base + dst, WARP_W, row0, kvalid, K, 1, tr, 4, 1 << 30});
   };
   add(w.trunk_k[0], wk.fwd_L[0], 0, h->Win, h->PKw, 0);
   for (int l = 1; l < WARP_DEPTH; ++l) add(w.trunk_k[l], wk.fwd_L[l], 0, WARP_W, WARP_W, 0);
   add(w.trunk_k[WARP_SKIP], wk.fwd_L4b, WARP_W, h->Win, h->PKw, 0);
   for (int l = 1; l < WARP_DEPTH && transposed; ++l) add(w.trunk_k[l], wk.bwd_LT[l], 0, WARP_W, WARP_W, 1);
+}
+
+// fp32 fragment images of level `lv`'s NeRF MLP (nerf_chain.h), packed from its leaves to base + h->pk: the forward layers and, with
+// `transposed`, the reverse chain's W^T images in between, in the order every ray plan's table has (nrf_debug_plan_digest hashes it)
+void mlp_pack_descs(const nrf_handle_s* h, int lv, int64_t base, bool transposed, std::vector<PackDesc>& out) {
+  const MlpParamOffsets& po = h->po[lv];
+  const PackOffsets& pk = h->pk;
+  auto add = [&](int64_t src, int dst, int ld, int row0, int kvalid, int K, int ncb, int tr, int nwaves = 4, int nvalid = 1 << 30) {
+    if (!tr || transposed) out.push_back(PackDesc{src, base + dst, ld, row0, kvalid, K, ncb, tr, nwaves, nvalid});
+  };
+  add(po.trunk_k[0], pk.fwd_L[0], 256, 0, h->P, h->PK, 2, 0);
+  for (int l = 1; l < TRUNK_DEPTH; ++l) add(po.trunk_k[l], pk.fwd_L[l], 256, 0, 256, 256, 2, 0);
+  add(po.trunk_k[h->d.nerf_skip_layer], pk.fwd_L4b, 256, 256, h->P, h->PK, 2, 0);
+  add(po.bn_k, pk.fwd_bn, 256, 0, 256, 256, 2, 0);
+  add(po.rgbh_k, pk.fwd_rgbh, 128, 0, 256, 256, 1, 0);
+  add(po.rgbh_k, pk.bwd_rgbhT, 128, 0, 128, 128, 2, 1);
+  for (int x = 0; x < h->d.nerf_rgb_branch_depth - 1; ++x) {   // 128 x 128, one 32-column block per wave, as is and transposed
+    add(po.rgbx_k[x], pk.fwd_rgbx + x * RGB_W * RGB_W, 128, 0, 128, 128, 1, 0);
+    add(po.rgbx_k[x], pk.bwd_rgbxT + x * RGB_W * RGB_W, 128, 0, 128, 128, 1, 1);
+  }
+  add(po.bn_k, pk.bwd_bnT, 256, 0, 256, 256, 2, 1);
+  for (int l = 1; l < TRUNK_DEPTH; ++l) add(po.trunk_k[l], pk.bwd_LT[l], 256, 0, 256, 256, 2, 1);
+  if (h->warp) {   // d posenc streams: B[k][n] = W[row0 + n][k], n < P, one 64-column group
+    add(po.trunk_k[0], pk.bwd_L0T, 256, 0, 256, 256, 2, 1, 1, h->P);
+    add(po.trunk_k[h->d.nerf_skip_layer], pk.bwd_L4bT, 256, 256, 256, 256, 2, 1, 1, h->P);
+  }
 }
 
 namespace {
@@ -438,7 +466,7 @@ std::vector<Table> tables_of(nrf_handle h) {
 }
 
 // build_plan's stages and what they hand on
-struct Planner {
+struct Planner : Carve {
   nrf_handle h;
   WsPlan& p;
   const nrf_model_desc& d;
@@ -456,14 +484,12 @@ struct Planner {
   std::vector<BSpec> bspecs;            // bf16 wgrad groups
   std::vector<int> nsplit, bnsplit;     // segments of each group
   std::vector<ReduceDesc> by_pass[4];   // reduce descriptors by pass (ReduceDesc::accumulate)
-  size_t o = 0;                         // floats laid out
 
   Planner(nrf_handle h_, uint32_t flags)
       : h(h_), p(h_->plan), d(h_->d), train(flags & NRF_FLAG_TRAIN), bft(train && (flags & NRF_FLAG_BF16)),
         x3(!train && (flags & NRF_FLAG_BF16X3)), jac((flags & NRF_FLAG_WARP_JACOBIAN) && h_->warp),
         bfw(bft && h_->warp && !(flags & NRF_FLAG_WARP_F32)), wstash((train && !bfw) || jac), rg(train && (flags & NRF_FLAG_RAY_GRADS)),
         frozen(rg && (flags & NRF_FLAG_FROZEN)), G(h_->num_cus) {}
-  size_t take(size_t n) { size_t r = o; o = align_up(o + n, ALIGN_F); return r; }
   void add_reduce(const ReduceDesc& r) { by_pass[r.accumulate].push_back(r); }
   // fp32 groups: leaf [kvalid][cols] <- X^T dY; the narrow heads: leaf [kvalid][vec] <- X^T v
   void gemm(int lv, int accu, Operand x, int kvalid, Operand dy, int64_t dst, int cols) {
@@ -908,40 +934,18 @@ void Planner::ray_grad_buffers() {
 //      NeRF MLPs (bfpack), so their fp32 fragment images are not rebuilt every step ----
 void Planner::pack_descs() {
   for (int lv = 0; lv < (bft ? 0 : h->nlevels); ++lv) {
-    const MlpParamOffsets& po = h->po[lv];
+    const size_t first = p.pack.size();
     const int64_t base = (int64_t)p.L[lv].wpk;
+    mlp_pack_descs(h, lv, base, true, p.pack);
+    if (!rg || h->warp) continue;
     // ray gradients without a warp field: the reverse chain reads its transposed images (and the two d-posenc ones) from rg_wpkT,
-    // taken behind everything else: those descriptors are built relative to it here and moved onto it by ray_grad_buffers
-    const bool rgT = rg && !h->warp;
-    if (rgT) { p.rg_L0T = h->pk.total; p.rg_L4bT = p.rg_L0T + 256 * 64; }   // behind the level's own images and their prefetch slack
-    const PackOffsets& pk = h->pk;
-    auto add = [&](int64_t src, int dst, int ld, int row0, int kvalid, int K, int ncb, int tr, int nwaves = 4,
-                   int nvalid = 1 << 30) {
-      PackDesc q;
-      q.src_off = src; q.dst_off = (tr && rgT ? 0 : base) + dst; q.src_ld = ld; q.src_row0 = row0; q.kvalid = kvalid; q.K = K; q.ncb = ncb;
-      q.transposed = tr; q.nwaves = nwaves; q.nvalid = nvalid;
-      if (tr && rgT) rg_packT[lv].push_back(p.pack.size());
-      p.pack.push_back(q);
-    };
-    add(po.trunk_k[0], pk.fwd_L[0], 256, 0, h->P, h->PK, 2, 0);
-    for (int l = 1; l < TRUNK_DEPTH; ++l) add(po.trunk_k[l], pk.fwd_L[l], 256, 0, 256, 256, 2, 0);
-    add(po.trunk_k[d.nerf_skip_layer], pk.fwd_L4b, 256, 256, h->P, h->PK, 2, 0);
-    add(po.bn_k, pk.fwd_bn, 256, 0, 256, 256, 2, 0);
-    add(po.rgbh_k, pk.fwd_rgbh, 128, 0, 256, 256, 1, 0);
-    add(po.rgbh_k, pk.bwd_rgbhT, 128, 0, 128, 128, 2, 1);
-    for (int x = 0; x < d.nerf_rgb_branch_depth - 1; ++x) {   // 128 x 128, one 32-column block per wave, as is and transposed
-      add(po.rgbx_k[x], pk.fwd_rgbx + x * RGB_W * RGB_W, 128, 0, 128, 128, 1, 0);
-      add(po.rgbx_k[x], pk.bwd_rgbxT + x * RGB_W * RGB_W, 128, 0, 128, 128, 1, 1);
-    }
-    add(po.bn_k, pk.bwd_bnT, 256, 0, 256, 256, 2, 1);
-    for (int l = 1; l < TRUNK_DEPTH; ++l) add(po.trunk_k[l], pk.bwd_LT[l], 256, 0, 256, 256, 2, 1);
-    if (h->warp) {   // d posenc streams: B[k][n] = W[row0 + n][k], n < P, one 64-column group
-      add(po.trunk_k[0], pk.bwd_L0T, 256, 0, 256, 256, 2, 1, 1, h->P);
-      add(po.trunk_k[d.nerf_skip_layer], pk.bwd_L4bT, 256, 256, 256, 256, 2, 1, 1, h->P);
-    } else if (rgT) {
-      add(po.trunk_k[0], p.rg_L0T, 256, 0, 256, 256, 2, 1, 1, h->P);
-      add(po.trunk_k[d.nerf_skip_layer], p.rg_L4bT, 256, 256, 256, 256, 2, 1, 1, h->P);
-    }
+    // taken behind everything else: those descriptors are made relative to it here and moved onto it by ray_grad_buffers
+    p.rg_L0T = h->pk.total; p.rg_L4bT = p.rg_L0T + 256 * 64;   // behind the level's own images and their prefetch slack
+    const MlpParamOffsets& po = h->po[lv];
+    p.pack.push_back(PackDesc{po.trunk_k[0], base + p.rg_L0T, 256, 0, 256, 256, 2, 1, 1, h->P});
+    p.pack.push_back(PackDesc{po.trunk_k[d.nerf_skip_layer], base + p.rg_L4bT, 256, 256, 256, 256, 2, 1, 1, h->P});
+    for (size_t i = first; i < p.pack.size(); ++i)
+      if (p.pack[i].transposed) { p.pack[i].dst_off -= base; rg_packT[lv].push_back(i); }
   }
   // fp32 fragment images of the SE3 trunk (a bf16-trunk training plan reads only its bf16 streams)
   if (h->warp && !bfw) warp_pack_descs(h, h->wpo, (int64_t)p.warp_wpk, !frozen, p.pack);   // frozen: no SE3 reverse chain, no W^T images
@@ -1147,7 +1151,6 @@ void query_device(nrf_handle h) {
     h->num_cus = cus;
   h->cu_queried = true;
 }
-
 
 }  // namespace api
 }  // namespace nrf

@@ -1,6 +1,7 @@
 // Launch sequences of the C-ABI layer: forward_impl stands in for NerfModel.apply (models.py:289-375), backward_impl for the gradient
 // half of training.train_step (training.py:168-265) incl. the regularisers; both run on the plan nrf_plan.hip built, as a list of
-// stages (Forward / Backward below, the pattern of nrf_plan.hip's Planner) over one call's context (Run).  See nrf_handle.h.
+// stages (Forward / Backward below, the pattern of nrf_plan.hip's Planner) over one call's context (Run).  The argument builders in
+// front of them also serve the stand-alone field entries (nrf_field.hip).  See nrf_handle.h.
 #include "nrf_handle.h"
 
 using namespace nrf;
@@ -31,15 +32,74 @@ WarpFwdArgs warp_points_args(nrf_handle h, const float* params, const WarpParamO
   return a;
 }
 
+int require_ids_or_codes(const nrf_handle_s* h, const nrf_rays* r, bool camera, bool appearance, bool warp) {
+  if (camera && h->d.use_camera_metadata && !r->camera_ids && !r->camera_codes) return fail(NRF_E_NULL, "camera_ids (or camera_codes) required (use_camera_metadata)");
+  if (appearance && h->app_in_cond && !r->appearance_ids && !r->appearance_codes) return fail(NRF_E_NULL, "appearance_ids (or appearance_codes) required");
+  if (warp && !r->warp_ids && !r->warp_codes) return fail(NRF_E_NULL, "warp_ids (or warp_codes) required (use_warp)");
+  return NRF_OK;
+}
+
+const float* embed_params(nrf_handle h, const float* params_x, const EmbedDesc* table, float* image, bool zero_by_kernel, hipStream_t stream) {
+  if (zero_by_kernel) {
+    // the frozen step is made to be captured and replayed many times (one alignment step per replay): its image is cleared by a
+    // kernel, not by a memset node.  Observed on an MI355X: from the SECOND replay of a captured step on, the image behind the
+    // replayed memset node is no longer the eager one and the step returns NaN once the host has allocated in between, on the
+    // non-frozen plans as well; with a full-width model (no padded image, no memset) every replay is exact.  The other callers
+    // keep hipMemsetAsync as they were.
+    ZeroArgs z;
+    memset(&z, 0, sizeof(z));
+    z.add(image, h->nparams);
+    launch_zero_ranges(z, stream);
+  } else if (hipMemsetAsync(image, 0, (size_t)h->nparams * sizeof(float), stream) != hipSuccess) {
+    fail(NRF_E_HIP, "zero padded params");
+    return nullptr;
+  }
+  launch_embed(table, (int)h->emb.size(), params_x, image, true, stream);
+  return image;
+}
+
+RayPrepArgs ray_prep_args(const nrf_handle_s* h, const float* params, const nrf_rays* r, const float* viewdirs, float* cond,
+                          const RayPrepLevel* lv, int nlv, bool app_only) {
+  RayPrepArgs ra;
+  memset(&ra, 0, sizeof(ra));
+  ra.params = params; ra.cond = cond; ra.viewdirs = viewdirs; ra.B = r->num_rays;
+  ra.app_ids = r->appearance_codes ? nullptr : r->appearance_ids; ra.app_codes = r->appearance_codes;
+  ra.app_feat = h->A; ra.app_off = h->app_off; ra.R = h->A;
+  if (!app_only) {
+    ra.cam_ids = r->camera_codes ? nullptr : r->camera_ids; ra.cam_codes = r->camera_codes;
+    ra.Fv = h->d.num_nerf_viewdir_freqs; ra.use_viewdirs = h->d.use_viewdirs;
+    ra.cam_feat = h->d.use_camera_metadata ? h->d.num_camera_features : 0; ra.cam_off = h->cam_off; ra.R = h->R;
+  }
+  for (int i = 0; i < nlv; ++i) {
+    const MlpParamOffsets& po = h->po[lv[i].level];
+    ra.rgbh_k[i] = po.rgbh_k; ra.rgbh_b[i] = po.rgbh_b; ra.alpha_k[i] = po.alpha_k;
+    ra.condterm[i] = lv[i].condterm; ra.alpha_ct[i] = h->A > 0 ? lv[i].alpha_ct : nullptr;
+  }
+  return ra;
+}
+
+ChainFwdArgs chain_model_args(const nrf_handle_s* h, const float* params, int level, const float* alpha_ct) {
+  ChainFwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.params = params; a.po = h->po[level]; a.pk = h->pk; a.alpha_ct = h->A > 0 ? alpha_ct : nullptr; a.nx = h->d.nerf_rgb_branch_depth - 1;
+  a.F = h->d.num_nerf_point_freqs; a.P = h->P; a.PK = h->PK; a.sigma_act = h->d.sigma_activation; a.skip = h->d.nerf_skip_layer;
+  return a;
+}
+
+// algorithmic flops per MLP row (2 flop / MAC, dense layers only, unpadded; SURVEY.md 8d)
+static double rgbx_flops_row(const nrf_handle_s* h) { return 2.0 * 16384.0 * (h->d.nerf_rgb_branch_depth - 1); }   // rgb branch layers 1..
+static double trunk_macs_row(const nrf_handle_s* h) { return h->P * 256 + 6 * 65536.0 + (256 + h->P) * 256 + 256; }   // 8 layers + alpha head
+double density_flops_row(const nrf_handle_s* h) { return 2.0 * (trunk_macs_row(h) + (h->A > 0 ? 65536.0 : 0.0)); }   // (+ bottleneck)
+double fwd_flops_row(const nrf_handle_s* h) { return 2.0 * (trunk_macs_row(h) + 65536.0 + (256.0 + h->R) * 128 + 128 * 3) + rgbx_flops_row(h); }
+// SE3 field per row (SURVEY.md 8d): trunk + heads
+double warp_fwd_flops_row(const nrf_handle_s* h) { return 2.0 * (h->Win * 128 + 3 * 16384.0 + (128 + h->Win) * 128 + 16384.0 + 128 * 6); }
+
 namespace {
 
 int validate_rays(nrf_handle h, const nrf_rays* rays) {
   if (!rays || !rays->origins || !rays->directions) return fail(NRF_E_NULL, "rays / origins / directions is null");
   if (rays->num_rays <= 0) return fail(NRF_E_SHAPE, "num_rays must be positive");
-  if (h->d.use_camera_metadata && !rays->camera_ids && !rays->camera_codes)
-    return fail(NRF_E_NULL, "camera_ids (or camera_codes) required (use_camera_metadata)");
-  if (h->app_in_cond && !rays->appearance_ids && !rays->appearance_codes) return fail(NRF_E_NULL, "appearance_ids (or appearance_codes) required");
-  if (h->warp && !h->time_enc && !rays->warp_ids && !rays->warp_codes) return fail(NRF_E_NULL, "warp_ids (or warp_codes) required (use_warp)");
+  CK(require_ids_or_codes(h, rays, true, true, h->warp && !h->time_enc));
   if (h->warp && h->time_enc && !rays->time && !rays->warp_codes) return fail(NRF_E_NULL, "time (or warp_codes) required (warp_metadata_encoder_type 'time')");
   return NRF_OK;
 }
@@ -50,20 +110,9 @@ int copy_out(float* dst, const float* src, size_t n, hipStream_t stream) {
   return e == hipSuccess ? NRF_OK : fail_hip(e, "copy output");
 }
 
-// algorithmic flops per MLP row (2 flop / MAC, dense layers only, unpadded; SURVEY.md 8d)
-double rgbx_flops_row(nrf_handle h) { return 2.0 * 16384.0 * (h->d.nerf_rgb_branch_depth - 1); }   // rgb branch layers 1..
-double fwd_flops_row(nrf_handle h) {
-  const double P = h->P, R = h->R;
-  return 2.0 * (P * 256 + 6 * 65536.0 + (256 + P) * 256 + 65536.0 + 256 + (256 + R) * 128 + 128 * 3) + rgbx_flops_row(h);
-}
 double dgrad_flops_row(nrf_handle h, bool warp_on) {
   const double base = 2.0 * (128 * 3 + 256 * 128 + 65536.0 + 256 + 7 * 65536.0) + rgbx_flops_row(h);
   return warp_on ? base + 2.0 * (2.0 * 256 * h->P) : base;   // + d posenc through layer 0 and the skip rows
-}
-// SE3 field per row (SURVEY.md 8d): trunk + heads
-double warp_fwd_flops_row(nrf_handle h) {
-  const double Wi = h->Win;
-  return 2.0 * (Wi * 128 + 3 * 16384.0 + (128 + Wi) * 128 + 16384.0 + 128 * 6);
 }
 double warp_dgrad_flops_row(nrf_handle h) { return 2.0 * (128 * 6 + 5 * 16384.0 + 2.0 * h->G * 128); }
 double warp_fwd_flops_row_or0(nrf_handle h) { return h->warp ? warp_fwd_flops_row(h) : 0.0; }
@@ -169,23 +218,8 @@ struct Forward : Run {
     if (tile_counter_or_null(ws + p.counters, 0) &&   // NRF_DYNAMIC_TILES experiment only
         hipMemsetAsync(ws + p.counters, 0, 64 * sizeof(int), stream) != hipSuccess) return fail(NRF_E_HIP, "zero tile counters");
     params = params_x;
-    if (h->embed) {   // narrower model: run on its zero-padded image
-      if (m.frozen) {
-        // the frozen step is made to be captured and replayed many times (one alignment step per replay): its image is cleared by a
-        // kernel, not by a memset node.  Observed on an MI355X: from the SECOND replay of a captured step on, the image behind the
-        // replayed memset node is no longer the eager one and the step returns NaN once the host has allocated in between, on the
-        // non-frozen plans as well; with a full-width model (no padded image, no memset) every replay is exact.  The other plans
-        // keep hipMemsetAsync as they were.
-        ZeroArgs z;
-        memset(&z, 0, sizeof(z));
-        z.add(ws + p.iparams, h->nparams);
-        launch_zero_ranges(z, stream);
-      } else if (hipMemsetAsync(ws + p.iparams, 0, (size_t)h->nparams * sizeof(float), stream) != hipSuccess) {
-        return fail(NRF_E_HIP, "zero padded params");
-      }
-      launch_embed(table<EmbedDesc>(p.emb_off_b), (int)h->emb.size(), params_x, ws + p.iparams, true, stream);
-      params = ws + p.iparams;
-    }
+    // narrower model: run on its zero-padded image (the table went up with upload_tables)
+    if (h->embed && !(params = embed_params(h, params_x, table<EmbedDesc>(p.emb_off_b), ws + p.iparams, m.frozen, stream))) return NRF_E_HIP;
     pf.begin("pack_prep_sample", 0, stream);
     if (!p.pack.empty()) launch_pack(table<PackDesc>(p.pack_off_b), (int)p.pack.size(), params, ws, stream);
     if (m.bf16 || m.x3) launch_bf16_pack(reinterpret_cast<const RcPackDesc*>(ws + p.bf_desc), (int)p.bfpack.size(), params, ws, stream);
@@ -202,19 +236,10 @@ struct Forward : Run {
   }
 
   void ray_prep() const {
-    RayPrepArgs ra;
-    memset(&ra, 0, sizeof(ra));
-    ra.params = params; ra.cond = ws + p.cond; ra.viewdirs = rays->viewdirs ? rays->viewdirs : rays->directions;   // models.py:326-329
-    ra.app_ids = rays->appearance_codes ? nullptr : rays->appearance_ids; ra.app_codes = rays->appearance_codes;
-    ra.cam_ids = rays->camera_codes ? nullptr : rays->camera_ids; ra.cam_codes = rays->camera_codes;
-    ra.B = B; ra.Fv = d.num_nerf_viewdir_freqs; ra.use_viewdirs = d.use_viewdirs;
-    ra.app_feat = h->app_in_cond ? d.num_appearance_features : 0; ra.app_off = h->app_off;
-    ra.cam_feat = d.use_camera_metadata ? d.num_camera_features : 0; ra.cam_off = h->cam_off; ra.R = h->R;
-    for (int lv = 0; lv < h->nlevels; ++lv) {
-      ra.rgbh_k[lv] = h->po[lv].rgbh_k; ra.rgbh_b[lv] = h->po[lv].rgbh_b; ra.alpha_k[lv] = h->po[lv].alpha_k;
-      ra.condterm[lv] = ws + p.L[lv].condterm; ra.alpha_ct[lv] = h->A > 0 ? ws + p.L[lv].alpha_ct : nullptr;
-    }
-    launch_ray_prep(ra, stream);
+    RayPrepLevel lv[2];
+    for (int i = 0; i < h->nlevels; ++i) lv[i] = {i, ws + p.L[i].condterm, ws + p.L[i].alpha_ct};
+    const float* viewdirs = rays->viewdirs ? rays->viewdirs : rays->directions;   // models.py:326-329
+    launch_ray_prep(ray_prep_args(h, params, rays, viewdirs, ws + p.cond, lv, h->nlevels, false), stream);
   }
 
   void sample_fine() {
@@ -300,16 +325,12 @@ struct Forward : Run {
 
   ChainFwdArgs chain_fwd_args(int lv) const {
     const LevelWs& L = p.L[lv];
-    ChainFwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.params = params; a.po = h->po[lv]; a.wpk = ws + L.wpk; a.pk = h->pk;
-    a.condterm = ws + L.condterm; a.zvals = ws + L.z; a.origins = rays->origins; a.directions = rays->directions;
+    ChainFwdArgs a = chain_model_args(h, params, lv, ws + L.alpha_ct);
+    a.wpk = ws + L.wpk; a.condterm = ws + L.condterm; a.zvals = ws + L.z; a.origins = rays->origins; a.directions = rays->directions;
     a.points = m.warp_on ? ws + L.wpoints : nullptr; a.out4 = f4(L.out4);
     a.S = p.S[lv]; a.B = B; a.rows = p.rows[lv]; a.ntiles = p.ntiles[lv];
-    a.F = d.num_nerf_point_freqs; a.P = h->P; a.PK = h->PK; a.sigma_act = d.sigma_activation; a.skip = d.nerf_skip_layer;
     a.tile_counter = tile_counter_or_null(ws + p.counters, CT_MLP_FWD + lv);
     a.timeline = knobs().timeline ? reinterpret_cast<unsigned long long*>(ws + p.timeline + lv * TIMELINE_LEVEL_F) : nullptr;
-    a.alpha_ct = h->A > 0 ? ws + L.alpha_ct : nullptr;
     if (d.noise_std > 0.f && d.use_stratified_sampling) {   // model_utils.noise_regularize (model_utils.py:266-282)
       a.noise_std = d.noise_std;
       a.noise = rnd ? (lv == 0 ? rnd->noise_coarse : rnd->noise_fine) : nullptr;
@@ -324,22 +345,20 @@ struct Forward : Run {
       a.st_pe = ws + L.st_pe; a.st_h = ws + L.st_h; a.st_bn = ws + L.st_bn; a.st_rgbh = ws + L.st_rgbh;
       a.bits_trunk = u32(L.bits_trunk); a.bits_rgbh = u32(L.bits_rgbh); a.st_rgbx = ws + L.st_rgbx; a.bits_rgbx = u32(L.bits_rgbx);
     }
-    a.nx = d.nerf_rgb_branch_depth - 1;
     return a;
   }
 
   void mlp(int lv) {
     ChainFwdArgs a = chain_fwd_args(lv);
-    const bool c32 = !m.bf16 && !m.x3 && chain32_for(h, p.ntiles[lv]);   // 32-row half tiles, four workgroups per CU; else 64-row, two
-    const int grid = c32 ? tile_grid(2 * p.ntiles[lv], 4, h->num_cus) : tile_grid(p.ntiles[lv], knobs().grid_mul, h->num_cus);
-    a.k_old = k_old_for(p.ntiles[lv], grid, h->num_cus, 0.0);
+    const ChainTiling t = chain_fwd_tiling(h, p.ntiles[lv], !m.bf16 && !m.x3);
+    a.k_old = t.k_old;
     pf.begin(lv == 0 ? "mlp_fwd_coarse" : "mlp_fwd_fine", fwd_flops_row(h) * p.rows[lv], stream);
     if (m.bf16 || m.x3) a.wpk = ws + p.L[lv].bf_wpk;
     if (m.bf16) launch_chain_fwd_bf16(a, h->num_cus, stream);   // one workgroup per CU (90 KiB of weight staging), 256 samples per workgroup iteration
     else if (m.x3) launch_chain_fwd_x3(a, h->num_cus, stream);   // one four-wave workgroup per CU (150 KiB ring), 128 samples per workgroup iteration
-    else if (m.frozen) launch_chain_fwd_frozen(a, c32, grid, stream);
-    else if (c32) launch_chain_fwd32(a, m.train, grid, stream);
-    else launch_chain_fwd(a, m.train, grid, stream);
+    else if (m.frozen) launch_chain_fwd_frozen(a, t.c32, t.grid, stream);
+    else if (t.c32) launch_chain_fwd32(a, m.train, t.grid, stream);
+    else launch_chain_fwd(a, m.train, t.grid, stream);
     pf.end(stream);
   }
 

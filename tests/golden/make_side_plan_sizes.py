@@ -1,0 +1,61 @@
+#!/usr/bin/env python
+"""tests/golden/side_plan_sizes.json: the workspace sizes of the stand-alone field entries (csrc/nrf_field.hip), which plan beside
+the ray plan and so have no digest -- nrf_query_workspace_bytes of every model of make_plan_digests.py at the (groups, points per
+group) and flags below, nrf_warp_points_workspace_bytes of every warp model at the point counts below --, or the error code where
+an entry refuses.  tests/test_field_query_host.py compares a fresh build against it.  Host only; neither size depends on the CU
+count.
+
+  python tests/golden/make_side_plan_sizes.py
+"""
+import ctypes as C
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+
+from make_plan_digests import MODELS, desc  # noqa: E402
+from nerfies_amd import lib as L  # noqa: E402
+
+OUT = os.path.join(HERE, 'side_plan_sizes.json')
+QUERY_SHAPES = ((1, 1), (3, 37), (70, 1), (2, 64), (1, 65536), (256, 256))   # (groups, points per group)
+QUERY_FLAGS = {'0': 0, 'NO_WARP': L.NRF_FLAG_NO_WARP}
+WARP_POINTS = (1, 63, 64, 65, 4097)
+
+
+def sizes(lib):
+  """{case: bytes, or the error code (negative) of a refusal} over every model."""
+  out = {}
+  for model, kw in MODELS.items():
+    h = C.c_void_p()
+    d = desc(**kw)
+    L.check(lib.nrf_create(C.byref(d), C.byref(h)), lib)
+    try:
+      n = C.c_size_t(0)
+      for G, S in QUERY_SHAPES:
+        for fname, flags in QUERY_FLAGS.items():
+          rc = lib.nrf_query_workspace_bytes(h, G, S, flags, C.byref(n))
+          out[f'{model}/query/{fname}/groups={G}/points={S}'] = n.value if rc == 0 else rc
+      if kw.get('use_warp', 0):
+        for num in WARP_POINTS:
+          rc = lib.nrf_warp_points_workspace_bytes(h, num, C.byref(n))
+          out[f'{model}/warp_points/n={num}'] = n.value if rc == 0 else rc
+    finally:
+      lib.nrf_destroy(h)
+  return out
+
+
+def main():
+  from nerfies_amd import build
+  build.build()
+  rec = sizes(L.load_library())
+  with open(OUT, 'w') as fp:
+    json.dump({'sizes': rec}, fp, indent=0, sort_keys=True)
+    fp.write('\n')
+  print('wrote', len(rec), 'sizes')
+
+
+if __name__ == '__main__':
+  main()

@@ -1,6 +1,7 @@
 """Field queries on the host (no GPU): the header's two structs against their ctypes mirrors, NRF_HAS_FIELD_QUERY next to an unchanged
 NRF_VERSION, every refusal nrf_query_points / nrf_query_grid decide before any HIP call (one assertion per rule, the offending name
-in nrf_last_error), the workspace size, the ray plans' digests behind a query plan, and the chunking of evaluation.density_grid."""
+in nrf_last_error), the workspace size (and the recorded sizes of every side plan), the ray plans' digests behind a query plan, and the chunking of
+evaluation.density_grid."""
 import ctypes as C
 import importlib.util
 import json
@@ -243,6 +244,22 @@ def test_ray_plans_keep_their_digests_behind_a_query_plan(lib, handles):
       c = _Call(lib, h)
       assert c.points(nbytes=0) == NRF_E_WORKSPACE
       assert lib.nrf_debug_plan_digest(h, C.byref(dg)) == 0 and '%016x' % dg.value == want['digest'], (model, rays)
+
+
+def test_side_plan_sizes_match_the_record(lib):
+  """tests/golden/side_plan_sizes.json: the workspace of every stand-alone field entry, byte for byte (a refusal: its error code)."""
+  spec = importlib.util.spec_from_file_location('make_side_plan_sizes', os.path.join(GOLDEN, 'make_side_plan_sizes.py'))
+  mod = importlib.util.module_from_spec(spec)
+  spec.loader.exec_module(mod)
+  with open(os.path.join(GOLDEN, 'side_plan_sizes.json')) as fp:
+    want = json.load(fp)['sizes']
+  got = mod.sizes(lib)
+  assert sorted(got) == sorted(want)
+  wrong = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+  assert not wrong, wrong
+  warp_models = [m for m, kw in mod.MODELS.items() if kw.get('use_warp', 0)]
+  assert len(want) == len(mod.MODELS) * len(mod.QUERY_SHAPES) * len(mod.QUERY_FLAGS) + len(warp_models) * len(mod.WARP_POINTS)
+  assert all(v > 0 for v in want.values())                    # no entry refuses a listed case
 
 
 class _RecordingLib:

@@ -1,6 +1,7 @@
 """Field queries on the GPU (nrf_query_points / nrf_query_grid): parity with the float64 oracle's own pieces at the smallest shapes
 that can go wrong, bit-identity with what the renderer saw, density-only against the full query, the grid, a query next to a stashed
-training call, and the Python surface down to scripts/export_density.py.
+training call, nrf_warp_points against the query's warped points and on a stashed call's workspace, and the Python surface down to
+scripts/export_density.py.
 
 Oracle parity, per output and per case: max error over the points / the oracle output's max-abs, against 4 x the same statistic of
 the oracle evaluated in float32 on the same inputs, computed here on the CPU (the rule helpers.D_RAW_TOL documents).  The one-point
@@ -271,6 +272,63 @@ def test_a_query_leaves_a_stashed_training_call_alone():
   # float atomics in the per-ray sums: two plain runs need not agree bitwise either; the query must move nothing beyond that
   tol = 1e-6 * float(g0.abs().max())
   print(f'[field query / stash] max |g_query - g_plain| {float((g1 - g0).abs().max()):.3e}, plain rerun {float((g2 - g0).abs().max()):.3e}, tol {tol:.3e}')
+  assert float((g1 - g0).abs().max()) <= tol
+
+
+@pytest.mark.parametrize('trunk', [{}, dict(warp_trunk_depth=4, warp_trunk_width=64)], ids=['se3', 'warp_trunk4x64'])
+def test_warp_points_equal_the_querys_warped_points(trunk):
+  """nrf_warp_points and a query of one point per group run the same SE3 kernel on explicit points with one id per point, and a
+  row's value does not depend on the grid: bit for bit.  N: one row, one row past a tile, past one tile per CU pair.  The 4 x 64
+  trunk runs both entries on the padded parameter image."""
+  spec, p, model, fp = _model('g_se3', **trunk)
+  for N in (1, 65, 4097):
+    g = torch.Generator().manual_seed(31 + N)
+    pts = ((torch.rand(N, 3, generator=g) * 2 - 1) * BOX).float().to(H.DEV)
+    ids = torch.randint(0, spec.num_warp_embeddings, (N,), generator=g).to(H.DEV)
+    direct = model.warp_points(fp, pts, ids, {'alpha': ALPHA})
+    query = model.query_points(fp, pts[:, None, :], metadata={'warp': ids[:, None]}, warp_extra={'alpha': ALPHA}, outputs=('warped_points',))
+    assert tuple(direct.shape) == (N, 3) and tuple(query['warped_points'].shape) == (N, 1, 3)
+    assert torch.isfinite(direct).all() and not torch.equal(direct, pts)
+    assert torch.equal(direct, query['warped_points'][:, 0]), (trunk, N)
+
+
+def test_warp_points_on_a_stashed_workspace_forgets_the_stash():
+  """nrf_warp_points writes its tables and images at the start of the memory it is handed.  Handed the workspace of a stashed
+  nrf_forward(NRF_FLAG_TRAIN) it forgets that stash (as a query does): nrf_backward is refused instead of differentiating what was
+  written over, and the next forward uploads its tables again."""
+  from nerfies_amd import lib as L, models as M
+  spec, p, model, fp = _model('g_se3', num_coarse_samples=16, num_fine_samples=16)
+  B, n = 5, 3
+  gb = H.gpu_batch(O.synthetic_batch(B, seed=9, dtype=torch.float32))
+  gen = torch.Generator().manual_seed(6)
+  d_c, d_f = torch.randn(B, 3, generator=gen).to(H.DEV), torch.randn(B, 3, generator=gen).to(H.DEV)
+  pts = ((torch.rand(n, 3, generator=gen) * 2 - 1) * BOX).float().to(H.DEV)
+  ids = torch.tensor([2, 0, 1], dtype=torch.int32, device=H.DEV)
+
+  def forward():
+    return model.apply(fp, gb, {'alpha': ALPHA}, train=True)['fine']['rgb'].clone()
+
+  rgb0 = forward()
+  g0 = model.backward(fp, gb, d_c, d_f).clone()
+  assert float(g0.abs().max()) > 0
+  forward()
+  ws = model.stash.ws
+  need = C.c_size_t(0)
+  L.check(model.lib.nrf_warp_points_workspace_bytes(model.handle, n, C.byref(need)), model.lib)
+  assert need.value < ws.numel() * 4                         # every call below is in bounds
+  warped = torch.empty(n, 3, device=H.DEV)
+  scal = M._scalars({'alpha': ALPHA})
+  L.check(model.lib.nrf_warp_points(model.handle, M._ptr(fp.flat), M._ptr(pts), M._ptr(ids), n, C.byref(scal), M._ptr(warped), M._ptr(ws),
+                                    ws.numel() * 4, M._stream(H.DEV)), model.lib)
+  assert torch.equal(warped, model.warp_points(fp, pts, ids, {'alpha': ALPHA}))   # the same call on memory of its own
+  with pytest.raises(L.NrfError, match='error -6'):          # NRF_E_STATE
+    model.backward(fp, gb, d_c, d_f)
+  rgb1 = forward()
+  g1 = model.backward(fp, gb, d_c, d_f)
+  assert torch.equal(rgb1, rgb0)
+  # float atomics in the per-ray sums: two plain runs need not agree bitwise (test_a_query_leaves_a_stashed_training_call_alone)
+  tol = 1e-6 * float(g0.abs().max())
+  print(f'[warp points / stash] max |g_after - g_plain| {float((g1 - g0).abs().max()):.3e}, tol {tol:.3e}')
   assert float((g1 - g0).abs().max()) <= tol
 
 
