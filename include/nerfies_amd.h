@@ -521,6 +521,48 @@ int nrf_query_grid(nrf_handle h, const float* params, const nrf_rays* group, con
                    int32_t level, const nrf_step_scalars* scalars, uint32_t flags, const nrf_field_out* out, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* ---- Gradient queries: the density's slope at arbitrary points (float32 mode) ----
+ * d sigma / d x of the field queried above, with respect to the CALLER's point -- through the warp field when it is on -- and the
+ * surface normal it gives: what shading a density export, orienting an iso-surface or an Eikonal term needs, in one call where
+ * central differences take six density queries.  Forward: the density chain keeping the posenc stash, the trunk's ReLU sign words
+ * and sigma'(raw) (about 0.5 KB per row; about 1 KB with the warp field's stash and Jacobian).  Reverse: the data-gradient chain
+ * started at the density -- no rgb branch, no per-group sum, no atomic: a row's result does not depend on the launch it ran in.
+ * Warp on: the SE3 field's primal and forward-mode tangent passes give J = d x' / d x per row and grad_x = J^T grad_x'.
+ * Entries of their own with a plan of their own: nrf_query_points / nrf_query_grid, nrf_field_out and what
+ * nrf_query_workspace_bytes returns are as they were.  Announced by NRF_HAS_FIELD_GRADIENT (NRF_VERSION is unchanged). */
+#define NRF_HAS_FIELD_GRADIENT 1
+#define NRF_QUERY_GRAD_MAX_POINTS (1 << 20) /* points of one call (the stash is ~1 KB per row; callers chunk); more is NRF_E_SHAPE */
+
+/* Device outputs of a gradient query, N rows each; any may be NULL. */
+typedef struct nrf_field_grad_out {
+  float* sigma;         /* (N,)   activated density: the same bits as nrf_query_points' density-only sigma */
+  float* grad_sigma;    /* (N,3)  d sigma / d x at the caller's point (through the warp when it is on) */
+  float* normals;       /* (N,3)  -g / |g| of g = grad_sigma, formed in float32 as
+                         *          s = fmaf(g.z, g.z, fmaf(g.y, g.y, g.x * g.x)), inv = 1 / sqrtf(s), n_c = -(g_c * inv)
+                         *        (one rounding per step, division and square root correctly rounded); exactly 0 where s is 0 or
+                         *        not finite */
+  float* warped_points; /* (N,3)  as nrf_field_out; needs the warp field on, else NRF_E_UNSUPPORTED */
+} nrf_field_grad_out;
+
+/* Workspace of a gradient query of num_groups x points_per_group points; one answer whatever the outputs asked for and for both
+ * values of flags (0 or NRF_FLAG_NO_WARP).  Needs no GPU. */
+int nrf_query_grad_workspace_bytes(nrf_handle h, int32_t num_groups, int32_t points_per_group, uint32_t flags, size_t* bytes);
+
+/* nrf_query_points' arguments and rules (groups, level, flags: 0 or NRF_FLAG_NO_WARP and every other bit refused by its name, the
+ * time encoder refused with the warp on, warped_points refused without it), at most NRF_QUERY_GRAD_MAX_POINTS points.  Density
+ * only: no view direction or camera code is read; a use_alpha_condition model needs its appearance ids (or codes).  Every refusal
+ * is decided before any HIP call.  Asynchronous on `stream`, no allocation, capturable into a hipGraph; handed the workspace of a
+ * ray plan it makes the handle forget that plan's upload and stash, as the queries above. */
+int nrf_query_points_grad(nrf_handle h, const float* params, const nrf_rays* groups, const float* points, int32_t points_per_group,
+                          int32_t level, const nrf_step_scalars* scalars, uint32_t flags, const nrf_field_grad_out* out, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/* The same at points [first, first + count) of `grid` (nrf_query_grid's rules; group->num_rays must be 1).  Workspace:
+ * nrf_query_grad_workspace_bytes(h, 1, count, flags). */
+int nrf_query_grid_grad(nrf_handle h, const float* params, const nrf_rays* group, const nrf_grid* grid, int64_t first, int32_t count,
+                        int32_t level, const nrf_step_scalars* scalars, uint32_t flags, const nrf_field_grad_out* out, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* flax.optim.Adam.apply_gradient (training.py:268-269; flax 0.3.4 optim/adam.py):
  * g = grad*grad_scale (grad_scale = 1/world_size folds lax.pmean, training.py:266),
  * m,v updated in place, step = number of updates already applied.  Hyper-parameters are doubles

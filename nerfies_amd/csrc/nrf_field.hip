@@ -201,6 +201,190 @@ int query_args(nrf_handle h, const float* params, const nrf_rays* groups, int S,
     return fail(NRF_E_UNSUPPORTED, "out->rgb on a use_viewdirs model needs groups->viewdirs (a point has no direction to fall back on)");
   return require_ids_or_codes(h, groups, out->rgb != nullptr, out->rgb || out->sigma, warp_on);
 }
+
+// what both grid entries check of the grid and the range inside it
+int grid_range(const char* entry, const nrf_rays* group, const nrf_grid* grid, int64_t first, int count) {
+  if (group->num_rays != 1) {
+    snprintf(g_err, sizeof(g_err), "%s: group->num_rays must be 1 (one condition for the whole grid)", entry);
+    return NRF_E_SHAPE;
+  }
+  if (grid->dims[0] <= 0 || grid->dims[1] <= 0 || grid->dims[2] <= 0) return fail(NRF_E_SHAPE, "grid dims must be positive");
+  // at most 2^40 points in a grid: the product of three int32 extents cannot wrap int64 behind this
+  const int64_t plane = (int64_t)grid->dims[0] * grid->dims[1];
+  if (plane > NRF_GRID_MAX_POINTS || plane * grid->dims[2] > NRF_GRID_MAX_POINTS)
+    return fail(NRF_E_SHAPE, "grid dims: more than NRF_GRID_MAX_POINTS (1 << 40) points in dims[0] * dims[1] * dims[2]");
+  const int64_t total = plane * grid->dims[2];
+  if (first < 0 || first + count > total) return fail(NRF_E_SHAPE, "first + count runs beyond the grid (dims[0] * dims[1] * dims[2] points)");
+  return NRF_OK;
+}
+
+// ---- Gradient queries (nrf_query_points_grad / nrf_query_grid_grad): the density chain keeping its sign words and posenc stash, the
+// reverse chain from the density to the point, the warp Jacobian of the row.  A plan of its own (query_plan is as it was).  Workspace:
+// [pack descriptors | embed table | padded params | forward and transposed images of one MLP, W0^T / skip rows^T behind them on a
+//  model without a warp field | SE3 trunk image | tile counters | cond, condterm, alpha_ct of G groups | grid points |
+//  sign words | posenc stash | sigma'(raw) | d points || warp: code rows | warped points | trunk input | sign words | (w, v) |
+//  tangent (dw, dv) | Jacobian]
+// Every per-row buffer holds ntiles * 64 rows: the reverse chain writes d_points for whole tiles and the stashes are indexed by tile.
+struct QueryGradPlan {
+  size_t desc_f, emb_f = 0, ip_f = 0, wpk_f, wwpk_f, ctr_f, cond_f, condterm_f, alpha_ct_f, points_f, bits_f, pe_f, dsig_f, dpoints_f;
+  size_t ids_f = 0, wpoints_f = 0, w_win_f = 0, w_bits_f = 0, w_wv_f = 0, t_wv_f = 0, jac_f = 0, total_f;
+  int N, ntiles, L0T, L4bT;   // L0T / L4bT: PackOffsets::bwd_L0T / bwd_L4bT inside the image at wpk_f
+};
+constexpr int QUERY_GRAD_MAX_DESCS = 48;   // 11 + 9 transposed + 2 d-posenc + 3 x 2 rgb branch layers + 7 of the SE3 trunk
+QueryGradPlan query_grad_plan(const nrf_handle_s* h, int G, int S) {
+  QueryGradPlan q;
+  q.N = G * S;
+  q.ntiles = (q.N + TILE_ROWS - 1) / TILE_ROWS;
+  const size_t rows_pad = (size_t)q.ntiles * TILE_ROWS;
+  const int PKS = (h->PK + 31) / 32 * 32;
+  Carve c;
+  q.desc_f = c.take(QUERY_GRAD_MAX_DESCS * sizeof(PackDesc) / 4);
+  if (h->embed) {   // a model narrower than the kernels runs on its zero-padded image
+    q.emb_f = c.take((h->emb.size() + 1) * sizeof(EmbedDesc) / 4);
+    q.ip_f = c.take((size_t)h->nparams);
+  }
+  // a warp model's PackOffsets hold the two d-posenc images; without a warp field they follow the level's own images and their
+  // prefetch slack (as a ray-gradient plan places them, nrf_plan.hip rg_wpkT)
+  q.L0T = h->warp ? h->pk.bwd_L0T : h->pk.total;
+  q.L4bT = h->warp ? h->pk.bwd_L4bT : h->pk.total + 256 * 64;
+  q.wpk_f = c.take(h->warp ? (size_t)h->pk.total : (size_t)q.L4bT + 256 * 64 + 4096);
+  q.wwpk_f = h->warp ? c.take(h->wpk.total) : 0;
+  q.ctr_f = c.take(16);
+  q.cond_f = c.take((size_t)G * (h->R > 0 ? h->R : 1));
+  q.condterm_f = c.take((size_t)G * RGB_W);
+  q.alpha_ct_f = c.take((size_t)G);
+  q.points_f = c.take(rows_pad * 3);                                // nrf_query_grid_grad forms its points here
+  q.bits_f = c.take((size_t)TRUNK_DEPTH * q.ntiles * 4 * 128);      // 8 layers x tile x 4 waves x 128 words: 256 B per row
+  q.pe_f = c.take((size_t)q.ntiles * PKS * TILE_ROWS);              // [PKS][64] per tile: 4 PKS B per row
+  q.dsig_f = c.take(rows_pad);
+  q.dpoints_f = c.take(rows_pad * 3);
+  if (h->warp) {
+    const int PKSw = (h->PKw + 31) / 32 * 32;
+    q.ids_f = c.take(rows_pad);
+    q.wpoints_f = c.take(rows_pad * 3);
+    q.w_win_f = c.take((size_t)q.ntiles * PKSw * TILE_ROWS);
+    q.w_bits_f = c.take((size_t)WARP_DEPTH * q.ntiles * 4 * 64);
+    q.w_wv_f = c.take(rows_pad * 8);
+    q.t_wv_f = c.take(3 * rows_pad * 8);                            // 3 tangent tiles per primal tile
+    q.jac_f = c.take(rows_pad * 9);
+  }
+  q.total_f = c.o;
+  return q;
+}
+
+int query_grad_shape(int G, int S) {
+  CK(query_shape(G, S));
+  if ((int64_t)G * S > NRF_QUERY_GRAD_MAX_POINTS)
+    return fail(NRF_E_SHAPE, "a gradient query takes at most 1 << 20 points per call (NRF_QUERY_GRAD_MAX_POINTS)");
+  return NRF_OK;
+}
+
+// what both gradient entries check of everything but the points: a density-only query's rules and the smaller point cap
+int query_grad_args(nrf_handle h, const float* params, const nrf_rays* groups, int S, int level, const nrf_step_scalars* sc, uint32_t flags,
+                    const nrf_field_grad_out* out, const void* workspace) {
+  if (h && params && groups && sc && !out) return fail(NRF_E_NULL, "out (nrf_field_grad_out) is null");
+  float always = 0.f;   // the density is computed whatever the caller asks for: the ids it needs are required
+  const nrf_field_out as_density = {&always, nullptr, out ? out->warped_points : nullptr};
+  CK(query_args(h, params, groups, S, level, sc, flags, &as_density, workspace));
+  return query_grad_shape(groups->num_rays, S);
+}
+
+// both entries behind their own argument checks; points == nullptr: the grid's, already formed at q.points_f
+int query_grad_impl(nrf_handle h, const float* params_x, const nrf_rays* groups, const float* points, int S, int level,
+                    const nrf_step_scalars* sc, uint32_t flags, const nrf_field_grad_out* out, float* ws, const QueryGradPlan& q,
+                    hipStream_t st, const char* entry) {
+  const int G = groups->num_rays, N = q.N;
+  const bool warp_on = h->warp && !(flags & NRF_FLAG_NO_WARP);
+  Prof& pf = h->prof;
+  query_device(h);
+  forget_workspace(h, ws);
+  if (!points) points = ws + q.points_f;
+  const float* params = params_x;
+  if (h->embed && !(params = embed_side(h, params_x, ws, q.emb_f, q.ip_f, st))) return NRF_E_HIP;
+  // forward and transposed images of the asked level, the two d-posenc images, the SE3 trunk's forward image
+  SidePack& pack = h->qg_pack;
+  refresh(pack, level, [&](std::vector<PackDesc>& v) {
+    mlp_pack_descs(h, level, (int64_t)q.wpk_f, true, v);
+    if (!h->warp) {   // mlp_pack_descs adds them for a warp model, at its PackOffsets
+      const MlpParamOffsets& po = h->po[level];
+      v.push_back(PackDesc{po.trunk_k[0], (int64_t)q.wpk_f + q.L0T, 256, 0, 256, 256, 2, 1, 1, h->P});
+      v.push_back(PackDesc{po.trunk_k[h->d.nerf_skip_layer], (int64_t)q.wpk_f + q.L4bT, 256, 256, 256, 256, 2, 1, 1, h->P});
+    }
+    if (h->warp) warp_pack_descs(h, h->wpo, (int64_t)q.wwpk_f, false, v);
+  });
+  if ((int)pack.descs.size() > QUERY_GRAD_MAX_DESCS) return fail(NRF_E_STATE, "gradient query: pack table larger than its workspace region");
+  hipError_t e = hipMemcpyAsync(ws + q.desc_f, pack.descs.data(), pack.descs.size() * sizeof(PackDesc), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return fail_hip(e, "upload gradient query pack table");
+  if (tile_counter_or_null(ws + q.ctr_f, 0)) {   // NRF_DYNAMIC_TILES experiment only
+    e = hipMemsetAsync(ws + q.ctr_f, 0, 16 * sizeof(int), st);
+    if (e != hipSuccess) return fail_hip(e, "zero tile counters");
+  }
+  pf.begin("qgrad_prep", 0, st);   // no return between a begin and its end
+  launch_pack(reinterpret_cast<const PackDesc*>(ws + q.desc_f), (int)pack.descs.size(), params, ws, st);
+  if (h->A > 0) {   // use_alpha_condition: the appearance code's term of the alpha head (query_impl)
+    const RayPrepLevel lv{level, ws + q.condterm_f, ws + q.alpha_ct_f};
+    launch_ray_prep(ray_prep_args(h, params, groups, groups->viewdirs, ws + q.cond_f, &lv, 1, true), st);
+  }
+  pf.end(st);
+  if (warp_on) {
+    // the primal SE3 forward on explicit points with one id per point (query_impl), keeping what a frozen ray plan keeps (trunk
+    // input, sign words, (w, v)); its tangent pass, three tangent tiles per primal tile; the Jacobian of every row
+    const int PKSw = (h->PKw + 31) / 32 * 32;
+    int32_t* ids = reinterpret_cast<int32_t*>(ws + q.ids_f);
+    launch_field_ids(groups->warp_codes ? nullptr : groups->warp_ids, N, S, ids, st);
+    WarpFwdArgs wa = warp_points_args(h, params, h->wpo, ws + q.wwpk_f, sc, points, ids, N, ws + q.wpoints_f);
+    if (groups->warp_codes) wa.embed_table = groups->warp_codes;
+    wa.tile_counter = tile_counter_or_null(ws + q.ctr_f, 0);
+    wa.st_win = ws + q.w_win_f; wa.st_wv = reinterpret_cast<float4*>(ws + q.w_wv_f); wa.bits = reinterpret_cast<uint32_t*>(ws + q.w_bits_f);
+    pf.begin("qgrad_warp", warp_fwd_flops_row(h) * N, st);
+    launch_warp_fwd(wa, nullptr, true, tile_grid(wa.ntiles, warp_grid_mul(), h->num_cus), st, true);
+    pf.end(st);
+    WarpFwdArgs ta = wa;
+    ta.nt_prim = q.ntiles; ta.prim_win = wa.st_win; ta.prim_bits = wa.bits;
+    ta.ntiles = 3 * q.ntiles; ta.rows = ta.ntiles * TILE_ROWS;
+    ta.st_win = nullptr; ta.bits = nullptr; ta.points_out = nullptr; ta.st_wv = reinterpret_cast<float4*>(ws + q.t_wv_f);
+    ta.tile_counter = tile_counter_or_null(ws + q.ctr_f, 2);
+    pf.begin("qgrad_tangent", 3.0 * warp_fwd_flops_row(h) * N, st);
+    launch_warp_fwd(ta, nullptr, true, tile_grid(ta.ntiles, warp_grid_mul(), h->num_cus), st, true);
+    pf.end(st);
+    JacobianArgs ja;
+    memset(&ja, 0, sizeof(ja));   // x_rows = nullptr: the points come from the trunk-input stash
+    ja.prim_win = wa.st_win; ja.prim_wv = wa.st_wv; ja.tan_wv = ta.st_wv; ja.out = ws + q.jac_f;
+    ja.rows = N; ja.rows_pad = q.ntiles * TILE_ROWS; ja.PKS = PKSw;
+    pf.begin("qgrad_jacobian", 0, st);
+    launch_jacobian(ja, st);
+    pf.end(st);
+    points = ws + q.wpoints_f;
+  }
+  ChainFwdArgs a = chain_model_args(h, params, level, ws + q.alpha_ct_f);
+  a.wpk = ws + q.wpk_f; a.points = points; a.S = S; a.B = G; a.rows = N; a.ntiles = q.ntiles;
+  a.st_pe = ws + q.pe_f; a.bits_trunk = reinterpret_cast<uint32_t*>(ws + q.bits_f);
+  a.tile_counter = tile_counter_or_null(ws + q.ctr_f, 1);
+  const ChainTiling t = chain_fwd_tiling(h, q.ntiles, false);   // 64-row tiles only (chain_query_grad.hip)
+  a.k_old = t.k_old;
+  pf.begin("qgrad_fwd", density_flops_row(h) * N, st);
+  launch_chain_density_stash(a, out->sigma, ws + q.dsig_f, t.grid, st);
+  pf.end(st);
+  ChainBwdArgs b;
+  memset(&b, 0, sizeof(b));
+  b.params = params; b.po = a.po; b.wpk = a.wpk; b.pk = a.pk; b.pk.bwd_L0T = q.L0T; b.pk.bwd_L4bT = q.L4bT;
+  b.S = S; b.B = G; b.rows = N; b.ntiles = q.ntiles;
+  b.bits_trunk = a.bits_trunk; b.st_pe = a.st_pe; b.d_points = ws + q.dpoints_f;
+  b.F = a.F; b.P = a.P; b.PK = a.PK; b.skip = a.skip; b.alpha_on_bn = h->A > 0;
+  pf.begin("qgrad_bwd", density_bwd_flops_row(h) * N, st);
+  launch_chain_density_bwd(b, ws + q.dsig_f, t.grid, st);
+  pf.end(st);
+  if (out->grad_sigma || out->normals) {
+    pf.begin("qgrad_finish", 0, st);
+    launch_field_grad_finish(ws + q.dpoints_f, warp_on ? ws + q.jac_f : nullptr, N, out->grad_sigma, out->normals, st);
+    pf.end(st);
+  }
+  if (out->warped_points) {
+    e = hipMemcpyAsync(out->warped_points, ws + q.wpoints_f, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return fail_hip(e, "copy warped points");
+  }
+  return check_launch(entry);
+}
 }  // namespace
 
 extern "C" {
@@ -266,19 +450,45 @@ int nrf_query_grid(nrf_handle h, const float* params, const nrf_rays* group, con
                    size_t workspace_bytes, void* stream) {
   if (h && !grid) return fail(NRF_E_NULL, "grid is null");
   CK(query_args(h, params, group, count, level, scalars, flags, out, workspace));
-  if (group->num_rays != 1) return fail(NRF_E_SHAPE, "nrf_query_grid: group->num_rays must be 1 (one condition for the whole grid)");
-  if (grid->dims[0] <= 0 || grid->dims[1] <= 0 || grid->dims[2] <= 0) return fail(NRF_E_SHAPE, "grid dims must be positive");
-  // at most 2^40 points in a grid: the product of three int32 extents cannot wrap int64 behind this
-  const int64_t plane = (int64_t)grid->dims[0] * grid->dims[1];
-  if (plane > NRF_GRID_MAX_POINTS || plane * grid->dims[2] > NRF_GRID_MAX_POINTS)
-    return fail(NRF_E_SHAPE, "grid dims: more than NRF_GRID_MAX_POINTS (1 << 40) points in dims[0] * dims[1] * dims[2]");
-  const int64_t total = plane * grid->dims[2];
-  if (first < 0 || first + count > total) return fail(NRF_E_SHAPE, "first + count runs beyond the grid (dims[0] * dims[1] * dims[2] points)");
+  CK(grid_range("nrf_query_grid", group, grid, first, count));
   const QueryPlan q = query_plan(h, 1, count);
   if (workspace_bytes < q.total_f * sizeof(float)) return fail(NRF_E_WORKSPACE, "workspace too small (see nrf_query_workspace_bytes)");
   query_device(h);
   launch_grid_points(*grid, first, count, (float*)workspace + q.points_f, (hipStream_t)stream);
   return query_impl(h, params, group, nullptr, count, level, scalars, flags, out, (float*)workspace, q, (hipStream_t)stream);
+}
+
+int nrf_query_grad_workspace_bytes(nrf_handle h, int32_t num_groups, int32_t points_per_group, uint32_t flags, size_t* bytes) {
+  if (!h || !bytes) return fail(NRF_E_NULL, "handle / bytes is null");
+  CK(query_flags(flags));
+  CK(query_grad_shape(num_groups, points_per_group));
+  *bytes = query_grad_plan(h, num_groups, points_per_group).total_f * sizeof(float);
+  return NRF_OK;
+}
+
+int nrf_query_points_grad(nrf_handle h, const float* params, const nrf_rays* groups, const float* points, int32_t points_per_group,
+                          int32_t level, const nrf_step_scalars* scalars, uint32_t flags, const nrf_field_grad_out* out, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  if (h && !points) return fail(NRF_E_NULL, "points is null");
+  CK(query_grad_args(h, params, groups, points_per_group, level, scalars, flags, out, workspace));
+  const QueryGradPlan q = query_grad_plan(h, groups->num_rays, points_per_group);
+  if (workspace_bytes < q.total_f * sizeof(float)) return fail(NRF_E_WORKSPACE, "workspace too small (see nrf_query_grad_workspace_bytes)");
+  return query_grad_impl(h, params, groups, points, points_per_group, level, scalars, flags, out, (float*)workspace, q, (hipStream_t)stream,
+                         "nrf_query_points_grad");
+}
+
+int nrf_query_grid_grad(nrf_handle h, const float* params, const nrf_rays* group, const nrf_grid* grid, int64_t first, int32_t count,
+                        int32_t level, const nrf_step_scalars* scalars, uint32_t flags, const nrf_field_grad_out* out, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  if (h && !grid) return fail(NRF_E_NULL, "grid is null");
+  CK(query_grad_args(h, params, group, count, level, scalars, flags, out, workspace));
+  CK(grid_range("nrf_query_grid_grad", group, grid, first, count));
+  const QueryGradPlan q = query_grad_plan(h, 1, count);
+  if (workspace_bytes < q.total_f * sizeof(float)) return fail(NRF_E_WORKSPACE, "workspace too small (see nrf_query_grad_workspace_bytes)");
+  query_device(h);
+  launch_grid_points(*grid, first, count, (float*)workspace + q.points_f, (hipStream_t)stream);
+  return query_grad_impl(h, params, group, nullptr, count, level, scalars, flags, out, (float*)workspace, q, (hipStream_t)stream,
+                         "nrf_query_grid_grad");
 }
 
 }  // extern "C"

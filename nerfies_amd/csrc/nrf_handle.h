@@ -253,6 +253,7 @@ struct nrf_handle_s {
   int stashed_B = -1;
   nrf::api::Modes stashed_modes;
   nrf::api::SidePack wp_pack, q_pack;   // nrf_warp_points (key: its image's offset) / the field queries (key: the level)
+  nrf::api::SidePack qg_pack;           // the gradient queries (key: the level)
 };
 
 namespace nrf {
@@ -276,6 +277,8 @@ void query_device(nrf_handle h);
 int check_launch(const char* where);
 // algorithmic flops per row (2 flop / MAC, dense layers only, unpadded): NeRF forward chain, its trunk + alpha head, SE3 forward
 double fwd_flops_row(const nrf_handle_s* h), density_flops_row(const nrf_handle_s* h), warp_fwd_flops_row(const nrf_handle_s* h);
+// ... the reverse chain of a gradient query: alpha head^T, (bottleneck^T,) seven trunk layers^T, the two d-posenc GEMMs
+double density_bwd_flops_row(const nrf_handle_s* h);
 // the "ids or codes" a call reads of `r`, among those the model has
 int require_ids_or_codes(const nrf_handle_s* h, const nrf_rays* r, bool camera, bool appearance, bool warp);
 // narrow-model prologue: zero `image`, embed the caller's params into it through the uploaded `table`; the image, or nullptr (g_err)

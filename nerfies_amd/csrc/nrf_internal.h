@@ -446,6 +446,15 @@ void launch_field_ids(const int32_t* group_ids, int rows, int S, int32_t* ids, h
 void launch_field_unpack(const float4* out4, int rows, float* sigma, float* rgb, hipStream_t stream);
 // points [first, first + count) of a grid -> out[count][3]
 void launch_grid_points(const nrf_grid& g, long long first, int count, float* out, hipStream_t stream);
+// chain_query_grad.hip: the kernels of a gradient query (nrf_query_points_grad / nrf_query_grid_grad), 64-row tiles.  Forward: the
+// density chain keeping a.st_pe, a.bits_trunk and sigma'(raw) in dsig[ntiles * 64]; sigma[rows] (may be nullptr) has the bits of
+// launch_chain_density.  Reverse: from dsig down the trunk to a.d_points[ntiles * 64][3]; `a` carries params / po / wpk / pk / rows /
+// ntiles / bits_trunk / st_pe / d_points / F / P / PK / skip / alpha_on_bn and nothing else is read
+void launch_chain_density_stash(const ChainFwdArgs& a, float* sigma, float* dsig, int grid, hipStream_t stream);
+void launch_chain_density_bwd(const ChainBwdArgs& a, const float* dsig, int grid, hipStream_t stream);
+// grad[rows][3] = J^T d_points (jac [rows][9] row-major d x'_i / d x_j, nullptr: the identity) and normals[rows][3] = -grad / |grad|
+// (exactly 0 where |grad|^2 is 0 or not finite); either output may be nullptr
+void launch_field_grad_finish(const float* d_points, const float* jac, int rows, float* grad, float* normals, hipStream_t stream);
 // a1 (optional): a second level in the same launch (background points behind the coarse samples)
 void launch_warp_fwd(const WarpFwdArgs& a, const WarpFwdArgs* a1, bool stash, int grid, hipStream_t stream, bool frozen = false);   // frozen: no activation stash
 // a1, a2 (optional): further levels in the same launch; bias partials of all levels go to a.small_part

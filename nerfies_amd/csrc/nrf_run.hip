@@ -90,6 +90,7 @@ ChainFwdArgs chain_model_args(const nrf_handle_s* h, const float* params, int le
 static double rgbx_flops_row(const nrf_handle_s* h) { return 2.0 * 16384.0 * (h->d.nerf_rgb_branch_depth - 1); }   // rgb branch layers 1..
 static double trunk_macs_row(const nrf_handle_s* h) { return h->P * 256 + 6 * 65536.0 + (256 + h->P) * 256 + 256; }   // 8 layers + alpha head
 double density_flops_row(const nrf_handle_s* h) { return 2.0 * (trunk_macs_row(h) + (h->A > 0 ? 65536.0 : 0.0)); }   // (+ bottleneck)
+double density_bwd_flops_row(const nrf_handle_s* h) { return 2.0 * (256 + (h->A > 0 ? 65536.0 : 0.0) + 7 * 65536.0 + 2.0 * 256 * h->P); }
 double fwd_flops_row(const nrf_handle_s* h) { return 2.0 * (trunk_macs_row(h) + 65536.0 + (256.0 + h->R) * 128 + 128 * 3) + rgbx_flops_row(h); }
 // SE3 field per row: trunk + heads
 double warp_fwd_flops_row(const nrf_handle_s* h) { return 2.0 * (h->Win * 128 + 3 * 16384.0 + (128 + h->Win) * 128 + 16384.0 + 128 * 6); }

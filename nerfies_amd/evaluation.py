@@ -273,6 +273,38 @@ def density_grid(model, params, bbox_min, bbox_max, resolution, level='fine', wa
   return sigma.view(res[2], res[1], res[0]).permute(2, 1, 0)
 
 
+def normal_grid(model, params, bbox_min, bbox_max, resolution, level='fine', warp_id=None, appearance_id=None, warp_extra=None,
+                chunk=1 << 20, device=None):
+  """Density and surface normals -grad sigma / |grad sigma| on the grid of `density_grid` (same box, voxel centres, memory order and
+  arguments): (sigma (X, Y, Z), normals (X, Y, Z, 3)), float32 device tensors.  A normal is exactly 0 where the gradient vanishes.
+  With a `warp_id` the gradient is taken with respect to the observation-space point, through the warp field.  The points are formed
+  on the device by nrf_query_grid_grad, `chunk` (at most NRF_QUERY_GRAD_MAX_POINTS) of them per call through one workspace."""
+  from nerfies_amd import lib as L
+  res = (int(resolution),) * 3 if isinstance(resolution, int) else tuple(int(r) for r in resolution)
+  if len(res) != 3 or min(res) <= 0:
+    raise ValueError(f'resolution must be a positive int or (X, Y, Z), got {resolution!r}')
+  lo = [float(v) for v in bbox_min]
+  hi = [float(v) for v in bbox_max]
+  step = [(h - l) / r for l, h, r in zip(lo, hi, res)]
+  origin = [l + 0.5 * s for l, s in zip(lo, step)]
+  if device is None:
+    device = params.flat.device if hasattr(params, 'flat') else 'cuda'
+  metadata = {}
+  if warp_id is not None:
+    metadata['warp'] = torch.tensor([[int(warp_id)]], dtype=torch.int32, device=device)
+  if appearance_id is not None:
+    metadata['appearance'] = torch.tensor([[int(appearance_id)]], dtype=torch.int32, device=device)
+  total = res[0] * res[1] * res[2]
+  chunk = max(1, min(int(chunk), total, L.NRF_QUERY_GRAD_MAX_POINTS))
+  sigma = torch.empty(total, dtype=torch.float32, device=device)
+  normals = torch.empty(total, 3, dtype=torch.float32, device=device)
+  for first, count in grid_chunks(total, chunk):
+    model.query_grid_gradient(params, origin, step, res, first, count,
+                              {'sigma': sigma[first:first + count], 'normals': normals[first:first + count]}, metadata=metadata,
+                              warp_extra=warp_extra, level=level, use_warp=warp_id is not None, workspace_points=chunk)
+  return sigma.view(res[2], res[1], res[0]).permute(2, 1, 0), normals.view(res[2], res[1], res[0], 3).permute(2, 1, 0, 3)
+
+
 def compute_psnr(mse):
   """utils.compute_psnr (utils.py:283-293): -10 log10(mse)."""
   return -10.0 * torch.log10(torch.as_tensor(mse))

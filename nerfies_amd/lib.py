@@ -139,7 +139,13 @@ class Grid(C.Structure):
   _fields_ = [('origin', C.c_float * 3), ('step', C.c_float * 3), ('dims', C.c_int32 * 3), ('reserved', C.c_int32)]
 
 
+class FieldGradOut(C.Structure):
+  """nrf_field_grad_out: the device outputs of a gradient query, N rows each; a NULL pointer skips that output."""
+  _fields_ = [('sigma', C.c_void_p), ('grad_sigma', C.c_void_p), ('normals', C.c_void_p), ('warped_points', C.c_void_p)]
+
+
 NRF_QUERY_MAX_POINTS = 1 << 24   # points of one nrf_query_points / nrf_query_grid call
+NRF_QUERY_GRAD_MAX_POINTS = 1 << 20   # points of one nrf_query_points_grad / nrf_query_grid_grad call
 NRF_GRID_MAX_POINTS = 1 << 40    # points of a whole nrf_grid
 NRF_OPT_CHAIN_TILE_ROWS = 1
 NRF_OPT_BF16_WGRAD_MERGE = 2
@@ -158,6 +164,7 @@ EXPORTS = [
     'nrf_train_step_loss_grad_rays', 'nrf_camera_table_compose', 'nrf_camera_table_compose_backward',
     'nrf_loss_grad_rays',
     'nrf_query_workspace_bytes', 'nrf_query_points', 'nrf_query_grid',
+    'nrf_query_grad_workspace_bytes', 'nrf_query_points_grad', 'nrf_query_grid_grad',
 ]
 
 _lib = None
@@ -220,6 +227,11 @@ def load_library(path=None):
       'nrf_query_points': [vp, vp, C.POINTER(Rays), vp, i32, i32, C.POINTER(StepScalars), u32, C.POINTER(FieldOut), vp, C.c_size_t, vp],
       'nrf_query_grid': [vp, vp, C.POINTER(Rays), C.POINTER(Grid), i64, i32, i32, C.POINTER(StepScalars), u32, C.POINTER(FieldOut), vp,
                          C.c_size_t, vp],
+      'nrf_query_grad_workspace_bytes': [vp, i32, i32, u32, C.POINTER(C.c_size_t)],
+      'nrf_query_points_grad': [vp, vp, C.POINTER(Rays), vp, i32, i32, C.POINTER(StepScalars), u32, C.POINTER(FieldGradOut), vp,
+                                C.c_size_t, vp],
+      'nrf_query_grid_grad': [vp, vp, C.POINTER(Rays), C.POINTER(Grid), i64, i32, i32, C.POINTER(StepScalars), u32,
+                              C.POINTER(FieldGradOut), vp, C.c_size_t, vp],
       'nrf_camera_pixels_to_rays': [C.POINTER(CameraDesc), vp, i64, vp, vp, vp, vp],
       'nrf_camera_pixels_to_points': [C.POINTER(CameraDesc), vp, vp, i64, vp, vp],
       'nrf_camera_project': [C.POINTER(CameraDesc), vp, i64, vp, vp],

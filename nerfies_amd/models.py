@@ -600,6 +600,98 @@ class NerfModel:
     del keep
     return out
 
+  # ---- gradient queries: the density's slope and the surface normal at the caller's points ----
+  GRADIENT_OUTPUTS = ('sigma', 'grad_sigma', 'normals', 'warped_points')
+
+  def _query_grad_record(self, num_groups, points_per_group, flags, device) -> CallRecord:
+    """As `_query_record`, for the plan of a gradient query (keys of its own in the workspace cache)."""
+    key = ('query_grad', int(num_groups), int(points_per_group), str(device))
+    ws = self._ws.get(key)
+    if ws is None:
+      nbytes = C.c_size_t(0)
+      L.check(self.lib.nrf_query_grad_workspace_bytes(self.handle, int(num_groups), int(points_per_group), flags, C.byref(nbytes)), self.lib)
+      ws = self._ws[key] = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=device)
+    return CallRecord(int(num_groups), ws, flags, self.generation)
+
+  def _gradient_outputs(self, outputs):
+    outputs = tuple(outputs)
+    if not outputs or set(outputs) - set(self.GRADIENT_OUTPUTS):
+      raise L.NrfError(f'outputs must be a non-empty selection of {self.GRADIENT_OUTPUTS}, got {outputs}')
+    return outputs
+
+  def query_gradient(self, variables, points, metadata=None, warp_extra=None, level='fine', use_warp=True, metadata_encoded=False,
+                     outputs=('sigma', 'grad_sigma', 'normals')):
+    """The density, its gradient with respect to `points` (through the warp field unless use_warp=False) and the surface normal
+    -grad / |grad| (exactly 0 where the gradient vanishes) at arbitrary points: nrf_query_points_grad.  `points` (..., S, 3) is
+    grouped as in `query_points`; no view direction is read.  `outputs` selects among 'sigma', 'grad_sigma', 'normals' and
+    'warped_points'.  More than NRF_QUERY_GRAD_MAX_POINTS points run as chunks of whole groups (or, one group, of points) through
+    one cached workspace.  Returns a dict of device tensors shaped like points[..., 0] (a trailing 3 for all but 'sigma')."""
+    device = torch.as_tensor(points).device
+    if device.type != 'cuda':
+      raise L.NrfError('points must live on the GPU: the hot path has no CPU fallback')
+    return self._query_gradient_chunks(variables, points, metadata, warp_extra, level, use_warp, metadata_encoded, outputs, device)
+
+  def _query_gradient_chunks(self, variables, points, metadata, warp_extra, level, use_warp, metadata_encoded, outputs, device):
+    """`query_gradient` behind its device rule: the calls into the library, one per chunk."""
+    outputs = self._gradient_outputs(outputs)
+    pts = _f32(points, device)
+    if pts.dim() < 2 or pts.shape[-1] != 3:
+      raise L.NrfError(f'points must be (..., S, 3), got {tuple(pts.shape)}')
+    lead, S = tuple(pts.shape[:-2]), pts.shape[-2]
+    G = 1
+    for n in lead:
+      G *= n
+    # a device other than the GPU is reached only under a recording stand-in for the library (tests/test_field_gradient_host.py drives
+    # the chunking on CPU tensors): the library itself follows these pointers on the GPU alone, and `query_gradient` refuses the rest
+    stream = _stream(device) if device.type == 'cuda' else None
+    md = {}
+    for k, v in (metadata or {}).items():   # one row per group: a chunk of groups takes its rows
+      v = torch.as_tensor(v, device=device)
+      if v.numel() % G or v.numel() == 0:
+        raise L.NrfError(f'metadata[{k!r}] must have one row per group ({G}), got shape {tuple(v.shape)}')
+      md[k] = v.reshape(G, -1)
+    pts = pts.reshape(G, S, 3)
+    ret = {k: torch.empty(G, S, *(() if k == 'sigma' else (3,)), dtype=torch.float32, device=device) for k in outputs}
+    cap = L.NRF_QUERY_GRAD_MAX_POINTS
+    if S <= cap:   # chunks of whole groups
+      per = cap // S
+      pieces = [(g0, min(per, G - g0), 0, S) for g0 in range(0, G, per)]
+    elif G == 1:   # one long group: chunks of its points
+      pieces = [(0, 1, s0, min(cap, S - s0)) for s0 in range(0, S, cap)]
+    else:
+      raise L.NrfError(f'query_gradient: groups of more than NRF_QUERY_GRAD_MAX_POINTS = {cap} points are chunked only when there is one group')
+    for g0, ng, s0, ns in pieces:   # every slice below is contiguous: whole groups, or a run of the one group's points
+      fp, groups, keep, scal, flags, lv, _ = self._query_setup(variables, ng, None, {k: v[g0:g0 + ng] for k, v in md.items()}, warp_extra,
+                                                               level, use_warp, metadata_encoded, ('sigma',), device)
+      rec = self._query_grad_record(pieces[0][1], pieces[0][3], flags, device)   # the first piece is the largest
+      fo = L.FieldGradOut(*(_ptr(ret[k][g0:g0 + ng, s0:s0 + ns]) if k in ret else None for k in self.GRADIENT_OUTPUTS))
+      L.check(self.lib.nrf_query_points_grad(self.handle, _ptr(fp.flat), C.byref(groups), _ptr(pts[g0:g0 + ng, s0:s0 + ns]), ns, lv,
+                                             C.byref(scal), flags, C.byref(fo), _ptr(rec.ws), rec.ws.numel() * 4, stream), self.lib)
+      del keep
+    return {k: v.reshape(*lead, S, *v.shape[2:]) for k, v in ret.items()}
+
+  def query_grid_gradient(self, variables, origin, step, dims, first, count, out, metadata=None, warp_extra=None, level='fine',
+                          use_warp=True, metadata_encoded=False, workspace_points=None):
+    """Points [first, first + count) of a regular grid (nrf_query_grid_grad; the grid of `query_grid`) into the preallocated tensors
+    of `out` ({'sigma': (count,), 'grad_sigma': (count, 3), 'normals': (count, 3), ...}); count <= NRF_QUERY_GRAD_MAX_POINTS."""
+    device = next(iter(out.values())).device
+    outputs = self._gradient_outputs(out)
+    fp, groups, keep, scal, flags, lv, _ = self._query_setup(variables, 1, None, metadata, warp_extra, level, use_warp, metadata_encoded,
+                                                             ('sigma',), device)
+    for k in outputs:
+      want = (count,) if k == 'sigma' else (count, 3)
+      if tuple(out[k].shape) != want or out[k].dtype != torch.float32 or not out[k].is_contiguous():
+        raise L.NrfError(f'query_grid_gradient: out[{k!r}] must be a contiguous float32 tensor of shape {want}')
+    grid = L.Grid((C.c_float * 3)(*[float(v) for v in origin]), (C.c_float * 3)(*[float(v) for v in step]),
+                  (C.c_int32 * 3)(*[int(v) for v in dims]), 0)
+    fo = L.FieldGradOut(*(_ptr(out.get(k)) for k in self.GRADIENT_OUTPUTS))
+    rec = self._query_grad_record(1, max(int(workspace_points or 0), int(count)), flags, device)
+    stream = _stream(device) if device.type == 'cuda' else None   # not cuda: a recording stand-in for the library only, as in query_grid
+    L.check(self.lib.nrf_query_grid_grad(self.handle, _ptr(fp.flat), C.byref(groups), C.byref(grid), int(first), int(count), lv,
+                                         C.byref(scal), flags, C.byref(fo), _ptr(rec.ws), rec.ws.numel() * 4, stream), self.lib)
+    del keep
+    return out
+
   def backward(self, variables, rays_dict, d_rgb_coarse=None, d_rgb_fine=None, grad_out: torch.Tensor = None, d_out=None,
                ray_grads=False):
     """VJP of the last `apply(..., train=True)` on the same rays: returns the flat parameter gradient.

@@ -11,6 +11,9 @@ Writes, next to the checkpoints' experiment directory:
   density_<name>.npy   float32 (X, Y, Z) sigma at the voxel centres (<name> = the frame id, or 'canonical'), and
   density_<name>.ply   ASCII point cloud of the voxel centres with sigma > --threshold, coloured by a full query along a fixed
                        view direction.
+With --normals (evaluation.normal_grid -> nrf_query_grid_grad: the density's gradient from the reverse chain, no finite differences):
+  normals_<name>.npy   float32 (X, Y, Z, 3) unit normals -grad sigma / |grad sigma| at the voxel centres (0 where the gradient
+                       vanishes), and the PLY's vertices gain the properties nx ny nz.
 There is no mesh extraction: the .npy grid is what a marching-cubes tool reads."""
 import argparse
 import os
@@ -38,6 +41,7 @@ def parse_flags(argv=None):
   which.add_argument('--canonical', action='store_true', help='query the canonical volume (NRF_FLAG_NO_WARP)')
   p.add_argument('--threshold', type=float, default=10.0, help='voxels with sigma above it go into the PLY')
   p.add_argument('--level', default='fine', choices=['coarse', 'fine'])
+  p.add_argument('--normals', action='store_true', help='also export the surface normals -grad sigma / |grad sigma| (npy, and nx ny nz in the PLY)')
   p.add_argument('--margin', type=float, default=0.0, help="grow the scene points' box by this fraction of its size on every side")
   own, rest = p.parse_known_args(argv)
   if len(own.resolution) not in (1, 3):
@@ -48,15 +52,22 @@ def parse_flags(argv=None):
   return flags
 
 
-def write_ply(path, xyz, rgb):
-  """ASCII PLY of points (N, 3) with colours (N, 3) in [0, 1]."""
+def write_ply(path, xyz, rgb, normals=None):
+  """ASCII PLY of points (N, 3) with colours (N, 3) in [0, 1] and, when given, normals (N, 3) as nx ny nz."""
   rgb8 = np.clip(np.rint(rgb * 255.0), 0, 255).astype(np.uint8)
   with open(path, 'w') as f:
     f.write('ply\nformat ascii 1.0\n')
     f.write(f'element vertex {len(xyz)}\n')
-    f.write('property float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n')
-    for (x, y, z), (r, g, b) in zip(xyz, rgb8):
-      f.write(f'{x:.6f} {y:.6f} {z:.6f} {r} {g} {b}\n')
+    f.write('property float x\nproperty float y\nproperty float z\n')
+    if normals is not None:
+      f.write('property float nx\nproperty float ny\nproperty float nz\n')
+    f.write('property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n')
+    if normals is None:
+      for (x, y, z), (r, g, b) in zip(xyz, rgb8):
+        f.write(f'{x:.6f} {y:.6f} {z:.6f} {r} {g} {b}\n')
+    else:
+      for (x, y, z), (nx, ny, nz), (r, g, b) in zip(xyz, normals, rgb8):
+        f.write(f'{x:.6f} {y:.6f} {z:.6f} {nx:.6f} {ny:.6f} {nz:.6f} {r} {g} {b}\n')
 
 
 def main(argv=None):
@@ -96,8 +107,16 @@ def main(argv=None):
   pad = flags.margin * (hi - lo)
   lo, hi = lo - pad, hi + pad
   res = tuple(flags.resolution * 3 if len(flags.resolution) == 1 else flags.resolution)
-  sigma = evaluation.density_grid(model, target, lo, hi, res, level=flags.level, warp_id=warp_id,
-                                  appearance_id=app_id if model.use_alpha_condition else None, warp_extra=state.warp_extra)
+  alpha_app = app_id if model.use_alpha_condition else None
+  normals, normals_npy = None, None
+  if flags.normals:   # the same sigma bits as density_grid, and the normals of the same voxels
+    sigma, normals = evaluation.normal_grid(model, target, lo, hi, res, level=flags.level, warp_id=warp_id, appearance_id=alpha_app,
+                                            warp_extra=state.warp_extra)
+    normals_npy = os.path.join(exp_dir, f'normals_{name}.npy')
+    np.save(normals_npy, np.ascontiguousarray(normals.cpu().numpy()))
+  else:
+    sigma = evaluation.density_grid(model, target, lo, hi, res, level=flags.level, warp_id=warp_id, appearance_id=alpha_app,
+                                    warp_extra=state.warp_extra)
   grid = sigma.cpu().numpy()
   npy = os.path.join(exp_dir, f'density_{name}.npy')
   np.save(npy, np.ascontiguousarray(grid))
@@ -120,10 +139,14 @@ def main(argv=None):
       parts.append(out['rgb'])
     rgb = torch.cat(parts, 0)
   ply = os.path.join(exp_dir, f'density_{name}.ply')
-  write_ply(ply, centres.cpu().numpy(), rgb.cpu().numpy())
+  write_ply(ply, centres.cpu().numpy(), rgb.cpu().numpy(),
+            None if normals is None else normals[idx[:, 0], idx[:, 1], idx[:, 2]].cpu().numpy())
   print(f'density_{name}: {res[0]} x {res[1]} x {res[2]} voxels over [{lo.round(4).tolist()}, {hi.round(4).tolist()}], sigma in '
         f'[{grid.min():.4g}, {grid.max():.4g}], {idx.shape[0]} voxels over {flags.threshold:g} -> {npy}, {ply}', flush=True)
-  return {'npy': npy, 'ply': ply, 'resolution': res, 'num_vertices': int(idx.shape[0]), 'bbox': (lo, hi)}
+  ret = {'npy': npy, 'ply': ply, 'resolution': res, 'num_vertices': int(idx.shape[0]), 'bbox': (lo, hi)}
+  if normals_npy is not None:
+    ret['normals_npy'] = normals_npy
+  return ret
 
 
 if __name__ == '__main__':

@@ -1,0 +1,388 @@
+"""Gradient queries on the GPU (nrf_query_points_grad / nrf_query_grid_grad): d sigma / d x against the float64 oracle's autograd,
+sigma and the warped points bit for bit against the density-only query, the normals' documented formula bit for bit, a row that
+does not depend on its launch, the grid, a gradient query next to a stashed training call and the Python surface down to
+scripts/export_density.py --normals.
+
+Oracle parity.  A ReLU network's gradient jumps where a pre-activation crosses zero, and float32 and float64 can land on different
+sides.  A row is therefore left out iff, IN THE FLOAT64 ORACLE ALONE, some trunk or warp-trunk pre-activation of that row has
+|pre| < 1e-5 x that layer's max-abs over the case (the rgb branch does not count; the GPU result plays no part).  At most 15 % of a
+case's rows may be left out (checked per case, on the CPU side of the test).  On the kept rows the statistic is the max error over
+rows / the max-abs of the reference gradient, held to 4 x the same statistic of the oracle evaluated in float32 on the same rows
+(the rule helpers.D_RAW_TOL documents).  Every case prints the GPU figure, the float32 figure, the bound and the share left out."""
+import os
+import sys
+from fractions import Fraction
+
+import numpy as np
+import pytest
+import torch
+
+import helpers as H
+from oracle import nerfies_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHAPES = ((3, 37), (70, 1), (2, 64))   # a ragged last tile with group boundaries inside; a new group on every row; group == tile
+BOX = 1.3
+ALPHA = 3.25
+KINK = 1e-5        # a row within this share of a layer's max-abs of a ReLU kink is left out
+MAX_LEFT_OUT = 0.15
+SEED = 14
+
+_WARP = dict(use_warp=True, num_warp_freqs=6)
+MODELS = {
+    'b_no_condition': dict(use_viewdirs=False),
+    'c_alpha_condition': dict(use_appearance_metadata=True, use_alpha_condition=True),
+    'd_narrow': dict(nerf_trunk_width=128, nerf_rgb_branch_width=64),
+    'f_skip5': dict(nerf_skips=(5,)),
+    'g_se3': dict(_WARP),
+    'i_translation': dict(_WARP, warp_field_type='translation'),
+    # the skip layer is the LAST trunk layer: the reverse chain's d-posenc section meets it at its first step (dpre_7)
+    'j_skip7': dict(nerf_skips=(7,)),
+    'k_alpha_condition_skip7': dict(use_appearance_metadata=True, use_alpha_condition=True, nerf_skips=(7,)),
+}
+_PARAMS, _GPU, _REF = {}, {}, {}
+
+
+def _params(name, **more):
+  """(spec, float32-rounded oracle tree in float64): no GPU."""
+  key = (name, tuple(sorted(more.items())))
+  if key not in _PARAMS:
+    spec = O.ModelSpec(**MODELS[name], **more)
+    p = O.init_params(spec, seed=SEED, trained_like=True)
+    _PARAMS[key] = (spec, p, O.tree_map(lambda t: t.float().double() if t.is_floating_point() else t, p))
+  return _PARAMS[key]
+
+
+def _model(name, **more):
+  key = (name, tuple(sorted(more.items())))
+  if key not in _GPU:
+    spec, p, _ = _params(name, **more)
+    _GPU[key] = H.gpu_model(spec, p)
+  return _GPU[key]
+
+
+def _inputs(spec, G, S, seed):
+  """float32 points in the samples' box, unit view directions and ids, one row per group (test_gpu_field_query.py _inputs)."""
+  g = torch.Generator().manual_seed(seed)
+  pts = ((torch.rand(G, S, 3, generator=g) * 2 - 1) * BOX).float()
+  vd = torch.randn(G, 3, generator=g)
+  vd = (vd / vd.norm(dim=-1, keepdim=True)).float()
+  md = {'warp': torch.randint(0, spec.num_warp_embeddings, (G, 1), generator=g),
+        'appearance': torch.randint(0, spec.num_appearance_embeddings, (G, 1), generator=g),
+        'camera': torch.randint(0, spec.num_camera_embeddings, (G, 1), generator=g)}
+  return pts, vd, md
+
+
+def _md_names(spec, use_warp):
+  names = []
+  if spec.use_warp and use_warp:
+    names.append('warp')
+  if spec.use_appearance_metadata:
+    names.append('appearance')
+  return names
+
+
+def _oracle_grad(p, spec, level, pts, vd, md, warp_on, dtype):
+  """sigma (G, S), d sigma / d points (G, S, 3) by autograd, and per row the smallest |pre| / layer max-abs over the trunk and
+  warp-trunk layers, from the oracle's own pieces in `dtype` (test_gpu_field_query.py _oracle, with the pre-activations read
+  through O.relu_hook)."""
+  cast = lambda t: t.to(dtype) if t.is_floating_point() else t
+  p = O.tree_map(cast, p)
+  x0 = pts.to(dtype).clone().requires_grad_(True)
+  md = {k: cast(v) for k, v in md.items()}
+  G, S = pts.shape[:2]
+  margin = torch.full((G * S,), float('inf'), dtype=torch.float64)
+
+  def hook(name, layer, pre):
+    nonlocal margin
+    if name.endswith('MLP_0') or name.endswith('warp'):
+      a = pre.detach().double().abs().reshape(G * S, -1)
+      margin = torch.minimum(margin, a.min(dim=1).values / a.max())
+    return torch.relu(pre)
+
+  alpha_c, rgb_c = O.get_condition_inputs(p, spec, vd.to(dtype), md, False)
+  with O.relu_hook(hook):
+    x = x0
+    if warp_on:
+      wm = md['warp'][:, None, :].expand(G, S, 1)
+      x = O.se3_field(p['warp_field'], x0, wm, ALPHA, spec.num_warp_freqs, False, False, name='q/warp')['warped_points']
+    _, raw_alpha = O.nerf_mlp(p[f'nerf_mlps_{level}'], O.sinusoidal_encode(x, spec.num_nerf_point_freqs), alpha_c, rgb_c, spec, name='q')
+  sigma = O._sigma_act(spec.sigma_activation, raw_alpha[..., 0])
+  (grad,) = torch.autograd.grad(sigma.sum(), x0)   # rows are independent: the gradient of the sum is every row's own gradient
+  return sigma.detach(), grad.detach(), margin.reshape(G, S), (x.detach() if warp_on else None)
+
+
+def reference_case(name, level, G, S, use_warp=True):
+  """The float64 reference, the float32 oracle and the kept rows of one case: CPU only, computed once."""
+  key = (name, level, G, S, use_warp)
+  if key not in _REF:
+    spec, _, p = _params(name)
+    warp_on = spec.use_warp and use_warp
+    pts, vd, md = _inputs(spec, G, S, seed=1000 * G + S)
+    s64, g64, margin, _ = _oracle_grad(p, spec, level, pts, vd, md, warp_on, torch.float64)
+    _, g32, _, _ = _oracle_grad(p, spec, level, pts, vd, md, warp_on, torch.float32)
+    keep = margin >= KINK
+    scale = float(g64[keep].abs().max())
+    floor = float((g32.double() - g64)[keep].abs().max()) / scale
+    _REF[key] = dict(pts=pts, md=md, sigma=s64, grad=g64, keep=keep, scale=scale, floor=floor, left_out=1.0 - float(keep.double().mean()))
+  return _REF[key]
+
+
+def _query(name, level, pts, md, use_warp=True, outputs=('sigma', 'grad_sigma', 'normals'), **more):
+  spec, _, _ = _params(name, **more)
+  model, fp = _model(name, **more)
+  mdg = {k: md[k].to(H.DEV) for k in _md_names(spec, use_warp)}
+  return model.query_gradient(fp, pts.to(H.DEV), metadata=mdg, warp_extra={'alpha': ALPHA}, level=level, use_warp=use_warp, outputs=outputs)
+
+
+CASES = [(n, True) for n in sorted(MODELS)] + [('g_se3', False)]
+
+
+@pytest.mark.parametrize('name,use_warp', CASES, ids=[n + ('' if w else '-no_warp') for n, w in CASES])
+def test_oracle_parity(name, use_warp):
+  spec, _, _ = _params(name)
+  model, fp = _model(name)
+  warp_on = spec.use_warp and use_warp
+  rows = []
+  for level in ('coarse', 'fine'):
+    for G, S in SHAPES:
+      ref = reference_case(name, level, G, S, use_warp)
+      assert ref['left_out'] <= MAX_LEFT_OUT, (name, level, G, S, ref['left_out'])
+      outputs = ('sigma', 'grad_sigma', 'normals') + (('warped_points',) if warp_on else ())
+      got = _query(name, level, ref['pts'], ref['md'], use_warp, outputs)
+      mdg = {k: ref['md'][k].to(H.DEV) for k in _md_names(spec, use_warp)}
+      dens = model.query_points(fp, ref['pts'].to(H.DEV), metadata=mdg, warp_extra={'alpha': ALPHA}, level=level, use_warp=use_warp,
+                                outputs=('sigma',) + (('warped_points',) if warp_on else ()))
+      assert tuple(got['grad_sigma'].shape) == (G, S, 3) and tuple(got['sigma'].shape) == (G, S)
+      assert torch.equal(got['sigma'], dens['sigma']), (name, level, G, S)              # every row, bit for bit
+      if warp_on:
+        assert torch.equal(got['warped_points'], dens['warped_points']), (name, level, G, S)
+      assert torch.isfinite(got['grad_sigma']).all()
+      err = float((got['grad_sigma'].cpu().double() - ref['grad'])[ref['keep']].abs().max()) / ref['scale']
+      rows.append((level, G, S, err, ref['floor'], ref['left_out']))
+  tag = name + ('' if use_warp else ' NO_WARP')
+  for level, G, S, err, floor, out in rows:
+    print(f'[field gradient parity] {tag:22s} {level:6s} ({G:2d},{S:2d}) gpu {err:.3e}  float32 oracle {floor:.3e}  bound {4 * floor:.3e}  '
+          f'left out {100 * out:.1f} %')
+  for level, G, S, err, floor, out in rows:
+    assert err <= 4.0 * floor, (tag, level, G, S, err, floor)
+
+
+# ---- the normals' documented formula on the host, every step rounded once to float32 ----
+def _round32(t):
+  """The float32 nearest to the exact rational t, ties to even (no double rounding through float64)."""
+  f = np.float32(float(t))
+  best = None
+  for c in (np.nextafter(f, np.float32(-np.inf)), f, np.nextafter(f, np.float32(np.inf))):
+    if not np.isfinite(c):
+      continue
+    d = abs(Fraction(float(c)) - t)
+    even = (int(np.array(c, dtype=np.float32).view(np.uint32)) & 1) == 0
+    if best is None or d < best[0] or (d == best[0] and even):
+      best = (d, c)
+  return best[1]
+
+
+def host_normals(g):
+  """s = fmaf(g.z, g.z, fmaf(g.y, g.y, g.x * g.x)); inv = 1 / sqrtf(s); n_c = -(g_c * inv); 0 where s is 0 or not finite."""
+  g = np.asarray(g, dtype=np.float32).reshape(-1, 3)
+  out = np.zeros_like(g)
+  for r, (x, y, z) in enumerate(g):
+    if not np.isfinite([x, y, z]).all():
+      continue
+    fx, fy, fz = Fraction(float(x)), Fraction(float(y)), Fraction(float(z))
+    big = Fraction(float(np.finfo(np.float32).max)) + Fraction(2) ** 103   # at or beyond: rounds to infinity
+    s = fx * fx
+    s = Fraction(float(_round32(s))) if s < big else None
+    s = None if s is None or fy * fy + s >= big else Fraction(float(_round32(fy * fy + s)))
+    s = None if s is None or fz * fz + s >= big else _round32(fz * fz + s)
+    if s is None or not s > 0:
+      continue
+    with np.errstate(all='ignore'):
+      inv = np.float32(1) / np.sqrt(np.float32(s))           # both correctly rounded in float32
+      out[r] = -(g[r] * inv)
+  return out
+
+
+def test_normals_are_the_documented_formula():
+  for name, level, (G, S) in (('b_no_condition', 'fine', (3, 37)), ('g_se3', 'coarse', (2, 64))):
+    ref = reference_case(name, level, G, S)
+    got = _query(name, level, ref['pts'], ref['md'])
+    g = got['grad_sigma'].cpu().numpy().reshape(-1, 3)
+    n = got['normals'].cpu().numpy().reshape(-1, 3)
+    want = host_normals(g)
+    assert np.array_equal(n.view(np.uint32), want.view(np.uint32)), (name, np.abs(n - want).max())
+    norm = np.sqrt((n.astype(np.float64) ** 2).sum(-1))
+    zero = (n == 0).all(-1)
+    assert (np.abs(norm[~zero] - 1.0) <= 4 * np.finfo(np.float32).eps).all() and (~zero).any(), (name, norm)
+    assert (np.sign(n[~zero]) == -np.sign(g[~zero])).all()       # pointing down the density's slope
+
+
+@pytest.mark.parametrize('name', ['b_no_condition', 'c_alpha_condition', 'g_se3'])
+def test_a_dead_alpha_head_gives_zero_gradients_and_zero_normals(name):
+  """w_alpha[0:256] = 0: the density no longer depends on the point.  b: the head's own term of the reverse chain; c: the
+  use_alpha_condition path (d bn = ds (x) 0, then the W_bn^T step; the appearance rows of the head keep their weights); g: the same
+  zero through J^T.  Exact zeros, no NaN."""
+  spec, p, _ = _params(name)
+  p0 = O.tree_map(lambda t: t.clone(), p)
+  for level in ('coarse', 'fine'):
+    p0[f'nerf_mlps_{level}']['MLP_2']['logit']['kernel'][:spec.nerf_trunk_width].zero_()
+  model, fp = H.gpu_model(spec, p0)
+  pts, _, md = _inputs(spec, 3, 37, seed=5)
+  mdg = {k: md[k].to(H.DEV) for k in _md_names(spec, True)}
+  for level in ('coarse', 'fine'):
+    got = model.query_gradient(fp, pts.to(H.DEV), metadata=mdg, warp_extra={'alpha': ALPHA}, level=level)
+    assert torch.isfinite(got['sigma']).all() and float(got['sigma'].min()) > 0          # softplus of the head's bias (+ code term): no slope
+    assert bool((got['grad_sigma'] == 0).all()) and bool((got['normals'] == 0).all()), (name, level)
+    assert not torch.isnan(got['normals']).any() and not torch.isnan(got['grad_sigma']).any()
+  if name == 'c_alpha_condition':   # the density still follows the appearance code
+    other = {'appearance': (mdg['appearance'] + 1) % spec.num_appearance_embeddings}
+    assert not torch.equal(model.query_gradient(fp, pts.to(H.DEV), metadata=other, outputs=('sigma',))['sigma'], got['sigma'])
+
+
+@pytest.mark.parametrize('name', ['c_alpha_condition', 'g_se3'])
+def test_a_row_does_not_depend_on_its_launch(name):
+  spec, _, _ = _params(name)
+  ref = reference_case(name, 'fine', 3, 37)
+  outputs = ('sigma', 'grad_sigma', 'normals')
+  whole = _query(name, 'fine', ref['pts'], ref['md'], outputs=outputs)
+  again = _query(name, 'fine', ref['pts'], ref['md'], outputs=outputs)     # the same workspace
+  for k in outputs:
+    assert torch.equal(whole[k], again[k]), (name, k)
+  for g, s in ((0, 0), (1, 20), (2, 36)):
+    one = _query(name, 'fine', ref['pts'][g:g + 1, s:s + 1], {k: v[g:g + 1] for k, v in ref['md'].items()}, outputs=outputs)
+    for k in outputs:
+      assert torch.equal(one[k][0, 0], whole[k][g, s]), (name, k, g, s)
+
+
+@pytest.mark.parametrize('name', ['b_no_condition', 'g_se3'])
+def test_grid(name):
+  from nerfies_amd import evaluation
+  spec, _, _ = _params(name)
+  model, fp = _model(name)
+  dims = (5, 3, 7)
+  lo, hi = (-0.9, -0.35, 0.1), (0.6, 0.55, 1.15)
+  step = [(h - l) / r for l, h, r in zip(lo, hi, dims)]
+  origin = [l + 0.5 * s for l, s in zip(lo, step)]
+  n = torch.arange(105)
+  idx = torch.stack([n % 5, (n // 5) % 3, n // 15], -1).float()
+  pts = torch.tensor(origin, dtype=torch.float32) + idx * torch.tensor(step, dtype=torch.float32)   # fl(origin + fl(idx * step))
+  warp_id = 2 if spec.use_warp else None
+  md = {'warp': torch.tensor([[warp_id]], dtype=torch.int32, device=H.DEV)} if spec.use_warp else {}
+  kw = dict(metadata=md, warp_extra={'alpha': ALPHA}, level='fine')
+  keys = ('sigma', 'grad_sigma', 'normals')
+  ref = model.query_gradient(fp, pts.to(H.DEV)[None], outputs=keys, **kw)
+  new = lambda c: {'sigma': torch.empty(c, device=H.DEV), 'grad_sigma': torch.empty(c, 3, device=H.DEV), 'normals': torch.empty(c, 3, device=H.DEV)}
+  parts = [model.query_grid_gradient(fp, origin, step, dims, first, count, new(count), workspace_points=32, **kw)
+           for first, count in evaluation.grid_chunks(105, 32)]
+  for k in keys:
+    assert torch.equal(torch.cat([q[k] for q in parts]), ref[k][0]), (name, k)
+  for chunk in (1 << 20, 32):
+    sigma, normals = evaluation.normal_grid(model, fp, lo, hi, dims, level='fine', warp_id=warp_id, warp_extra={'alpha': ALPHA}, chunk=chunk)
+    assert tuple(sigma.shape) == dims and sigma.stride() == (1, 5, 15) and tuple(normals.shape) == dims + (3,) and normals.is_cuda
+    assert torch.equal(sigma.permute(2, 1, 0).reshape(-1), ref['sigma'][0])
+    assert torch.equal(normals.permute(2, 1, 0, 3).reshape(-1, 3), ref['normals'][0])
+    dens = evaluation.density_grid(model, fp, lo, hi, dims, level='fine', warp_id=warp_id, warp_extra={'alpha': ALPHA}, chunk=chunk)
+    assert torch.equal(dens, sigma)
+
+
+def test_a_gradient_query_leaves_a_stashed_training_call_alone():
+  more = dict(num_coarse_samples=16, num_fine_samples=16)
+  spec, _, _ = _params('g_se3', **more)
+  model, fp = _model('g_se3', **more)
+  B = 37
+  gb = H.gpu_batch(O.synthetic_batch(B, seed=8, dtype=torch.float32))
+  gen = torch.Generator().manual_seed(3)
+  d_c, d_f = torch.randn(B, 3, generator=gen).to(H.DEV), torch.randn(B, 3, generator=gen).to(H.DEV)
+  pts, _, md = _inputs(spec, 3, 37, seed=2)
+
+  def run(with_query):
+    out = model.apply(fp, gb, {'alpha': ALPHA}, train=True)
+    rgb = out['fine']['rgb'].clone()
+    if with_query:
+      q = model.query_gradient(fp, pts.to(H.DEV), metadata={'warp': md['warp'].to(H.DEV)}, warp_extra={'alpha': 1.5}, level='coarse',
+                               outputs=('sigma', 'grad_sigma', 'normals', 'warped_points'))
+      assert torch.isfinite(q['grad_sigma']).all()
+      model.query_gradient(fp, pts.to(H.DEV), warp_extra={'alpha': 1.5}, use_warp=False)
+    return rgb, model.backward(fp, gb, d_c, d_f).clone()
+
+  rgb0, g0 = run(False)
+  rgb1, g1 = run(True)
+  rgb2, g2 = run(False)
+  assert torch.equal(rgb0, rgb1) and float(g0.abs().max()) > 0
+  # float atomics in the ray path's per-ray sums: two plain runs need not agree bitwise either; the query must move nothing beyond that
+  tol = 1e-6 * float(g0.abs().max())
+  print(f'[field gradient / stash] max |g_query - g_plain| {float((g1 - g0).abs().max()):.3e}, plain rerun {float((g2 - g0).abs().max()):.3e}, tol {tol:.3e}')
+  assert float((g1 - g0).abs().max()) <= tol
+
+
+def test_python_surface():
+  from nerfies_amd import lib as L
+  spec, _, _ = _params('g_se3')
+  model, fp = _model('g_se3')
+  pts, _, md = _inputs(spec, 6, 5, seed=4)
+  mdg = {'warp': md['warp'].to(H.DEV)}
+  kw = dict(warp_extra={'alpha': ALPHA})
+  one = model.query_gradient(fp, pts[0].to(H.DEV), metadata={'warp': mdg['warp'][:1]}, **kw)            # (N, 3): one group
+  assert set(one) == {'sigma', 'grad_sigma', 'normals'}
+  assert tuple(one['sigma'].shape) == (5,) and tuple(one['grad_sigma'].shape) == (5, 3) and tuple(one['normals'].shape) == (5, 3)
+  gs = model.query_gradient(fp, pts.to(H.DEV), metadata=mdg, outputs=('sigma', 'grad_sigma', 'normals', 'warped_points'), **kw)
+  assert tuple(gs['sigma'].shape) == (6, 5) and all(tuple(gs[k].shape) == (6, 5, 3) for k in ('grad_sigma', 'normals', 'warped_points'))
+  assert torch.equal(gs['grad_sigma'][0], one['grad_sigma']) and torch.equal(gs['sigma'][0], one['sigma'])
+  lead = model.query_gradient(fp, pts.reshape(2, 3, 5, 3).to(H.DEV), metadata={'warp': mdg['warp'].reshape(2, 3, 1)}, **kw)
+  assert tuple(lead['sigma'].shape) == (2, 3, 5) and tuple(lead['normals'].shape) == (2, 3, 5, 3)
+  assert torch.equal(lead['grad_sigma'].reshape(6, 5, 3), gs['grad_sigma'])
+  only = model.query_gradient(fp, pts.to(H.DEV), metadata=mdg, outputs=('normals',), **kw)
+  assert set(only) == {'normals'} and torch.equal(only['normals'], gs['normals'])
+  with pytest.raises(L.NrfError, match='outputs'):
+    model.query_gradient(fp, pts.to(H.DEV), metadata=mdg, outputs=('rgb',), **kw)
+  with pytest.raises(L.NrfError, match='GPU'):
+    model.query_gradient(fp, pts, metadata=mdg, **kw)
+  with pytest.raises(L.NrfError, match='warped_points'):
+    model.query_gradient(fp, pts.to(H.DEV), use_warp=False, outputs=('warped_points',), **kw)
+
+
+def test_export_density_with_normals_end_to_end(tmp_path):
+  sys.path.insert(0, ROOT)
+  sys.path.insert(0, os.path.join(ROOT, 'scripts'))
+  import train as train_driver
+  import export_density
+  from test_gpu_field_query import GIN
+  from nerfies_amd import datasets, gin_lite as gin
+  cap, exp = str(tmp_path / 'cap'), str(tmp_path / 'exp')
+  datasets.write_synthetic_scene(cap, num_frames=8, size=(24, 16))
+  cfg = tmp_path / 'run.gin'
+  cfg.write_text(GIN)
+  args = ['--base_folder', exp, '--data_dir', cap, '--gin_configs', str(cfg)]
+  gin.clear_config()
+  train_driver.main(args)
+  for extra, name in ((['--frame', '000002'], '000002'), (['--canonical'], 'canonical')):
+    common = args + extra + ['--resolution', '8']
+    gin.clear_config()
+    probe = export_density.main(common + ['--threshold', '1e30'])
+    assert probe['num_vertices'] == 0 and 'normals_npy' not in probe
+    grid = np.load(probe['npy'])
+    plain_ply = open(probe['ply']).read()
+    assert 'property float nx' not in plain_ply and not os.path.exists(os.path.join(exp, f'normals_{name}.npy'))
+    thr = float(np.sort(grid.ravel())[grid.size // 2])
+    gin.clear_config()
+    res = export_density.main(common + ['--threshold', repr(thr), '--normals'])
+    assert np.array_equal(np.load(res['npy']), grid)                 # the same sigma bits with and without the flag
+    normals = np.load(res['normals_npy'])
+    assert res['normals_npy'] == os.path.join(exp, f'normals_{name}.npy')
+    assert normals.shape == (8, 8, 8, 3) and normals.dtype == np.float32 and np.isfinite(normals).all()
+    norm = np.sqrt((normals.astype(np.float64) ** 2).sum(-1))
+    assert (np.abs(norm - 1.0) <= 4 * np.finfo(np.float32).eps)[norm > 0].all() and (norm > 0).any()
+    want = int((grid > thr).sum())
+    lines = open(res['ply']).read().splitlines()
+    head = lines[:lines.index('end_header')]
+    assert f'element vertex {want}' in head and 0 < want < grid.size
+    props = [l.split()[-1] for l in head if l.startswith('property')]
+    assert props == ['x', 'y', 'z', 'nx', 'ny', 'nz', 'red', 'green', 'blue']
+    body = np.array([[float(v) for v in l.split()] for l in lines[lines.index('end_header') + 1:]])
+    assert body.shape == (want, 9)
+    ijk = np.argwhere(grid > thr)
+    assert np.allclose(body[:, 3:6], normals[ijk[:, 0], ijk[:, 1], ijk[:, 2]], atol=1e-6)
+  gin.clear_config()
