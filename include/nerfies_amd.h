@@ -563,6 +563,70 @@ int nrf_query_grid_grad(nrf_handle h, const float* params, const nrf_rays* group
                         int32_t level, const nrf_step_scalars* scalars, uint32_t flags, const nrf_field_grad_out* out, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---- Mesh extraction: a triangle mesh of the level set sigma = threshold of a device density grid (surface nets) ----
+ * Handle-free, like the camera tables: the grid may come from nrf_query_grid or from anywhere.  An indexed mesh with shared
+ * vertices, the same bits on every run (no atomic, no claimed slot: every output position is a rank in the order below).
+ * Announced by NRF_HAS_MESH (NRF_VERSION is unchanged).
+ *
+ * sigma: float32 DEVICE array laid out as `grid` lays it out: sample n has i = n % X, j = (n / X) % Y, k = n / (X Y)
+ * (X, Y, Z = grid->dims) and sits at origin + idx * step.
+ * Inside: a sample is inside iff sigma > threshold (strict: a NaN sample is outside).
+ * Cells: cell (i, j, k), 0 <= i < X-1 (likewise j, k), has the corners (i+di, j+dj, k+dk), corner bit b = di + 2 dj + 4 dk; it is
+ *   ACTIVE iff its 8 corners are neither all inside nor all outside.  Its linear index is i + (X-1) (j + (Y-1) k).
+ * Vertices: one per active cell; the vertex index is the cell's rank among the active cells in linear order.
+ * Position, in float32, one rounding per operation, nothing contracted:
+ *   walk the 12 cell edges in the order corner a ascending, axis ascending; an edge runs from a to b = a | (1 << axis); take it where
+ *   bit `axis` of a is 0 and the two ends differ in insideness.  t = (threshold - s_a) / (s_b - s_a), 0.5 if that is not finite,
+ *   else clamped to [0, 1].  The crossing in cell-local coordinates is corner a's offset (di, dj, dk) with t added on `axis`.
+ *   local = (the sum of the crossings, added in that order, per axis) / (float)(their count), and
+ *   vertex_c = ((float)idx_c + local_c) * step_c + origin_c: one sum, one product, one sum.
+ * Faces: for a cell c and an axis ax in the order x, y, z, with u = (ax+1) % 3 and v = (ax+2) % 3: if c[u] >= 1, c[v] >= 1 and the
+ *   samples at c and at c + e_ax differ in insideness, the quad of the vertices of the cells c - e_u - e_v, c - e_v, c, c - e_u, in
+ *   that order, reversed when the sample at c is outside, split as (q0, q1, q2), (q0, q2, q3).  Faces are ordered by the owner cell's
+ *   linear index, then by axis.  Normals (counter-clockwise faces) point from high density to low; a surface that leaves the grid's
+ *   box stays open there.  An all-outside (or all-inside) grid is no error: 0 vertices, 0 triangles.
+ *
+ * Every refusal is decided before any HIP call and names the entry and the rule in nrf_last_error: a NULL pointer (NRF_E_NULL), a
+ * dimension below 2, more than NRF_MESH_MAX_CELLS cells, a non-finite threshold, a negative capacity or count (NRF_E_SHAPE), a
+ * workspace that is short (NRF_E_WORKSPACE) or not 16-byte aligned.  Asynchronous on `stream`, nothing allocated or synchronised. */
+#define NRF_HAS_MESH 1
+/* Cells of a grid, (X-1)(Y-1)(Z-1).  Sized by the largest index the entries form in int32: a cell owns at most 3 quads = 6
+ * triangles, so triangle indices stay below 6 * 2^28 < 2^31 (and samples, X Y Z <= 8 cells, at or below 2^31 - 1 as well). */
+#define NRF_MESH_MAX_CELLS (1 << 28)
+
+/* The first 16 bytes of a mesh workspace after nrf_mesh_count / nrf_mesh_emit ran (DEVICE memory; the caller may copy them). */
+typedef struct nrf_mesh_status {
+  int32_t num_vertices;       /* what nrf_mesh_count found (also in its `counts`) */
+  int32_t num_triangles;
+  int32_t emitted_vertices;   /* what the last nrf_mesh_emit wrote: the two totals, or 0 and 0 when a capacity was short */
+  int32_t emitted_triangles;
+} nrf_mesh_status;
+
+/* Bytes of workspace for a grid of these dims (about 5 bytes per cell: a corner mask and the cell-to-vertex map).  Needs no GPU. */
+int nrf_mesh_workspace_bytes(const nrf_grid* grid, size_t* bytes);
+
+/* Classifies the cells and scans the totals: counts[0] = vertices, counts[1] = triangles (two DEVICE int32).  The caller reads them
+ * and allocates; the library allocates nothing.  The workspace then serves nrf_mesh_emit for the same sigma, grid and threshold. */
+int nrf_mesh_count(const float* sigma, const nrf_grid* grid, float threshold, int32_t* counts, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
+/* vertices (V,3) float32, vertex_cell (V,) int32 (each vertex's linear cell index), triangles (F,3) int32, from the workspace
+ * nrf_mesh_count filled for the same sigma, grid and threshold.  The capacities (in vertices / triangles) are held against the
+ * scanned totals ON THE DEVICE: when either is short, nothing at all is written to the three buffers and
+ * nrf_mesh_status.emitted_* become 0; otherwise they become the totals.  No write ever lands at or past a capacity.  A buffer
+ * may be NULL where its capacity is 0.  The cell-to-vertex map (int32 per cell, -1 if inactive) is left in the workspace. */
+int nrf_mesh_emit(const float* sigma, const nrf_grid* grid, float threshold, int32_t max_vertices, int32_t max_triangles, float* vertices,
+                  int32_t* vertex_cell, int32_t* triangles, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One Newton step of every vertex onto the level set, in place, from the field's own density sigma_at (V,) and gradient grad_at
+ * (V,3) at the vertices (nrf_query_points_grad):
+ *   s = fmaf(g.z, g.z, fmaf(g.y, g.y, g.x * g.x)),  q = (sigma - threshold) / s,  x_c = fmaf(-q, g_c, x_c),
+ * then each coordinate is clamped to its own cell's box [origin_c + (float)i_c * step_c, origin_c + (float)(i_c + 1) * step_c]
+ * (i = the cell of vertex_cell; a NaN coordinate lands on the lower end): the mesh keeps its topology and cannot fold across
+ * cells.  The vertex is unchanged where s is 0 or not finite, or where sigma is not finite.  num_vertices == 0 is a no-op. */
+int nrf_mesh_snap(float* vertices, const int32_t* vertex_cell, const float* sigma_at, const float* grad_at, const nrf_grid* grid,
+                  float threshold, int32_t num_vertices, void* stream);
+
 /* flax.optim.Adam.apply_gradient (training.py:268-269; flax 0.3.4 optim/adam.py):
  * g = grad*grad_scale (grad_scale = 1/world_size folds lax.pmean, training.py:266),
  * m,v updated in place, step = number of updates already applied.  Hyper-parameters are doubles

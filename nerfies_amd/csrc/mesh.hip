@@ -1,0 +1,471 @@
+// Surface nets on a device density grid (nrf_mesh_count / nrf_mesh_emit / nrf_mesh_snap; the definition is in
+// include/nerfies_amd.h): an indexed, deterministic triangle mesh of the level set sigma = threshold.
+//
+// Cells are walked in their linear order, i fastest: a workgroup of 256 threads owns MESH_BLOCK_CELLS = 1024 consecutive cells as
+// four rounds of 256, so the 64 lanes of a wave read consecutive x (the eight corner reads of a wave are eight runs of 65 floats,
+// but for the rows that end inside the wave) and the neighbours' re-reads hit the cache.  Every output slot is a rank: the number of
+// active cells (quads) before this one in that order = scanned workgroup total + the totals of the (round, wave) pairs before this
+// wave + the popcount of the wave's ballot below this lane.  No atomic, no flag another workgroup waits on: classify stores
+// per-workgroup totals, a one-workgroup kernel scans them, the emit kernels read the scan.
+//
+// Every float operation below is a single rounding in the order the header states: contraction is off for the whole file.
+#include "nrf_handle.h"
+
+#include <cmath>
+
+#pragma clang fp contract(off)
+
+using namespace nrf;
+using namespace nrf::api;
+
+namespace {
+
+constexpr int MESH_THREADS = 256;
+constexpr int MESH_WAVES = MESH_THREADS / 64;
+constexpr int MESH_ROUNDS = 4;
+constexpr int MESH_BLOCK_CELLS = MESH_THREADS * MESH_ROUNDS;
+constexpr int MESH_SLOTS = MESH_ROUNDS * MESH_WAVES;   // (round, wave) pairs of a workgroup, in cell order
+constexpr int SCAN_THREADS = 1024;
+constexpr size_t MESH_HEADER_BYTES = 256;              // nrf_mesh_status, padded
+constexpr size_t MESH_ALIGN = 256;
+
+struct MeshDims {
+  int X, Y, Z;      // samples
+  int cx, cy, cz;   // cells
+  int ncells;
+  int nblocks;      // workgroups of MESH_BLOCK_CELLS cells
+};
+
+// byte offsets of the workspace's regions
+struct MeshPlan {
+  size_t block_v, block_q, mask, map, total;
+};
+
+MeshDims mesh_dims(const nrf_grid* g) {
+  MeshDims d;
+  d.X = g->dims[0]; d.Y = g->dims[1]; d.Z = g->dims[2];
+  d.cx = d.X - 1; d.cy = d.Y - 1; d.cz = d.Z - 1;
+  d.ncells = d.cx * d.cy * d.cz;
+  d.nblocks = (d.ncells + MESH_BLOCK_CELLS - 1) / MESH_BLOCK_CELLS;
+  return d;
+}
+
+MeshPlan mesh_plan(const MeshDims& d) {
+  MeshPlan p;
+  size_t o = MESH_HEADER_BYTES;
+  p.block_v = o; o = align_up(o + sizeof(int) * (size_t)d.nblocks, MESH_ALIGN);
+  p.block_q = o; o = align_up(o + sizeof(int) * (size_t)d.nblocks, MESH_ALIGN);
+  p.mask = o;    o = align_up(o + (size_t)d.ncells, MESH_ALIGN);
+  p.map = o;     o = align_up(o + sizeof(int) * (size_t)d.ncells, MESH_ALIGN);
+  p.total = o;
+  return p;
+}
+
+__device__ __forceinline__ void cell_coords(int cell, const MeshDims& d, int& i, int& j, int& k) {
+  i = cell % d.cx;
+  const int r = cell / d.cx;
+  j = r % d.cy;
+  k = r / d.cy;
+}
+
+__device__ __forceinline__ unsigned long long lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
+
+// the three quads a cell may own, from its corner mask and its position: bit ax set iff the samples at c and c + e_ax differ in
+// insideness and c[u] >= 1, c[v] >= 1 (u = ax + 1, v = ax + 2 mod 3)
+__device__ __forceinline__ unsigned owned_quads(unsigned m, int i, int j, int k) {
+  const unsigned c0 = m & 1u;
+  unsigned q = 0;
+  if ((((m >> 1) & 1u) != c0) && j >= 1 && k >= 1) q |= 1u;
+  if ((((m >> 2) & 1u) != c0) && k >= 1 && i >= 1) q |= 2u;
+  if ((((m >> 4) & 1u) != c0) && i >= 1 && j >= 1) q |= 4u;
+  return q;
+}
+
+// Stage 1: corner mask per cell, per-workgroup totals of active cells and owned quads.
+__global__ __launch_bounds__(MESH_THREADS) void mesh_classify_kernel(const float* __restrict__ sigma, const MeshDims d, const float thr,
+                                                                     unsigned char* __restrict__ mask, int* __restrict__ block_v,
+                                                                     int* __restrict__ block_q) {
+  __shared__ int sv[MESH_SLOTS], sq[MESH_SLOTS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t sy = (size_t)d.X, sz = (size_t)d.X * (size_t)d.Y;
+#pragma unroll
+  for (int r = 0; r < MESH_ROUNDS; ++r) {
+    const int cell = blockIdx.x * MESH_BLOCK_CELLS + r * MESH_THREADS + threadIdx.x;
+    bool active = false;
+    unsigned q = 0;
+    if (cell < d.ncells) {
+      int i, j, k;
+      cell_coords(cell, d, i, j, k);
+      const float* s = sigma + ((size_t)i + sy * (size_t)j + sz * (size_t)k);
+      unsigned m = 0;
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        const float v = s[(size_t)(b & 1) + sy * (size_t)((b >> 1) & 1) + sz * (size_t)(b >> 2)];
+        m |= (v > thr ? 1u : 0u) << b;   // strict: a NaN sample is outside
+      }
+      mask[cell] = (unsigned char)m;
+      active = m != 0u && m != 255u;
+      q = owned_quads(m, i, j, k);
+    }
+    const unsigned long long bv = __ballot(active);
+    const unsigned long long bx = __ballot((q & 1u) != 0u), by = __ballot((q & 2u) != 0u), bz = __ballot((q & 4u) != 0u);
+    if (lane == 0) {
+      sv[r * MESH_WAVES + wave] = __popcll(bv);
+      sq[r * MESH_WAVES + wave] = __popcll(bx) + __popcll(by) + __popcll(bz);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int tv = 0, tq = 0;
+#pragma unroll
+    for (int e = 0; e < MESH_SLOTS; ++e) { tv += sv[e]; tq += sq[e]; }
+    block_v[blockIdx.x] = tv;
+    block_q[blockIdx.x] = tq;
+  }
+}
+
+// Stage 2: exclusive scans of the workgroup totals, in place, by ONE workgroup (each thread a contiguous run); the totals go to the
+// workspace's status words and to the caller's counts.
+__global__ __launch_bounds__(SCAN_THREADS) void mesh_scan_kernel(int* __restrict__ block_v, int* __restrict__ block_q, const int nblocks,
+                                                                 int* __restrict__ status, int* __restrict__ counts) {
+  __shared__ int tv[SCAN_THREADS], tq[SCAN_THREADS];
+  const int t = threadIdx.x;
+  const int per = (nblocks + SCAN_THREADS - 1) / SCAN_THREADS;
+  const long long first = (long long)t * per;
+  const int b0 = first < nblocks ? (int)first : nblocks;
+  const int b1 = b0 + per < nblocks ? b0 + per : nblocks;
+  int mv = 0, mq = 0;
+  for (int b = b0; b < b1; ++b) { mv += block_v[b]; mq += block_q[b]; }
+  tv[t] = mv;
+  tq[t] = mq;
+  __syncthreads();
+  for (int off = 1; off < SCAN_THREADS; off <<= 1) {
+    const int av = t >= off ? tv[t - off] : 0, aq = t >= off ? tq[t - off] : 0;
+    __syncthreads();
+    tv[t] += av;
+    tq[t] += aq;
+    __syncthreads();
+  }
+  int rv = tv[t] - mv, rq = tq[t] - mq;
+  for (int b = b0; b < b1; ++b) {
+    const int v = block_v[b], q = block_q[b];
+    block_v[b] = rv;
+    block_q[b] = rq;
+    rv += v;
+    rq += q;
+  }
+  if (t == SCAN_THREADS - 1) {
+    const int nv = tv[t], nt = 2 * tq[t];
+    status[0] = nv;
+    status[1] = nt;
+    status[2] = 0;
+    status[3] = 0;
+    counts[0] = nv;
+    counts[1] = nt;
+  }
+}
+
+// the vertex of an active cell: the mean of its edge crossings in cell-local coordinates, then (idx + local) * step + origin
+__device__ __forceinline__ void cell_vertex(const float* __restrict__ s, const size_t sy, const size_t sz, const unsigned m, const float thr,
+                                            const int i, const int j, const int k, const nrf_grid& g, float out[3]) {
+  float v[8];
+#pragma unroll
+  for (int b = 0; b < 8; ++b) v[b] = s[(size_t)(b & 1) + sy * (size_t)((b >> 1) & 1) + sz * (size_t)(b >> 2)];
+  float ax = 0.f, ay = 0.f, az = 0.f;
+  int count = 0;
+#pragma unroll
+  for (int a = 0; a < 8; ++a) {
+#pragma unroll
+    for (int axis = 0; axis < 3; ++axis) {
+      if ((a >> axis) & 1) continue;
+      const int b = a | (1 << axis);
+      if ((((m >> a) ^ (m >> b)) & 1u) == 0u) continue;
+      float t = (thr - v[a]) / (v[b] - v[a]);
+      if (!isfinite(t)) t = 0.5f;
+      else if (t < 0.f) t = 0.f;
+      else if (t > 1.f) t = 1.f;
+      float px = (float)(a & 1), py = (float)((a >> 1) & 1), pz = (float)(a >> 2);
+      if (axis == 0) px = px + t;
+      if (axis == 1) py = py + t;
+      if (axis == 2) pz = pz + t;
+      ax = ax + px;
+      ay = ay + py;
+      az = az + pz;
+      ++count;
+    }
+  }
+  const float n = (float)count;
+  const float lx = ax / n, ly = ay / n, lz = az / n;
+  const float hx = (float)i + lx, hy = (float)j + ly, hz = (float)k + lz;
+  const float mx = hx * g.step[0], my = hy * g.step[1], mz = hz * g.step[2];
+  out[0] = mx + g.origin[0];
+  out[1] = my + g.origin[1];
+  out[2] = mz + g.origin[2];
+}
+
+// Stage 3a: the cell-to-vertex map (always), and, when both capacities hold the scanned totals, the vertices and their cells.
+__global__ __launch_bounds__(MESH_THREADS) void mesh_vertices_kernel(const float* __restrict__ sigma, const MeshDims d, const nrf_grid g,
+                                                                     const float thr, const unsigned char* __restrict__ mask,
+                                                                     const int* __restrict__ block_v, int* __restrict__ status,
+                                                                     const int max_vertices, const int max_triangles,
+                                                                     float* __restrict__ vertices, int* __restrict__ vertex_cell,
+                                                                     int* __restrict__ map) {
+  __shared__ int sv[MESH_SLOTS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool fits = status[0] <= max_vertices && status[1] <= max_triangles;
+  int rank[MESH_ROUNDS];
+  unsigned ms[MESH_ROUNDS];
+#pragma unroll
+  for (int r = 0; r < MESH_ROUNDS; ++r) {
+    const int cell = blockIdx.x * MESH_BLOCK_CELLS + r * MESH_THREADS + threadIdx.x;
+    const unsigned m = cell < d.ncells ? (unsigned)mask[cell] : 0u;
+    const unsigned long long bv = __ballot(m != 0u && m != 255u);
+    ms[r] = m;
+    rank[r] = __popcll(bv & lanes_below());
+    if (lane == 0) sv[r * MESH_WAVES + wave] = __popcll(bv);
+  }
+  __syncthreads();
+  if (blockIdx.x == 0 && threadIdx.x == 0) {   // what the caller reads back: all of the mesh, or none of it
+    status[2] = fits ? status[0] : 0;
+    status[3] = fits ? status[1] : 0;
+  }
+  int before = block_v[blockIdx.x];
+  const size_t sy = (size_t)d.X, sz = (size_t)d.X * (size_t)d.Y;
+#pragma unroll
+  for (int r = 0; r < MESH_ROUNDS; ++r) {
+#pragma unroll
+    for (int w = 0; w < MESH_WAVES; ++w) {
+      const int e = r * MESH_WAVES + w;
+      if (w == wave) {
+        const int cell = blockIdx.x * MESH_BLOCK_CELLS + r * MESH_THREADS + threadIdx.x;
+        const unsigned m = ms[r];
+        if (cell < d.ncells) {
+          const bool active = m != 0u && m != 255u;
+          const int vid = before + rank[r];
+          map[cell] = active ? vid : -1;
+          if (active && fits && vid < max_vertices) {
+            int i, j, k;
+            cell_coords(cell, d, i, j, k);
+            float p[3];
+            cell_vertex(sigma + ((size_t)i + sy * (size_t)j + sz * (size_t)k), sy, sz, m, thr, i, j, k, g, p);
+            vertices[3 * (size_t)vid + 0] = p[0];
+            vertices[3 * (size_t)vid + 1] = p[1];
+            vertices[3 * (size_t)vid + 2] = p[2];
+            vertex_cell[vid] = cell;
+          }
+        }
+      }
+      before += sv[e];
+    }
+  }
+}
+
+// Stage 3b: two triangles per owned quad, from the map.
+__global__ __launch_bounds__(MESH_THREADS) void mesh_faces_kernel(const MeshDims d, const unsigned char* __restrict__ mask,
+                                                                  const int* __restrict__ map, const int* __restrict__ block_q,
+                                                                  const int* __restrict__ status, const int max_vertices,
+                                                                  const int max_triangles, int* __restrict__ triangles) {
+  __shared__ int sq[MESH_SLOTS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (!(status[0] <= max_vertices && status[1] <= max_triangles)) return;   // uniform over the grid
+  int rank[MESH_ROUNDS];
+  unsigned qs[MESH_ROUNDS];
+#pragma unroll
+  for (int r = 0; r < MESH_ROUNDS; ++r) {
+    const int cell = blockIdx.x * MESH_BLOCK_CELLS + r * MESH_THREADS + threadIdx.x;
+    unsigned q = 0;
+    if (cell < d.ncells) {
+      int i, j, k;
+      cell_coords(cell, d, i, j, k);
+      const unsigned m = (unsigned)mask[cell];
+      q = owned_quads(m, i, j, k) | ((m & 1u) << 3);   // bit 3: the sample at c is inside
+    }
+    const unsigned long long bx = __ballot((q & 1u) != 0u), by = __ballot((q & 2u) != 0u), bz = __ballot((q & 4u) != 0u);
+    const unsigned long long lt = lanes_below();
+    qs[r] = q;
+    rank[r] = __popcll(bx & lt) + __popcll(by & lt) + __popcll(bz & lt);
+    if (lane == 0) sq[r * MESH_WAVES + wave] = __popcll(bx) + __popcll(by) + __popcll(bz);
+  }
+  __syncthreads();
+  int before = block_q[blockIdx.x];
+  const int ey = d.cx, ez = d.cx * d.cy;   // cell strides
+#pragma unroll
+  for (int r = 0; r < MESH_ROUNDS; ++r) {
+#pragma unroll
+    for (int w = 0; w < MESH_WAVES; ++w) {
+      const int e = r * MESH_WAVES + w;
+      if (w == wave && (qs[r] & 7u) != 0u) {
+        const int cell = blockIdx.x * MESH_BLOCK_CELLS + r * MESH_THREADS + threadIdx.x;
+        const bool inside = (qs[r] & 8u) != 0u;
+        int quad = before + rank[r];
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+          if (((qs[r] >> ax) & 1u) == 0u) continue;
+          const int eu = ax == 0 ? ey : (ax == 1 ? ez : 1), ev = ax == 0 ? ez : (ax == 1 ? 1 : ey);
+          int q0 = map[cell - eu - ev], q1 = map[cell - ev], q2 = map[cell], q3 = map[cell - eu];
+          if (!inside) {
+            int t = q0; q0 = q3; q3 = t;
+            t = q1; q1 = q2; q2 = t;
+          }
+          const long long tri = 2ll * quad;
+          if (tri + 1 < (long long)max_triangles) {
+            int* o = triangles + 3 * (size_t)tri;
+            o[0] = q0; o[1] = q1; o[2] = q2;
+            o[3] = q0; o[4] = q2; o[5] = q3;
+          }
+          ++quad;
+        }
+      }
+      before += sq[e];
+    }
+  }
+}
+
+// One Newton step onto the level set per vertex, then the clamp to the vertex's own cell.
+__global__ __launch_bounds__(MESH_THREADS) void mesh_snap_kernel(float* __restrict__ vertices, const int* __restrict__ vertex_cell,
+                                                                 const float* __restrict__ sigma_at, const float* __restrict__ grad_at,
+                                                                 const nrf_grid g, const MeshDims d, const float thr, const int n) {
+  const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
+  if (v >= n) return;
+  const float gx = grad_at[3 * (size_t)v + 0], gy = grad_at[3 * (size_t)v + 1], gz = grad_at[3 * (size_t)v + 2];
+  const float sg = sigma_at[v];
+  const float s = fmaf(gz, gz, fmaf(gy, gy, gx * gx));
+  if (!(s > 0.f) || !isfinite(s) || !isfinite(sg)) return;
+  const int cell = vertex_cell[v];
+  if (cell < 0 || cell >= d.ncells) return;   // not a vertex of this grid: nothing to clamp to
+  int idx[3];
+  cell_coords(cell, d, idx[0], idx[1], idx[2]);
+  const float q = (sg - thr) / s;
+  const float gr[3] = {gx, gy, gz};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float x = fmaf(-q, gr[c], vertices[3 * (size_t)v + c]);
+    const float p0 = (float)idx[c] * g.step[c], p1 = (float)(idx[c] + 1) * g.step[c];
+    const float e0 = g.origin[c] + p0, e1 = g.origin[c] + p1;
+    const float lo = e0 < e1 ? e0 : e1, hi = e0 < e1 ? e1 : e0;
+    if (!(x >= lo)) x = lo;   // a NaN (an infinite step times a zero slope) lands on lo
+    else if (x > hi) x = hi;
+    vertices[3 * (size_t)v + c] = x;
+  }
+}
+
+// what every entry checks of its grid and threshold before any HIP call
+int mesh_args(const char* entry, const nrf_grid* grid, float threshold, bool with_threshold) {
+  char msg[200];
+  if (!grid) {
+    snprintf(msg, sizeof(msg), "%s: grid is null", entry);
+    return fail(NRF_E_NULL, msg);
+  }
+  long long cells = 1;
+  for (int c = 0; c < 3; ++c) {
+    if (grid->dims[c] < 2) {
+      snprintf(msg, sizeof(msg), "%s: grid->dims[%d] = %d: a mesh needs at least 2 samples per axis", entry, c, grid->dims[c]);
+      return fail(NRF_E_SHAPE, msg);
+    }
+    cells *= (long long)(grid->dims[c] - 1);
+    if (cells > NRF_MESH_MAX_CELLS) {
+      snprintf(msg, sizeof(msg), "%s: more than NRF_MESH_MAX_CELLS = 1 << 28 cells", entry);
+      return fail(NRF_E_SHAPE, msg);
+    }
+  }
+  if (with_threshold && !std::isfinite(threshold)) {
+    snprintf(msg, sizeof(msg), "%s: threshold must be finite", entry);
+    return fail(NRF_E_SHAPE, msg);
+  }
+  return NRF_OK;
+}
+
+int mesh_null(const char* entry, const char* name) {
+  char msg[200];
+  snprintf(msg, sizeof(msg), "%s: %s is null", entry, name);
+  return fail(NRF_E_NULL, msg);
+}
+
+int mesh_workspace(const char* entry, const MeshPlan& p, const void* workspace, size_t bytes) {
+  char msg[200];
+  if (!workspace) return mesh_null(entry, "workspace");
+  if (((uintptr_t)workspace & 15u) != 0) {
+    snprintf(msg, sizeof(msg), "%s: workspace must be 16-byte aligned", entry);
+    return fail(NRF_E_SHAPE, msg);
+  }
+  if (bytes < p.total) {
+    snprintf(msg, sizeof(msg), "%s: workspace too small (see nrf_mesh_workspace_bytes)", entry);
+    return fail(NRF_E_WORKSPACE, msg);
+  }
+  return NRF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nrf_mesh_workspace_bytes(const nrf_grid* grid, size_t* bytes) {
+  CK(mesh_args("nrf_mesh_workspace_bytes", grid, 0.f, false));
+  if (!bytes) return mesh_null("nrf_mesh_workspace_bytes", "bytes");
+  *bytes = mesh_plan(mesh_dims(grid)).total;
+  return NRF_OK;
+}
+
+int nrf_mesh_count(const float* sigma, const nrf_grid* grid, float threshold, int32_t* counts, void* workspace, size_t workspace_bytes,
+                   void* stream) {
+  const char* entry = "nrf_mesh_count";
+  if (!sigma) return mesh_null(entry, "sigma");
+  CK(mesh_args(entry, grid, threshold, true));
+  if (!counts) return mesh_null(entry, "counts");
+  const MeshDims d = mesh_dims(grid);
+  const MeshPlan p = mesh_plan(d);
+  CK(mesh_workspace(entry, p, workspace, workspace_bytes));
+  char* ws = (char*)workspace;
+  hipLaunchKernelGGL(mesh_classify_kernel, dim3(d.nblocks), dim3(MESH_THREADS), 0, (hipStream_t)stream, sigma, d, threshold,
+                     (unsigned char*)(ws + p.mask), (int*)(ws + p.block_v), (int*)(ws + p.block_q));
+  hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, (int*)(ws + p.block_v), (int*)(ws + p.block_q),
+                     d.nblocks, (int*)ws, counts);
+  return check_launch(entry);
+}
+
+int nrf_mesh_emit(const float* sigma, const nrf_grid* grid, float threshold, int32_t max_vertices, int32_t max_triangles, float* vertices,
+                  int32_t* vertex_cell, int32_t* triangles, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* entry = "nrf_mesh_emit";
+  char msg[200];
+  if (!sigma) return mesh_null(entry, "sigma");
+  CK(mesh_args(entry, grid, threshold, true));
+  if (max_vertices < 0 || max_triangles < 0) {
+    snprintf(msg, sizeof(msg), "%s: %s must not be negative", entry, max_vertices < 0 ? "max_vertices" : "max_triangles");
+    return fail(NRF_E_SHAPE, msg);
+  }
+  if (max_vertices > 0 && !vertices) return mesh_null(entry, "vertices");
+  if (max_vertices > 0 && !vertex_cell) return mesh_null(entry, "vertex_cell");
+  if (max_triangles > 0 && !triangles) return mesh_null(entry, "triangles");
+  const MeshDims d = mesh_dims(grid);
+  const MeshPlan p = mesh_plan(d);
+  CK(mesh_workspace(entry, p, workspace, workspace_bytes));
+  char* ws = (char*)workspace;
+  hipLaunchKernelGGL(mesh_vertices_kernel, dim3(d.nblocks), dim3(MESH_THREADS), 0, (hipStream_t)stream, sigma, d, *grid, threshold,
+                     (const unsigned char*)(ws + p.mask), (const int*)(ws + p.block_v), (int*)ws, max_vertices, max_triangles, vertices,
+                     vertex_cell, (int*)(ws + p.map));
+  hipLaunchKernelGGL(mesh_faces_kernel, dim3(d.nblocks), dim3(MESH_THREADS), 0, (hipStream_t)stream, d, (const unsigned char*)(ws + p.mask),
+                     (const int*)(ws + p.map), (const int*)(ws + p.block_q), (const int*)ws, max_vertices, max_triangles, triangles);
+  return check_launch(entry);
+}
+
+int nrf_mesh_snap(float* vertices, const int32_t* vertex_cell, const float* sigma_at, const float* grad_at, const nrf_grid* grid,
+                  float threshold, int32_t num_vertices, void* stream) {
+  const char* entry = "nrf_mesh_snap";
+  char msg[200];
+  CK(mesh_args(entry, grid, threshold, true));
+  if (num_vertices < 0) {
+    snprintf(msg, sizeof(msg), "%s: num_vertices must not be negative", entry);
+    return fail(NRF_E_SHAPE, msg);
+  }
+  if (num_vertices == 0) return NRF_OK;   // an empty mesh: the buffers may be NULL
+  if (!vertices) return mesh_null(entry, "vertices");
+  if (!vertex_cell) return mesh_null(entry, "vertex_cell");
+  if (!sigma_at) return mesh_null(entry, "sigma_at");
+  if (!grad_at) return mesh_null(entry, "grad_at");
+  const MeshDims d = mesh_dims(grid);
+  hipLaunchKernelGGL(mesh_snap_kernel, dim3((num_vertices + MESH_THREADS - 1) / MESH_THREADS), dim3(MESH_THREADS), 0, (hipStream_t)stream,
+                     vertices, vertex_cell, sigma_at, grad_at, *grid, d, threshold, num_vertices);
+  return check_launch(entry);
+}
+
+}  // extern "C"

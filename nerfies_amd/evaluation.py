@@ -1,4 +1,5 @@
 """Host-side mirror of nerfies.evaluation.render_image (reference: nerfies/evaluation.py:28-101)."""
+import ctypes as C
 import math
 from typing import Any, Callable, Dict, Optional
 
@@ -303,6 +304,110 @@ def normal_grid(model, params, bbox_min, bbox_max, resolution, level='fine', war
                               {'sigma': sigma[first:first + count], 'normals': normals[first:first + count]}, metadata=metadata,
                               warp_extra=warp_extra, level=level, use_warp=warp_id is not None, workspace_points=chunk)
   return sigma.view(res[2], res[1], res[0]).permute(2, 1, 0), normals.view(res[2], res[1], res[0], 3).permute(2, 1, 0, 3)
+
+
+MESH_VIEW_DIRECTION = (0.0, 0.0, 1.0)   # the direction every exported colour is queried along
+
+
+def _mesh_grid(sigma, origin, step):
+  """(the x-fastest flat view of an (X, Y, Z) density tensor, its nrf_grid)."""
+  from nerfies_amd import lib as L
+  if sigma.dim() != 3 or sigma.dtype != torch.float32:
+    raise ValueError(f'sigma must be a float32 (X, Y, Z) tensor, got {sigma.dtype} {tuple(sigma.shape)}')
+  flat = sigma.permute(2, 1, 0).contiguous().reshape(-1)   # no copy for a tensor laid out as density_grid returns it
+  grid = L.Grid((C.c_float * 3)(*[float(v) for v in origin]), (C.c_float * 3)(*[float(v) for v in step]),
+                (C.c_int32 * 3)(*[int(n) for n in sigma.shape]), 0)
+  return flat, grid
+
+
+def _dev_stream(device):
+  return torch.cuda.current_stream(device).cuda_stream if device.type == 'cuda' else None   # not cuda: a recording stand-in only
+
+
+def extract_mesh_from_grid(sigma, origin, step, threshold, lib=None):
+  """Surface nets of a density grid from anywhere (nrf_mesh_count, then nrf_mesh_emit; the definition is in
+  include/nerfies_amd.h): `sigma` is a float32 (X, Y, Z) device tensor whose sample (i, j, k) sits at origin + idx * step (the
+  memory order of `density_grid` is used as it is; any other is copied once).  A sample is inside iff sigma > threshold.  Returns
+  device tensors {'vertices' (V, 3) float32, 'vertex_cell' (V,) int32, 'faces' (F, 3) int32}: one vertex per active cell, shared by
+  its faces, counter-clockwise faces whose normals point from high density to low, the same bits on every run.  The two counts are
+  read back once, to size the outputs; an empty mesh is (0, 3) tensors."""
+  from nerfies_amd import lib as L
+  lib = lib or L.load_library()
+  flat, grid = _mesh_grid(sigma, origin, step)
+  device = flat.device
+  stream = _dev_stream(device)
+  nbytes = C.c_size_t(0)
+  L.check(lib.nrf_mesh_workspace_bytes(C.byref(grid), C.byref(nbytes)), lib)
+  ws = torch.empty((nbytes.value + 3) // 4, dtype=torch.int32, device=device)
+  counts = torch.zeros(2, dtype=torch.int32, device=device)
+  L.check(lib.nrf_mesh_count(flat.data_ptr(), C.byref(grid), float(threshold), counts.data_ptr(), ws.data_ptr(), ws.numel() * 4, stream), lib)
+  nv, nt = (int(v) for v in counts.tolist())
+  vertices = torch.empty(nv, 3, dtype=torch.float32, device=device)
+  vertex_cell = torch.empty(nv, dtype=torch.int32, device=device)
+  faces = torch.empty(nt, 3, dtype=torch.int32, device=device)
+  ptr = lambda t: t.data_ptr() if t.numel() else None
+  L.check(lib.nrf_mesh_emit(flat.data_ptr(), C.byref(grid), float(threshold), nv, nt, ptr(vertices), ptr(vertex_cell), ptr(faces),
+                            ws.data_ptr(), ws.numel() * 4, stream), lib)
+  return {'vertices': vertices, 'vertex_cell': vertex_cell, 'faces': faces}
+
+
+def extract_mesh(model, params, bbox_min, bbox_max, resolution, threshold, level='fine', warp_id=None, appearance_id=None, camera_id=None,
+                 warp_extra=None, refine_steps=2, colors=True, chunk=1 << 21):
+  """A triangle mesh of the field's level set sigma = threshold over the box [bbox_min, bbox_max], all on the device: `density_grid`
+  (same arguments; its voxel centres are the mesh's samples, so `resolution` R gives R - 1 cells per axis), surface nets
+  (`extract_mesh_from_grid`), then `refine_steps` rounds of the field's own density and gradient at the vertices
+  (NerfModel.query_gradient) and one Newton step onto the level set each (nrf_mesh_snap: every vertex stays inside its cell, the
+  faces do not change).  `warp_id=None` meshes the canonical (template) volume, an id that frame's observation volume.
+  `appearance_id` / `camera_id`: the codes the colour is queried with (and, for a use_alpha_condition model, the density).
+  Returns device tensors {'vertices' (V, 3), 'faces' (F, 3) int32, 'normals' (V, 3) = -grad sigma / |grad sigma| at the final
+  vertices, 'sigma' (V,) there, and with `colors` 'rgb' (V, 3) along MESH_VIEW_DIRECTION}."""
+  from nerfies_amd import lib as L
+  res = (int(resolution),) * 3 if isinstance(resolution, int) else tuple(int(r) for r in resolution)
+  alpha_app = appearance_id if getattr(model, 'use_alpha_condition', False) else None
+  sigma = density_grid(model, params, bbox_min, bbox_max, res, level=level, warp_id=warp_id, appearance_id=alpha_app,
+                       warp_extra=warp_extra, chunk=chunk)
+  lo = [float(v) for v in bbox_min]
+  hi = [float(v) for v in bbox_max]
+  step = [(h - l) / r for l, h, r in zip(lo, hi, res)]
+  origin = [l + 0.5 * s for l, s in zip(lo, step)]
+  lib = model.lib
+  mesh = extract_mesh_from_grid(sigma, origin, step, threshold, lib=lib)
+  vertices, vertex_cell = mesh['vertices'], mesh['vertex_cell']
+  device = vertices.device
+  nv = vertices.shape[0]
+  out = {'vertices': vertices, 'faces': mesh['faces']}
+  if nv == 0:
+    out.update(normals=torch.zeros(0, 3, device=device), sigma=torch.zeros(0, device=device))
+    if colors:
+      out['rgb'] = torch.zeros(0, 3, device=device)
+    return out
+  use_warp = warp_id is not None
+  ids = lambda v: torch.tensor([[int(v)]], dtype=torch.int32, device=device)
+  md = {}
+  if use_warp:
+    md['warp'] = ids(warp_id)
+  if alpha_app is not None:
+    md['appearance'] = ids(alpha_app)
+  _, grid = _mesh_grid(sigma, origin, step)
+  kw = dict(metadata=md, warp_extra=warp_extra, level=level, use_warp=use_warp)
+  for _ in range(int(refine_steps)):
+    q = model.query_gradient(params, vertices, outputs=('sigma', 'grad_sigma'), **kw)
+    L.check(lib.nrf_mesh_snap(vertices.data_ptr(), vertex_cell.data_ptr(), q['sigma'].data_ptr(), q['grad_sigma'].data_ptr(), C.byref(grid),
+                              float(threshold), nv, _dev_stream(device)), lib)
+  q = model.query_gradient(params, vertices, outputs=('sigma', 'normals'), **kw)
+  out.update(normals=q['normals'], sigma=q['sigma'])
+  if colors:
+    cmd = dict(md)
+    if appearance_id is not None:
+      cmd['appearance'] = ids(appearance_id)
+    if camera_id is not None:
+      cmd['camera'] = ids(camera_id)
+    view = torch.tensor([MESH_VIEW_DIRECTION], dtype=torch.float32, device=device)
+    per = max(1, min(int(chunk), L.NRF_QUERY_MAX_POINTS))
+    parts = [model.query_points(params, vertices[first:first + count], viewdirs=view, metadata=cmd, warp_extra=warp_extra, level=level,
+                                use_warp=use_warp, outputs=('rgb',))['rgb'] for first, count in grid_chunks(nv, per)]
+    out['rgb'] = torch.cat(parts, 0)
+  return out
 
 
 def compute_psnr(mse):

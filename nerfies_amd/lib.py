@@ -144,9 +144,15 @@ class FieldGradOut(C.Structure):
   _fields_ = [('sigma', C.c_void_p), ('grad_sigma', C.c_void_p), ('normals', C.c_void_p), ('warped_points', C.c_void_p)]
 
 
+class MeshStatus(C.Structure):
+  """nrf_mesh_status: the first 16 bytes of a mesh workspace (device memory) after nrf_mesh_count / nrf_mesh_emit."""
+  _fields_ = [('num_vertices', C.c_int32), ('num_triangles', C.c_int32), ('emitted_vertices', C.c_int32), ('emitted_triangles', C.c_int32)]
+
+
 NRF_QUERY_MAX_POINTS = 1 << 24   # points of one nrf_query_points / nrf_query_grid call
 NRF_QUERY_GRAD_MAX_POINTS = 1 << 20   # points of one nrf_query_points_grad / nrf_query_grid_grad call
 NRF_GRID_MAX_POINTS = 1 << 40    # points of a whole nrf_grid
+NRF_MESH_MAX_CELLS = 1 << 28     # cells of a grid handed to nrf_mesh_count / nrf_mesh_emit (triangle indices stay in int32)
 NRF_OPT_CHAIN_TILE_ROWS = 1
 NRF_OPT_BF16_WGRAD_MERGE = 2
 
@@ -165,6 +171,7 @@ EXPORTS = [
     'nrf_loss_grad_rays',
     'nrf_query_workspace_bytes', 'nrf_query_points', 'nrf_query_grid',
     'nrf_query_grad_workspace_bytes', 'nrf_query_points_grad', 'nrf_query_grid_grad',
+    'nrf_mesh_workspace_bytes', 'nrf_mesh_count', 'nrf_mesh_emit', 'nrf_mesh_snap',
 ]
 
 _lib = None
@@ -232,6 +239,10 @@ def load_library(path=None):
                                 C.c_size_t, vp],
       'nrf_query_grid_grad': [vp, vp, C.POINTER(Rays), C.POINTER(Grid), i64, i32, i32, C.POINTER(StepScalars), u32,
                               C.POINTER(FieldGradOut), vp, C.c_size_t, vp],
+      'nrf_mesh_workspace_bytes': [C.POINTER(Grid), C.POINTER(C.c_size_t)],
+      'nrf_mesh_count': [vp, C.POINTER(Grid), f32, vp, vp, C.c_size_t, vp],
+      'nrf_mesh_emit': [vp, C.POINTER(Grid), f32, i32, i32, vp, vp, vp, vp, C.c_size_t, vp],
+      'nrf_mesh_snap': [vp, vp, vp, vp, C.POINTER(Grid), f32, i32, vp],
       'nrf_camera_pixels_to_rays': [C.POINTER(CameraDesc), vp, i64, vp, vp, vp, vp],
       'nrf_camera_pixels_to_points': [C.POINTER(CameraDesc), vp, vp, i64, vp, vp],
       'nrf_camera_project': [C.POINTER(CameraDesc), vp, i64, vp, vp],

@@ -14,7 +14,10 @@ Writes, next to the checkpoints' experiment directory:
 With --normals (evaluation.normal_grid -> nrf_query_grid_grad: the density's gradient from the reverse chain, no finite differences):
   normals_<name>.npy   float32 (X, Y, Z, 3) unit normals -grad sigma / |grad sigma| at the voxel centres (0 where the gradient
                        vanishes), and the PLY's vertices gain the properties nx ny nz.
-There is no mesh extraction: the .npy grid is what a marching-cubes tool reads."""
+With --mesh (evaluation.extract_mesh -> nrf_mesh_count / nrf_mesh_emit / nrf_mesh_snap: surface nets on the device grid, the vertices
+pulled onto the level set sigma = --threshold by --mesh_refine Newton steps along the field's own gradient):
+  mesh_<name>.ply      binary little-endian triangle mesh: vertices x y z nx ny nz red green blue, faces as vertex_indices lists.
+The .npy grid and the point cloud stay what they were; the mesh is the iso-surface they stopped short of."""
 import argparse
 import os
 import sys
@@ -42,6 +45,8 @@ def parse_flags(argv=None):
   p.add_argument('--threshold', type=float, default=10.0, help='voxels with sigma above it go into the PLY')
   p.add_argument('--level', default='fine', choices=['coarse', 'fine'])
   p.add_argument('--normals', action='store_true', help='also export the surface normals -grad sigma / |grad sigma| (npy, and nx ny nz in the PLY)')
+  p.add_argument('--mesh', action='store_true', help='also extract the triangle mesh of the level set sigma = --threshold (mesh_<name>.ply)')
+  p.add_argument('--mesh_refine', type=int, default=2, metavar='K', help='Newton steps of the mesh vertices onto the level set')
   p.add_argument('--margin', type=float, default=0.0, help="grow the scene points' box by this fraction of its size on every side")
   own, rest = p.parse_known_args(argv)
   if len(own.resolution) not in (1, 3):
@@ -68,6 +73,24 @@ def write_ply(path, xyz, rgb, normals=None):
     else:
       for (x, y, z), (nx, ny, nz), (r, g, b) in zip(xyz, normals, rgb8):
         f.write(f'{x:.6f} {y:.6f} {z:.6f} {nx:.6f} {ny:.6f} {nz:.6f} {r} {g} {b}\n')
+
+
+def write_mesh_ply(path, vertices, normals, rgb, faces):
+  """Binary little-endian PLY of an indexed triangle mesh: vertices (V, 3), normals (V, 3), colours (V, 3) in [0, 1], faces (F, 3)."""
+  vert = np.zeros(len(vertices), dtype=[('xyz', '<f4', 3), ('n', '<f4', 3), ('rgb', 'u1', 3)])
+  vert['xyz'], vert['n'] = vertices, normals
+  vert['rgb'] = np.clip(np.rint(np.asarray(rgb) * 255.0), 0, 255).astype(np.uint8)
+  face = np.zeros(len(faces), dtype=[('n', 'u1'), ('idx', '<i4', 3)])
+  face['n'], face['idx'] = 3, faces
+  head = ('ply\nformat binary_little_endian 1.0\n'
+          f'element vertex {len(vert)}\n'
+          'property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n'
+          'property uchar red\nproperty uchar green\nproperty uchar blue\n'
+          f'element face {len(face)}\nproperty list uchar int vertex_indices\nend_header\n')
+  with open(path, 'wb') as f:
+    f.write(head.encode('ascii'))
+    f.write(vert.tobytes())
+    f.write(face.tobytes())
 
 
 def main(argv=None):
@@ -146,6 +169,14 @@ def main(argv=None):
   ret = {'npy': npy, 'ply': ply, 'resolution': res, 'num_vertices': int(idx.shape[0]), 'bbox': (lo, hi)}
   if normals_npy is not None:
     ret['normals_npy'] = normals_npy
+  if flags.mesh:
+    mesh = evaluation.extract_mesh(model, target, lo, hi, res, flags.threshold, level=flags.level, warp_id=warp_id, appearance_id=app_id,
+                                   camera_id=cam_id, warp_extra=state.warp_extra, refine_steps=flags.mesh_refine)
+    mesh_ply = os.path.join(exp_dir, f'mesh_{name}.ply')
+    write_mesh_ply(mesh_ply, *(mesh[k].cpu().numpy() for k in ('vertices', 'normals', 'rgb', 'faces')))
+    print(f'mesh_{name}: {mesh["vertices"].shape[0]} vertices, {mesh["faces"].shape[0]} faces at sigma = {flags.threshold:g}, '
+          f'{flags.mesh_refine} refine steps -> {mesh_ply}', flush=True)
+    ret.update(mesh_ply=mesh_ply, num_mesh_vertices=int(mesh['vertices'].shape[0]), num_mesh_faces=int(mesh['faces'].shape[0]))
   return ret
 
 
