@@ -21,66 +21,14 @@ sys.path.insert(0, HERE)
 
 from oracle import nerfies_oracle as O  # noqa: E402
 import helpers as H  # noqa: E402
+from bf16_reference import MLP, WARP_ALPHA, mlp_setup as _setup, check_forward_and_stash, check_backward_given_the_stash  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
-# the step-1 checks below pin the NeRF-MLP chain against an oracle that rounds exactly what that chain rounds: they run the mode
-# that keeps the SE3 trunk in float32 (bf16='mlp' = NRF_FLAG_BF16 | NRF_FLAG_WARP_F32); the bfloat16 trunk has its own checks
-# in tests/test_gpu_bf16_warp.py, and the end-to-end gates (gradient direction, PSNR) run the full bf16 mode
-MLP = 'mlp'
-
-
-class _RoundFwd(torch.autograd.Function):
-  """x -> bfloat16(x) (RNE), gradient passed through (the master copy is float32)."""
-
-  @staticmethod
-  def forward(ctx, x):
-    return x.to(torch.bfloat16).to(x.dtype)
-
-  @staticmethod
-  def backward(ctx, g):
-    return g
-
-
-class _RoundBwd(torch.autograd.Function):
-  """identity whose incoming gradient is rounded to bfloat16 (the dY stash)."""
-
-  @staticmethod
-  def forward(ctx, x):
-    return x.view_as(x)
-
-  @staticmethod
-  def backward(ctx, g):
-    return g.to(torch.bfloat16).to(g.dtype)
-
-
-def bf16_dense_for(spec):
-  """csrc/mlp_bf16.hip's arithmetic of one Dense of the NeRF MLP: bf16 operands (for the rgb hidden layer only the
-  bottleneck columns: the per-ray condition columns are folded into an exact fp32 term by ray_prep), exact bias, dY rounded."""
-  tw, rw = spec.nerf_trunk_width, spec.nerf_rgb_branch_width
-
-  def dense(p, x):
-    w = p['kernel']
-    if O._SCOPE != 'nerf_mlp':   # the warp field stays float32 in the bf16 mode
-      return x @ w + p['bias']
-    nq = tw if (w.shape[1] == rw and w.shape[0] > tw and rw != tw) else w.shape[0]
-    y = _RoundFwd.apply(x[..., :nq]) @ _RoundFwd.apply(w[:nq])
-    if nq < w.shape[0]:
-      y = y + x[..., nq:] @ w[nq:]
-    return _RoundBwd.apply(y + p['bias'])
-  return dense
-
-
-def _setup(B, seed=3, **kw):
-  spec = O.ModelSpec(**dict(dict(num_coarse_samples=64, num_fine_samples=128, num_nerf_point_freqs=8, use_stratified_sampling=True), **kw))
-  p = O.init_params(spec, seed=seed, trained_like=True, dtype=torch.float64)
-  b = O.synthetic_batch(B, seed=seed + 1, dtype=torch.float64)
-  g = torch.Generator().manual_seed(seed + 2)
-  t_rand = torch.rand(B, spec.num_coarse_samples, generator=g).double()
-  u = torch.rand(B, spec.num_fine_samples, generator=g).double()
-  model, fp = H.gpu_model(spec, p, B)
-  rngs = {'coarse': t_rand.float().to(DEV), 'fine': u.float().to(DEV)}
-  return spec, p, b, t_rand, u, model, fp, rngs
+# the step-1 checks below (tests/bf16_reference.py, shared with the other layouts of tests/test_gpu_bf16_layouts.py) pin the NeRF-MLP
+# chain against an oracle that rounds exactly what that chain rounds: they run the mode that keeps the SE3 trunk in float32
+# (MLP: bf16='mlp' = NRF_FLAG_BF16 | NRF_FLAG_WARP_F32); the bfloat16 trunk has its own checks in tests/test_gpu_bf16_warp.py, and the
+# end-to-end gates (gradient direction, PSNR) run the full bf16 mode
 
 
 CASES = [(37, {}), (401, {}), (50, dict(num_nerf_point_freqs=10, use_camera_metadata=True)),
@@ -89,132 +37,11 @@ CASES = [(37, {}), (401, {}), (50, dict(num_nerf_point_freqs=10, use_camera_meta
          (21, dict(use_warp=True, num_nerf_point_freqs=10, num_coarse_samples=32, num_fine_samples=32)),
          (3, dict(num_coarse_samples=8, num_fine_samples=5)),       # 24 / 39 rows: one workgroup iteration, most waves padding
          (1, dict(num_coarse_samples=16, num_fine_samples=0))]      # a single ray, coarse level only
-WARP_ALPHA = 4.0
-
-
-def check_forward_and_stash(setup, ulp_frac=0.05):
-  """Step 1a: loss, rendered outputs and every stashed activation against the float64 oracle with the same roundings.
-  float32 vs float64 accumulation moves a pre-activation by ~1e-7 relative, which flips the bfloat16 rounding of about
-  one element in 3000 by one ulp (0.4 %), and later layers inherit those: per layer the relative L2 distance stays below
-  5e-3, the largest deviation below 2 % of the layer's scale, at least 95 % of the elements within one ulp."""
-  spec, p, b, t_rand, u, model, fp, rngs = setup
-  B = b['origins'].shape[0]
-  gb = H.gpu_batch(b)
-  grad, stats = model.loss_and_grad(fp, gb, warp_extra={'alpha': WARP_ALPHA}, rngs=rngs, bf16=MLP)
-  torch.cuda.synchronize()
-  ws = model.workspace(B, True, DEV, bf16=MLP)
-  S = (spec.num_coarse_samples, spec.num_coarse_samples + spec.num_fine_samples)
-  fine = spec.num_fine_samples > 0
-  z_fine = torch.from_numpy(H._ws_words(model, ws, 'z', 1, B * S[1]).view('float32').reshape(B, S[1]).copy()).double() if fine else None
-  acts = {}
-
-  def record(name, layer, pre):
-    acts[(name, layer)] = H.bf16_round(torch.relu(pre.detach())).float()   # exact in float32, half the host memory
-    return torch.relu(pre)
-  with H.host_threads(64), torch.no_grad(), O.dense_hook(bf16_dense_for(spec)), O.relu_hook(record):   # forward only: no graph
-    loss, ostats, ret = O.loss_fn(p, spec, b, warp_alpha=WARP_ALPHA, t_rand=t_rand, u=u, fixed_fine_z=z_fine)
-  assert abs(stats[4].item() - loss.item()) < 5e-5, (stats[4].item(), loss.item())
-  tw, rw = spec.nerf_trunk_width, spec.nerf_rgb_branch_width
-  for lv, name in enumerate(('coarse', 'fine') if fine else ('coarse',)):
-    rows = B * S[lv]
-    hs = H.bf16_stash(model, ws, 'b_h', lv, 8, 8, rows, as_float32=True)
-    rg = H.bf16_stash(model, ws, 'b_rgbh', lv, 1, 4, rows, as_float32=True)[0]
-    def close(got, want, what):
-      # one-ulp bf16 ties (float32 vs float64 accumulation, v_sin_f32 vs sin in the posenc) propagate: a unit near its kink
-      # may differ by a multiple of its own value, never by more than a few bf16 ulps of the layer's scale
-      got, want = got.double(), want.double()
-      err = (got - want).abs()
-      assert err.max().item() <= 2e-2 * want.abs().max().item(), (what, err.max().item(), want.abs().max().item())
-      assert (err.norm() / want.norm()).item() <= 5e-3, (what, (err.norm() / want.norm()).item())
-      frac = (err > 2.0 ** -7 * want.abs() + 1e-6 * want.abs().max()).float().mean().item()
-      assert frac < ulp_frac, (what, frac)
-    for l in range(8):
-      close(hs[l][:, :tw], acts[(f'{name}/MLP_0', l)], (name, l))
-      assert (hs[l][:, tw:] == 0).all()   # padded units of a narrower trunk stay dead
-    close(rg[:, :rw], acts[(f'{name}/MLP_1', 0)], (name, 'rgb hidden'))
-  out = model.apply({'params': fp}, gb, {'alpha': WARP_ALPHA}, rngs=rngs, return_weights=True, bf16=MLP)
-  for lv in out:
-    np.testing.assert_allclose(out[lv]['weights'].cpu().numpy(), ret[lv]['weights'].detach().numpy(), atol=1e-4)
-    np.testing.assert_allclose(out[lv]['rgb'].cpu().numpy(), ret[lv]['rgb'].detach().numpy(), atol=1e-3)
 
 
 @pytest.mark.parametrize('B,kw', CASES)
 def test_bf16_forward_and_stash_match_the_rounded_oracle(B, kw):
   check_forward_and_stash(_setup(B, **kw))
-
-
-def check_backward_given_the_stash(setup):
-  """Step 1b: the dgrad chain and the transposing wgrad kernel against a float64 evaluation of the SAME quantities from
-  the kernels' own forward stash (bfloat16 activations X, bfloat16 d raw, bfloat16 weights, every dpre rounded to
-  bfloat16 before use): all weight / bias gradient leaves to 5e-3 of the leaf's max-abs (measured 5e-5 .. 2e-3: a dpre within
-  float32 rounding of a bfloat16 tie rounds the other way in float64, and at a few thousand rows one such element shows).  (The end-to-end comparison with
-  the rounded oracle is not used for the gradients: the one-ulp rounding ties of step 1a, harmless in the rendered
-  colour, are amplified by the cancellation inside d sigma = T (c_i - C_behind) to percents of the density gradient.)"""
-  from nerfies_amd import params as P
-  spec, p, b, t_rand, u, model, fp, rngs = setup
-  B = b['origins'].shape[0]
-  grad, stats = model.loss_and_grad(fp, H.gpu_batch(b), warp_extra={'alpha': WARP_ALPHA}, rngs=rngs, bf16=MLP)
-  torch.cuda.synchronize()
-  ws = model.workspace(B, True, DEV, bf16=MLP)
-  S = (spec.num_coarse_samples, spec.num_coarse_samples + spec.num_fine_samples)
-  got = P.tree_from_flat(grad.cpu(), model.layout)
-  tw, rw, P_ = spec.nerf_trunk_width, spec.nerf_rgb_branch_width, 3 + 6 * spec.num_nerf_point_freqs
-  q = H.bf16_round
-  worst = ('', 0.0)
-  for lv, name in enumerate(('nerf_mlps_coarse', 'nerf_mlps_fine') if spec.num_fine_samples > 0 else ('nerf_mlps_coarse',)):
-    rows = B * S[lv]
-    prm = O.tree_map(lambda t: t.float().double(), p[name])     # the float32 master weights
-    W = lambda path: H.leaf(prm, path)
-    pe = H.bf16_stash(model, ws, 'b_pe', lv, 1, 2, rows)[0][:, :P_]
-    h = H.bf16_stash(model, ws, 'b_h', lv, 8, 8, rows)
-    h = [t[:, :tw] for t in h]
-    bn = H.bf16_stash(model, ws, 'b_bn', lv, 1, 8, rows)[0][:, :tw]
-    rgbh = H.bf16_stash(model, ws, 'b_rgbh', lv, 1, 4, rows)[0][:, :rw]
-    draw = H.bf16_stash(model, ws, 'b_dsmall', lv, 1, 2, rows)[0][:, :4]
-    dlog, dsig = draw[:, :3], draw[:, 3:4]
-    want = {}
-    want['MLP_1/logit/kernel'], want['MLP_1/logit/bias'] = rgbh.T @ dlog, dlog.sum(0)
-    want['MLP_2/logit/kernel'], want['MLP_2/logit/bias'] = h[7].T @ dsig, dsig.sum(0)
-    d = q((dlog @ q(W('MLP_1/logit/kernel')).T) * (rgbh > 0))
-    want['MLP_1/hidden_0/kernel[:tw]'], want['MLP_1/hidden_0/bias'] = bn.T @ d, d.sum(0)
-    d = q(d @ q(W('MLP_1/hidden_0/kernel')[:tw]).T)
-    want['bottleneck/kernel'], want['bottleneck/bias'] = h[7].T @ d, d.sum(0)
-    wa = W('MLP_2/logit/kernel')[:tw]
-    wa = q(wa) + q(wa - q(wa))                                  # the alpha row is a (hi, lo) bfloat16 pair
-    d = q((d @ q(W('bottleneck/kernel')).T + dsig @ wa.T) * (h[7] > 0))
-    dpre = {}
-    for l in range(7, -1, -1):
-      dpre[l] = d
-      x = h[l - 1] if l > 0 else pe
-      wk = W(f'MLP_0/hidden_{l}/kernel')
-      gk = x.T @ d
-      if l == 4:
-        gk = torch.cat([gk, pe.T @ d], 0)
-      want[f'MLP_0/hidden_{l}/kernel'], want[f'MLP_0/hidden_{l}/bias'] = gk, d.sum(0)
-      if l > 0:
-        d = q((d @ q(wk[:tw]).T) * (h[l - 1] > 0))
-    for path, w in want.items():
-      sl = path.endswith('[:tw]')
-      have = H.leaf(got[name], path.replace('[:tw]', '')).double()
-      have = have[:tw] if sl else have
-      scale = max(w.abs().max().item(), 1e-30)
-      err = (have.reshape(w.shape) - w).abs().max().item() / scale
-      worst = max(worst, (f'{name}/{path}', err), key=lambda t: t[1])
-      assert err < 5e-3, (name, path, err, scale)
-    if spec.use_warp:   # d points = chain rule of the posenc applied to d posenc = dpre_0 . W0^T + dpre_4 . W4[256:]^T
-      rows_pad = (rows + 63) // 64 * 64
-      x = torch.from_numpy(H._ws_words(model, ws, 'wpoints', lv, rows_pad * 3).view('float32').reshape(rows_pad, 3)[:rows].copy()).double()
-      have = torch.from_numpy(H._ws_words(model, ws, 'd_points', lv, rows_pad * 3).view('float32').reshape(rows_pad, 3)[:rows].copy()).double()
-      dpe = dpre[0] @ q(W('MLP_0/hidden_0/kernel')).T + dpre[4] @ q(W('MLP_0/hidden_4/kernel')[tw:]).T
-      dx = dpe[:, :3].clone()
-      for f in range(spec.num_nerf_point_freqs):
-        a = (x.float() * float(2 ** f)).double()
-        dx += 2.0 ** f * (torch.cos(a) * dpe[:, 3 + 6 * f:6 + 6 * f] - torch.sin(a) * dpe[:, 6 + 6 * f:9 + 6 * f])
-      err = (have - dx).abs().max().item() / dx.abs().max().item()
-      worst = max(worst, (f'{name}/d_points', err), key=lambda t: t[1])
-      assert err < 5e-3, (name, 'd_points', err)
-  print(f'[bf16 backward given the stash, B={B}] worst leaf {worst[0]}: {worst[1]:.2e}')
-  return grad
 
 
 @pytest.mark.parametrize('B,kw', CASES)
