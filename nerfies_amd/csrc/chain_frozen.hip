@@ -3,8 +3,9 @@
 //   forward  (64- and 32-row tiles): the posenc stash and the ReLU sign words, no activation stash (nerf_chain.h fwd_tile<., STASH_BITS>);
 //   reverse  (64-row tiles):         d_points and dray, no dY image, no bias column sums -- none of the 23 cross-tile accumulators
 //                                    of BwdAcc, nothing to flush, small_part untouched (nerf_chain.h bwd_tile<., ., false>).
-// The tile bodies are those of mlp_chain.hip / mlp_chain32.hip; the kernels live in a translation unit of their own so that the
-// instantiations serving every other plan are compiled from unchanged kernels.
+// The tile bodies are those of mlp_chain.hip / mlp_chain32.hip (nerf_chain.h), instantiated on compile-time modes, as are the density
+// kernels of chain_query.hip / chain_query_grad.hip (fwd_tile's DENSITY, bwd_tile's DENS); the kernels of one kind of plan share a
+// translation unit.
 #include "nerf_chain.h"
 
 namespace nrf {

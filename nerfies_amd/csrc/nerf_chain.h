@@ -258,9 +258,16 @@ struct ChainFwdArgs1 { ChainFwdArgs a[1]; };
 // One tile of the forward chain: 64-row tile `tile`, or its half T on 32-row tiles.  STAMP() marks a phase boundary for the
 // in-kernel timeline of the 64-row kernel (a no-op otherwise).  STASH (chain_common.h): STASH_BITS keeps the posenc stash and the
 // sign words and stores no activation.
-template <class G, int STASH, class Stamp>
+// DENSITY (field queries, chain_query.hip / chain_query_grad.hip; 64-row tiles): the tile ends at the alpha head.  It runs the prologue,
+// the posenc stash (if STASH), the eight trunk layers and the head -- a use_alpha_condition model also the bottleneck layer its head
+// reads, unstashed, and the per-group code term -- and stores sigma[rows] = sigma_activation(raw) (may be nullptr) and, if STASH,
+// dsig[ntiles * 64] = sigma'(raw), the start of bwd_tile<., ., false, true>.  No rgb branch, logits or noise term; every rounding of
+// a row's sigma is the full chain's, so the two give the same bits.  A density launch reads params / po / wpk / pk / points / rows /
+// ntiles / F / P / PK / skip / sigma_act / alpha_ct, S and B with alpha_ct, st_pe and bits_trunk with STASH.
+template <class G, int STASH, bool DENSITY = false, class Stamp>
 __device__ __forceinline__ void fwd_tile(const ChainFwdArgs& A, const int tile, const int T, float* smem, const int tid0, const int wave,
-                                         Stamp& STAMP) {
+                                         Stamp& STAMP, float* __restrict__ sigma = nullptr, float* __restrict__ dsig = nullptr) {
+  static_assert(G::FULL || !DENSITY, "density mode: 64-row tiles only (the 32-row K loop spills, profiles/field_query.md)");
   constexpr int ROWS = G::ROWS;
   float* act = smem;                  // [256][ROWS] swizzled
   float* pe = smem + TRUNK_W * ROWS;  // [max(PK, G::SCRATCH_ROWS)][ROWS]; reused as scratch after the skip layer
@@ -283,7 +290,7 @@ __device__ __forceinline__ void fwd_tile(const ChainFwdArgs& A, const int tile, 
     int r = row0 + p;
     r = r < A.rows ? r : A.rows - 1;
     float x[3];
-    if (A.points) {
+    if (DENSITY || A.points) {   // a density launch always has points
       x[0] = A.points[3 * r]; x[1] = A.points[3 * r + 1]; x[2] = A.points[3 * r + 2];
     } else {
       const int ray = r / A.S;
@@ -379,6 +386,25 @@ __device__ __forceinline__ void fwd_tile(const ChainFwdArgs& A, const int tile, 
   if (!A.alpha_ct) alpha_head();
 
   STAMP();   // alpha head done
+  // ---- density mode: the tile ends here.  Only a use_alpha_condition model's head reads the bottleneck; nothing is kept of it ----
+  if constexpr (DENSITY) {
+    if (A.alpha_ct) {
+      bias_set<2>(acc, bnext);
+      G::template k_loop<2, true>(acc, act, 16, wpk4 + (A.pk.fwd_bn / 4) + wave * 64 * 64, lane, wnext);
+      __builtin_amdgcn_sched_barrier(0);
+      fwd_epilogue<2, EPI_LINEAR, STASH_NONE, G>(acc, wave * 64, act, make_rsrc(nullptr, FRAG_TILE_256 * 4), 0, nullptr, lane, T);
+      alpha_head();
+      if (part == 0) sigma_raw += A.alpha_ct[min((row0 + p) / A.S, A.B - 1)];
+    }
+    if (part == 0) {
+      const float sg = sigma_activation(sigma_raw, A.sigma_act);
+      if (sigma != nullptr && row0 + p < A.rows) sigma[(size_t)row0 + p] = sg;
+      // sigma'(raw): softplus' = sigmoid(raw) = 1 - exp(-sigma) from the activated value (ray_kernels.hip composite_bwd), relu'
+      if constexpr (STASH != STASH_NONE) dsig[(size_t)row0 + p] = A.sigma_act == 1 ? -expm1f(-sg) : (sg > 0.f ? 1.f : 0.f);
+    }
+    __syncthreads();   // scratch (aliases pe) is free again for the next tile's prologue
+    return;
+  }
   // ---- bottleneck: Dense(256), no activation (modules.py:149-150) ----
   bias_set<2>(acc, bnext);
   G::template k_loop<2, true>(acc, act, 16, wpk4 + (A.pk.fwd_bn / 4) + wave * 64 * 64, lane, wnext);
@@ -569,8 +595,16 @@ __device__ __forceinline__ float bwd_epilogue(Src src, bool add_ds, const float*
 // One tile of level A (tile = index inside the level; T = its half on 32-row tiles).  C: BwdAcc on 64-row tiles.
 // DY = false (frozen-field plans, NRF_FLAG_FROZEN: the reverse pass stops at the rays): the chain still forms every dpre tile in
 // LDS, accumulates dray and writes d_points, but stores no dY image and keeps no bias column sum (C: NoBwdAcc; small_part unused).
-template <class G, class Acc, bool DY = true>
-__device__ __forceinline__ void bwd_tile(const ChainBwdArgs& A, const int tile, const int T, float* smem, Acc& C) {
+// DENS (gradient queries, chain_query_grad.hip; 64-row tiles, DY = false): the reverse starts at the density.  dsig [ntiles * 64] =
+// sigma'(raw) (fwd_tile<., STASH_BITS, true>) takes the place of d sigma_raw and there is no d rgb: no logit^T, rgb branch, per-ray
+// sums or d-bottleneck GEMM.  ds enters at the alpha head -- dpre_7 = mask_7(ds (x) w_alpha) needs no GEMM; a use_alpha_condition
+// model: d bn = ds (x) w_alpha[0:256], then the W_bn^T step -- and runs down the trunk and through the d-posenc section as it stands.
+// Nothing is accumulated across rows, so there is no atomic and a row's gradient does not depend on the launch it ran in.  A density
+// launch reads params / po / wpk / pk / rows / ntiles / bits_trunk / d_points (always set) / st_pe / F / P / PK / skip / alpha_on_bn.
+template <class G, class Acc, bool DY = true, bool DENS = false>
+__device__ __forceinline__ void bwd_tile(const ChainBwdArgs& A, const int tile, const int T, float* smem, Acc& C,
+                                         const float* __restrict__ dsig = nullptr) {
+  static_assert(!DENS || (G::FULL && !DY), "density start: 64-row tiles (the d-points section), no dY image, no bias sums");
   constexpr int ROWS = G::ROWS;
   constexpr bool REGS = G::BIAS_IN_REGS && DY;    // bias column sums in the workgroup's registers ...
   constexpr bool ATOM = !G::BIAS_IN_REGS && DY;   // ... or added to its small_part slice
@@ -587,127 +621,134 @@ __device__ __forceinline__ void bwd_tile(const ChainBwdArgs& A, const int tile, 
   const int wv = wave * 2 * 8 * 1024;                           // bytes: this wave's slice of a tile
   [[maybe_unused]] float* sp = A.small_part + (size_t)blockIdx.x * SMALL_PART;
   const auto no_mask = [](const float4& v, int) { return v; };
-  // ---- d raw of the tile rows -> LDS; its column sums are the logit / alpha bias gradients ----
-  if (tid < ROWS) {
-    const float4 d = A.d_raw4[(size_t)row0 + tid];
-    dr[tid] = d.x; dr[ROWS + tid] = d.y; dr[2 * ROWS + tid] = d.z; dr[3 * ROWS + tid] = d.w;
-    if constexpr (REGS) { C.dsum[0] += d.x; C.dsum[1] += d.y; C.dsum[2] += d.z; C.dsum[3] += d.w; }
-  } else if (ATOM && tid >= 64 && tid < 64 + ROWS) {   // wave 1, lanes 0..31 sum the columns
-    const float4 d = A.d_raw4[(size_t)row0 + tid - 64];
-    float s0 = d.x, s1 = d.y, s2 = d.z, s3 = d.w;
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o); s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); s3 += __shfl_xor(s3, o); }
-    if (tid == 64) {
-      atomicAdd(sp + SP_DB_LOGIT, s0); atomicAdd(sp + SP_DB_LOGIT + 1, s1); atomicAdd(sp + SP_DB_LOGIT + 2, s2);
-      atomicAdd(sp + SP_DB_ALPHA, s3);
+  if constexpr (DENS) {
+    // ---- density start: sigma'(raw) of the tile rows -> the d sigma_raw row (read behind the next barrier) ----
+    if (tid < ROWS) dr[3 * ROWS + tid] = dsig[(size_t)row0 + tid];
+  } else {
+    // ---- d raw of the tile rows -> LDS; its column sums are the logit / alpha bias gradients ----
+    if (tid < ROWS) {
+      const float4 d = A.d_raw4[(size_t)row0 + tid];
+      dr[tid] = d.x; dr[ROWS + tid] = d.y; dr[2 * ROWS + tid] = d.z; dr[3 * ROWS + tid] = d.w;
+      if constexpr (REGS) { C.dsum[0] += d.x; C.dsum[1] += d.y; C.dsum[2] += d.z; C.dsum[3] += d.w; }
+    } else if (ATOM && tid >= 64 && tid < 64 + ROWS) {   // wave 1, lanes 0..31 sum the columns
+      const float4 d = A.d_raw4[(size_t)row0 + tid - 64];
+      float s0 = d.x, s1 = d.y, s2 = d.z, s3 = d.w;
+  #pragma unroll
+      for (int o = 16; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o); s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); s3 += __shfl_xor(s3, o); }
+      if (tid == 64) {
+        atomicAdd(sp + SP_DB_LOGIT, s0); atomicAdd(sp + SP_DB_LOGIT + 1, s1); atomicAdd(sp + SP_DB_LOGIT + 2, s2);
+        atomicAdd(sp + SP_DB_ALPHA, s3);
+      }
     }
-  }
-  __syncthreads();
+    __syncthreads();
 
-  // ---- rgb logit^T (3 -> 128) on the VALU, ReLU mask of the rgb hidden layer ----
-  {
-    int ln = lane;
-    asm volatile("" : "+v"(ln));   // section-local lane constants (see the d posenc section)
-    const int lane = ln, j = ln & 31, h = ln >> 5;
-    const int n = wave * 32 + j;
-    const float w0 = prm[A.po.logit_k + 3 * n], w1 = prm[A.po.logit_k + 3 * n + 1], w2 = prm[A.po.logit_k + 3 * n + 2];
-    // the logits read the LAST rgb layer: layer nx's mask, dY image and bias partial when the branch is deeper than one layer
-    const int nx = G::FULL ? A.nx : 0;
-    const size_t xt = nx ? (size_t)(nx - 1) * A.ntiles + tile : 0;
-    const auto mb = G::template mask_load<1>(nx ? A.bits_rgbx + (xt * 4 + wave) * 64 : A.bits_rgbh + ((size_t)tile * 4 + wave) * 64, lane);
-    const __amdgpu_buffer_rsrc_t dy =
-        make_rsrc(nx ? A.dy_rgbx + xt * FRAG_TILE_128 : A.dy_rgbh + (size_t)tile * FRAG_TILE_128, FRAG_TILE_128 * 4);
-    float bsum = 0.f;
-    if constexpr (REGS) bsum = nx ? 0.f : C.db_rgbh;
-    bsum = bwd_epilogue<G, DY>(
-        [&](int, int g) {
-          const float4 d0 = *reinterpret_cast<const float4*>(dr + 4 * g);
-          const float4 d1 = *reinterpret_cast<const float4*>(dr + ROWS + 4 * g);
-          const float4 d2 = *reinterpret_cast<const float4*>(dr + 2 * ROWS + 4 * g);
-          // d0 w0 + d1 w1 + d2 w2 with the rounding steps spelled out (one product, two fused multiply-adds): left to the
-          // compiler's contraction, the grouping depends on the code around it, and every tiling must produce the same bits
-          auto dot3 = [&](float a0, float a1, float a2) { return fmaf(a2, w2, fmaf(a0, w0, __fmul_rn(a1, w1))); };
-          return make_float4(dot3(d0.x, d1.x, d2.x), dot3(d0.y, d1.y, d2.y), dot3(d0.z, d1.z, d2.z), dot3(d0.w, d1.w, d2.w));
-        },
-        false, nullptr, 0.f, [&](const float4& v, int q) { return mask4(v, G::template mask_nibble<1>(mb, 0, T, q, h)); }, bsum, n, act, dy,
-        wave * 8 * 1024, lane, T);
-    if constexpr (REGS) {
-      if (nx) rgbx_bias_add(A, nx - 1, n, h, bsum);
-      else C.db_rgbh = bsum;
-    } else if constexpr (ATOM) {
-      bias32_add(sp + SP_DB_RGBH + n, bsum, h);
-    }
-  }
-  __syncthreads();
-  // ---- rgb branch layers nx..1 (none for a depth-1 branch):  dpre_{x-1} = (dpre_x . W_x^T) * mask_{x-1}; dpre_0 lands where the
-  //      depth-1 chain leaves it (LDS tile, dy_rgbh, db_rgbh), so everything below is the same for every depth.  64-row tiles only ----
-  if constexpr (G::FULL) {
-#pragma unroll 1
-    for (int x = A.nx; x >= 1; --x) {
-      f32x16 acc1[G::RB][1];
-      zero_acc<1>(acc1);
-      {
-        const float4* wx = wpk4 + ((A.pk.bwd_rgbxT + (x - 1) * RGB_W * RGB_W) / 4) + wave * 16 * 64;
-        G::template k_loop<1, true>(acc1, act, 8, wx, lane, prefetch_quad<1>(wx, lane));
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      const size_t xt = x > 1 ? (size_t)(x - 2) * A.ntiles + tile : 0;
-      const __amdgpu_buffer_rsrc_t dy =
-          make_rsrc(x > 1 ? A.dy_rgbx + xt * FRAG_TILE_128 : A.dy_rgbh + (size_t)tile * FRAG_TILE_128, FRAG_TILE_128 * 4);
-      __syncthreads();   // every wave has read dpre_x
-      int le = tid;
-      asm volatile("" : "+v"(le));   // epilogue-local lane constants
-      const int lane = le & 63, j = lane & 31, h = lane >> 5;
+    // ---- rgb logit^T (3 -> 128) on the VALU, ReLU mask of the rgb hidden layer ----
+    {
+      int ln = lane;
+      asm volatile("" : "+v"(ln));   // section-local lane constants (see the d posenc section)
+      const int lane = ln, j = ln & 31, h = ln >> 5;
       const int n = wave * 32 + j;
-      const auto mb = G::template mask_load<1>(x > 1 ? A.bits_rgbx + (xt * 4 + wave) * 64 : A.bits_rgbh + ((size_t)tile * 4 + wave) * 64, lane);
-      [[maybe_unused]] const float bsum = bwd_epilogue<G, DY>(
-          [&](int q, int) { return G::template piece<1>(acc1, 0, q); }, false, nullptr, 0.f,
-          [&](const float4& v, int q) { return mask4(v, G::template mask_nibble<1>(mb, 0, T, q, h)); }, 0.f, n, act, dy, wave * 8 * 1024, lane, T);
+      const float w0 = prm[A.po.logit_k + 3 * n], w1 = prm[A.po.logit_k + 3 * n + 1], w2 = prm[A.po.logit_k + 3 * n + 2];
+      // the logits read the LAST rgb layer: layer nx's mask, dY image and bias partial when the branch is deeper than one layer
+      const int nx = G::FULL ? A.nx : 0;
+      const size_t xt = nx ? (size_t)(nx - 1) * A.ntiles + tile : 0;
+      const auto mb = G::template mask_load<1>(nx ? A.bits_rgbx + (xt * 4 + wave) * 64 : A.bits_rgbh + ((size_t)tile * 4 + wave) * 64, lane);
+      const __amdgpu_buffer_rsrc_t dy =
+          make_rsrc(nx ? A.dy_rgbx + xt * FRAG_TILE_128 : A.dy_rgbh + (size_t)tile * FRAG_TILE_128, FRAG_TILE_128 * 4);
+      float bsum = 0.f;
+      if constexpr (REGS) bsum = nx ? 0.f : C.db_rgbh;
+      bsum = bwd_epilogue<G, DY>(
+          [&](int, int g) {
+            const float4 d0 = *reinterpret_cast<const float4*>(dr + 4 * g);
+            const float4 d1 = *reinterpret_cast<const float4*>(dr + ROWS + 4 * g);
+            const float4 d2 = *reinterpret_cast<const float4*>(dr + 2 * ROWS + 4 * g);
+            // d0 w0 + d1 w1 + d2 w2 with the rounding steps spelled out (one product, two fused multiply-adds): left to the
+            // compiler's contraction, the grouping depends on the code around it, and every tiling must produce the same bits
+            auto dot3 = [&](float a0, float a1, float a2) { return fmaf(a2, w2, fmaf(a0, w0, __fmul_rn(a1, w1))); };
+            return make_float4(dot3(d0.x, d1.x, d2.x), dot3(d0.y, d1.y, d2.y), dot3(d0.z, d1.z, d2.z), dot3(d0.w, d1.w, d2.w));
+          },
+          false, nullptr, 0.f, [&](const float4& v, int q) { return mask4(v, G::template mask_nibble<1>(mb, 0, T, q, h)); }, bsum, n, act, dy,
+          wave * 8 * 1024, lane, T);
       if constexpr (REGS) {
-        if (x > 1) rgbx_bias_add(A, x - 2, n, h, bsum);
-        else C.db_rgbh += bsum;
+        if (nx) rgbx_bias_add(A, nx - 1, n, h, bsum);
+        else C.db_rgbh = bsum;
+      } else if constexpr (ATOM) {
+        bias32_add(sp + SP_DB_RGBH + n, bsum, h);
       }
-      __syncthreads();
     }
-  }
-  // ---- per-ray sums of dpre_rgbh (gradient of the per-ray condition columns of the rgb branch):
-  //      thread (n, half) walks ROWS / 2 tile rows of feature n in LDS and flushes at ray boundaries ----
-  {
-    int t2 = tid;
-    asm volatile("" : "+v"(t2));
-    const int n = t2 & 127, hf = t2 >> 7;
-    const int r0 = ROWS / 2 * hf;
-    int ray = (row0 + r0) / A.S;
-    int nextb = (ray + 1) * A.S - row0;   // first tile row of the next ray
-    const int nvalid = A.rows - row0;      // tile rows >= nvalid are padding
-    float ray_sum = 0.f;
-#pragma unroll 1
-    for (int g = r0 / 4; g < r0 / 4 + ROWS / 8; ++g) {
-      const float4 v4 = *reinterpret_cast<const float4*>(act + G::addr(n, g));
-      const float v[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int pr = 4 * g + e;
-        while (pr >= nextb) {
-          if (ray < A.B && ray_sum != 0.f) atomicAdd(A.dray + (size_t)ray * RGB_W + n, ray_sum);
-          ray_sum = 0.f; ++ray; nextb += A.S;
+    __syncthreads();
+    // ---- rgb branch layers nx..1 (none for a depth-1 branch):  dpre_{x-1} = (dpre_x . W_x^T) * mask_{x-1}; dpre_0 lands where the
+    //      depth-1 chain leaves it (LDS tile, dy_rgbh, db_rgbh), so everything below is the same for every depth.  64-row tiles only ----
+    if constexpr (G::FULL) {
+  #pragma unroll 1
+      for (int x = A.nx; x >= 1; --x) {
+        f32x16 acc1[G::RB][1];
+        zero_acc<1>(acc1);
+        {
+          const float4* wx = wpk4 + ((A.pk.bwd_rgbxT + (x - 1) * RGB_W * RGB_W) / 4) + wave * 16 * 64;
+          G::template k_loop<1, true>(acc1, act, 8, wx, lane, prefetch_quad<1>(wx, lane));
         }
-        if (pr < nvalid) ray_sum += v[e];
+        __builtin_amdgcn_sched_barrier(0);
+        const size_t xt = x > 1 ? (size_t)(x - 2) * A.ntiles + tile : 0;
+        const __amdgpu_buffer_rsrc_t dy =
+            make_rsrc(x > 1 ? A.dy_rgbx + xt * FRAG_TILE_128 : A.dy_rgbh + (size_t)tile * FRAG_TILE_128, FRAG_TILE_128 * 4);
+        __syncthreads();   // every wave has read dpre_x
+        int le = tid;
+        asm volatile("" : "+v"(le));   // epilogue-local lane constants
+        const int lane = le & 63, j = lane & 31, h = lane >> 5;
+        const int n = wave * 32 + j;
+        const auto mb = G::template mask_load<1>(x > 1 ? A.bits_rgbx + (xt * 4 + wave) * 64 : A.bits_rgbh + ((size_t)tile * 4 + wave) * 64, lane);
+        [[maybe_unused]] const float bsum = bwd_epilogue<G, DY>(
+            [&](int q, int) { return G::template piece<1>(acc1, 0, q); }, false, nullptr, 0.f,
+            [&](const float4& v, int q) { return mask4(v, G::template mask_nibble<1>(mb, 0, T, q, h)); }, 0.f, n, act, dy, wave * 8 * 1024, lane, T);
+        if constexpr (REGS) {
+          if (x > 1) rgbx_bias_add(A, x - 2, n, h, bsum);
+          else C.db_rgbh += bsum;
+        }
+        __syncthreads();
       }
     }
-    if (ray < A.B && ray_sum != 0.f) atomicAdd(A.dray + (size_t)ray * RGB_W + n, ray_sum);
+    // ---- per-ray sums of dpre_rgbh (gradient of the per-ray condition columns of the rgb branch):
+    //      thread (n, half) walks ROWS / 2 tile rows of feature n in LDS and flushes at ray boundaries ----
+    {
+      int t2 = tid;
+      asm volatile("" : "+v"(t2));
+      const int n = t2 & 127, hf = t2 >> 7;
+      const int r0 = ROWS / 2 * hf;
+      int ray = (row0 + r0) / A.S;
+      int nextb = (ray + 1) * A.S - row0;   // first tile row of the next ray
+      const int nvalid = A.rows - row0;      // tile rows >= nvalid are padding
+      float ray_sum = 0.f;
+  #pragma unroll 1
+      for (int g = r0 / 4; g < r0 / 4 + ROWS / 8; ++g) {
+        const float4 v4 = *reinterpret_cast<const float4*>(act + G::addr(n, g));
+        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+  #pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int pr = 4 * g + e;
+          while (pr >= nextb) {
+            if (ray < A.B && ray_sum != 0.f) atomicAdd(A.dray + (size_t)ray * RGB_W + n, ray_sum);
+            ray_sum = 0.f; ++ray; nextb += A.S;
+          }
+          if (pr < nvalid) ray_sum += v[e];
+        }
+      }
+      if (ray < A.B && ray_sum != 0.f) atomicAdd(A.dray + (size_t)ray * RGB_W + n, ray_sum);
+    }
   }
 
   f32x16 acc[G::RB][2];
-  // ---- d bottleneck = dpre_rgbh . W_rgbh[0:256]^T   (K=128 -> N=256), linear ----
+  // ---- d bottleneck = dpre_rgbh . W_rgbh[0:256]^T   (K=128 -> N=256), linear.  Density start: there is no d rgb, so d bn is the
+  //      alpha head's term alone (use_alpha_condition: zero accumulators + ds (x) w_alpha[0:256]) or not formed at all ----
   zero_acc<2>(acc);
-  {
+  if constexpr (!DENS) {
     const float4* w0 = wpk4 + (A.pk.bwd_rgbhT / 4) + wave * 32 * 64;
     G::template k_loop<2, true>(acc, act, 8, w0, lane, prefetch_quad<2>(w0, lane));
   }
-  WQuad<2> wnext = prefetch_quad<2>(wpk4 + (A.pk.bwd_bnT / 4) + wave * 64 * 64, lane);
+  // the next GEMM's first weights: W_bn^T, or (density start, the head on the trunk) W_7^T
+  WQuad<2> wnext = prefetch_quad<2>(wpk4 + ((DENS && !A.alpha_on_bn ? A.pk.bwd_LT[TRUNK_DEPTH - 1] : A.pk.bwd_bnT) / 4) + wave * 64 * 64, lane);
   __builtin_amdgcn_sched_barrier(0);
-  {
+  if (!DENS || A.alpha_on_bn) {
     const __amdgpu_buffer_rsrc_t dy = make_rsrc(A.dy_bn + (size_t)tile * FRAG_TILE_256, FRAG_TILE_256 * 4);
     __syncthreads();
     int le = tid;
@@ -733,7 +774,9 @@ __device__ __forceinline__ void bwd_tile(const ChainBwdArgs& A, const int tile, 
     const auto mb = G::template mask_load<2>(A.bits_trunk + (((size_t)(l - 1) * A.ntiles + tile) * 4 + wave) * 128, lane);
     zero_acc<2>(acc);
     const int woff = (l == TRUNK_DEPTH) ? A.pk.bwd_bnT : A.pk.bwd_LT[l];
-    G::template k_loop<2, true>(acc, act, 16, wpk4 + (woff / 4) + wave * 64 * 64, lane, wnext);
+    // density start, the head on the trunk: the l = 8 step is the head's own term, ds (x) w_alpha on zero accumulators -- nothing to multiply
+    if (!DENS || l < TRUNK_DEPTH || A.alpha_on_bn)
+      G::template k_loop<2, true>(acc, act, 16, wpk4 + (woff / 4) + wave * 64 * 64, lane, wnext);
     wnext = prefetch_quad<2>(wpk4 + (A.pk.bwd_LT[l > 1 ? l - 1 : 1] / 4) + wave * 64 * 64, lane);
     __builtin_amdgcn_sched_barrier(0);
     const __amdgpu_buffer_rsrc_t dy =
