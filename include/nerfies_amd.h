@@ -662,7 +662,10 @@ int nrf_debug_wgrad_segments(nrf_handle h, const void* workspace, double* out, i
 /* Test aid: float offset inside the workspace of an internal buffer of `level` (0 coarse, 1 fine, 2 background
  * points, 3 Jacobian tangents) for the last planned (num_rays, flags): "st_pe", "st_h", "st_bn", "st_rgbh",
  * "dy_trunk", "dy_bn", "dy_rgbh", "d_raw4", "z", "out4", "wpoints", "d_points", "w_st_win", "w_st_h", "w_st_wv",
- * "w_dy", "w_dw4", "w_dv4", "bits_trunk", "bits_rgbh", "w_bits"; with nerf_rgb_branch_depth = D > 1 also "st_rgbx", "bits_rgbx",
+ * "w_dy", "w_dw4", "w_dv4", "bits_trunk", "bits_rgbh", "w_bits", "points_raw" (the unwarped sample points, [rows][3]),
+ * "weights" (the per-sample compositing weights, [rows]), "el_dw4", "el_dv4" (level 0 under the elastic regulariser: its
+ * gradient w.r.t. the primal SE3 head outputs, [rows] float4; the gradient w.r.t. the head tangents is "w_dw4" / "w_dv4" of
+ * level 3, row c * padded_rows + r for d/dx_c); with nerf_rgb_branch_depth = D > 1 also "st_rgbx", "bits_rgbx",
  * "dy_rgbx": the rgb branch layers 1..D-1 as [D-1][tiles] images of the "st_rgbh" / "bits_rgbh" / "dy_rgbh" kind (those keep meaning layer 0).
  * Stash tiles are [features][64 rows] in fragment order (csrc/chain_common.h frag_index); the ReLU sign bits are one
  * uint32 per (tile, wave, lane, column block): nibble q, bit e <-> tile row 4 * ((q&1) + 2*(lane>>5) + 4*(q>>1)) + e of

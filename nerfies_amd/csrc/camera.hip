@@ -474,7 +474,7 @@ __global__ __launch_bounds__(CAM_THREADS) void camera_table_reduce_kernel(TableW
 }
 
 // ---- camera delta tables (nrf_camera_table_compose*): one thread per camera.  The rotation is the SE3 field's closed form with
-// v = 0 on the columns of R0 (se3_math.h: the theta^2 series below |omega|^2 = 0.04), so value and VJP are exact at omega = 0.
+// v = 0 on the columns of R0 (se3_math.h: the theta^2 series below |omega|^2 = 4), so value and VJP are exact at omega = 0.
 constexpr int ND = NRF_CAMERA_DELTA_ROW;
 
 __global__ __launch_bounds__(CAM_THREADS) void camera_compose_kernel(const float* __restrict__ cameras, const float* __restrict__ deltas,

@@ -419,7 +419,7 @@ int nrf_debug_ws_offset(nrf_handle h, const char* name, int32_t level, int64_t* 
       {"b_pe", L.b_pe}, {"b_h", L.b_h}, {"b_bn", L.b_bn}, {"b_rgbh", L.b_rgbh}, {"b_bits", L.b_bits}, {"b_dy", L.b_dy},
       {"b_dbn", L.b_dbn}, {"b_drgbh", L.b_drgbh}, {"b_dsmall", L.b_dsmall},
       {"bw_in", L.bw_in}, {"bw_h", L.bw_h}, {"bw_bits", L.bw_bits}, {"bw_dy", L.bw_dy}, {"bw_dhead", L.bw_dhead},
-      {"points_raw", L.points_raw},
+      {"points_raw", L.points_raw}, {"weights", L.weights}, {"el_dw4", L.el_dw4}, {"el_dv4", L.el_dv4},
       {"bg_points", h->plan.bg_points}, {"bg_ids", h->plan.bg_ids},
       {"timeline", h->plan.timeline + (size_t)(level & 1) * TIMELINE_LEVEL_F}};
   for (const auto& t : tab)

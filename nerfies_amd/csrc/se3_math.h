@@ -46,19 +46,23 @@ template <typename T> __device__ __forceinline__ V3T<T> cross(V3T<T> a, V3T<T> b
 // derivatives  dA/dw = Ab w,  dB/dw = Bb w,  dC/dw = Cb w  with
 //   Ab = C - B (= (t cos t - sin t)/t^3),  Bb = (A - 2B)/t^2,  Cb = (B - 3C)/t^2.
 // The reference evaluates the un-simplified normalised-axis form in fp32 (rigid_body.py:54-89),
-// whose 1-cos / t-sin terms cancel catastrophically for small angles and are NaN at t = 0; here
-// small angles use the Taylor series, so the result tracks the exact value to fp32 rounding.
+// whose 1-cos / t-sin terms cancel catastrophically for small angles and are NaN at t = 0.  So do C, Bb and Cb above when t is not
+// large: each is a difference of nearly equal numbers over a power of t, and at t = 0.2 Cb keeps three digits.  Below t2 = 4 every
+// coefficient is therefore its own series in t2 (sum_n (-t2)^n / (2n+k)! and its derivatives, cut where the next term is below a
+// quarter ulp at t2 = 4); from t2 = 4 on the differences lose a digit at most (tests/test_se3_math_host.py sweeps both sides).
+constexpr float SE3_SERIES_T2 = 4.f;       // below: series for all;  from here on: closed forms, except
+constexpr float SE3_SERIES_DCB_T2 = 9.f;   // dCb (two differences deep), which stays a series up to here
 template <typename T> struct Se3Coef { T A, B, C, Ab, Bb, Cb; };
 template <typename T>
 __device__ __forceinline__ Se3Coef<T> se3_coef(T t2) {
   Se3Coef<T> c;
-  if (val(t2) < 0.04f) {
-    c.A = T(1.f) + t2 * (T(-1.f / 6.f) + t2 * (T(1.f / 120.f) + t2 * T(-1.f / 5040.f)));
-    c.B = T(0.5f) + t2 * (T(-1.f / 24.f) + t2 * (T(1.f / 720.f) + t2 * T(-1.f / 40320.f)));
-    c.C = T(1.f / 6.f) + t2 * (T(-1.f / 120.f) + t2 * (T(1.f / 5040.f) + t2 * T(-1.f / 362880.f)));
-    c.Ab = T(-1.f / 3.f) + t2 * (T(1.f / 30.f) + t2 * (T(-1.f / 840.f) + t2 * T(1.f / 45360.f)));
-    c.Bb = T(-1.f / 12.f) + t2 * (T(1.f / 180.f) + t2 * (T(-1.f / 6720.f) + t2 * T(1.f / 453600.f)));
-    c.Cb = T(-1.f / 60.f) + t2 * (T(1.f / 1260.f) + t2 * (T(-1.f / 60480.f) + t2 * T(1.f / 4989600.f)));
+  if (val(t2) < SE3_SERIES_T2) {
+    c.A = T(1.f) + t2 * (T(-1.f / 6.f) + t2 * (T(1.f / 120.f) + t2 * (T(-1.f / 5040.f) + t2 * (T(1.f / 362880.f) + t2 * (T(-1.f / 39916800.f) + t2 * T(1.f / 6227020800.f))))));
+    c.B = T(0.5f) + t2 * (T(-1.f / 24.f) + t2 * (T(1.f / 720.f) + t2 * (T(-1.f / 40320.f) + t2 * (T(1.f / 3628800.f) + t2 * (T(-1.f / 479001600.f) + t2 * T(1.f / 87178291200.f))))));
+    c.C = T(1.f / 6.f) + t2 * (T(-1.f / 120.f) + t2 * (T(1.f / 5040.f) + t2 * (T(-1.f / 362880.f) + t2 * (T(1.f / 39916800.f) + t2 * T(-1.f / 6227020800.f)))));
+    c.Ab = T(-1.f / 3.f) + t2 * (T(1.f / 30.f) + t2 * (T(-1.f / 840.f) + t2 * (T(1.f / 45360.f) + t2 * (T(-1.f / 3991680.f) + t2 * (T(1.f / 518918400.f) + t2 * T(-1.f / 93405312000.f))))));
+    c.Bb = T(-1.f / 12.f) + t2 * (T(1.f / 180.f) + t2 * (T(-1.f / 6720.f) + t2 * (T(1.f / 453600.f) + t2 * (T(-1.f / 47900160.f) + t2 * (T(1.f / 7264857600.f) + t2 * T(-1.f / 1494484992000.f))))));
+    c.Cb = T(-1.f / 60.f) + t2 * (T(1.f / 1260.f) + t2 * (T(-1.f / 60480.f) + t2 * (T(1.f / 4989600.f) + t2 * (T(-1.f / 622702080.f) + t2 * T(1.f / 108972864000.f)))));
   } else {
     const T t = sqrt_t(t2);
     T s, co, sh, ch;
@@ -80,20 +84,22 @@ __device__ __forceinline__ Se3Coef<T> se3_coef(T t2) {
 // direction costs six multiplies instead of a second evaluation of the divisions / sincos (round 6: the elastic kernel spent most
 // of its 6 k instructions re-deriving them six times).  From dX/dw = Xb w and dt2/dw = 2 w:
 //   A' = Ab / 2,  B' = Bb / 2,  C' = Cb / 2,  Ab' = (Cb - Bb) / 2,  Bb' = (Ab / 2 - 2 Bb) / t2,  Cb' = (Bb / 2 - 5 Cb / 2) / t2;
-// below t2 = 0.04 Bb' and Cb' are the derivatives of the Taylor polynomials above (no division by a small t2).
+// below the switches Bb' and Cb' are the derivatives of the series above (Cb' is a difference of differences: its closed form has
+// no digit left at t = 0.2 and two at t = 1, and is within the sweep's gate only from t = 3 on).
 struct Se3CoefD { Se3Coef<float> c; float dAb, dBb, dCb; };
 __device__ __forceinline__ Se3CoefD se3_coef_d(float t2) {
   Se3CoefD r;
   r.c = se3_coef<float>(t2);
   r.dAb = 0.5f * (r.c.Cb - r.c.Bb);
-  if (t2 < 0.04f) {
-    r.dBb = 1.f / 180.f + t2 * (-1.f / 3360.f + t2 * (1.f / 151200.f));
-    r.dCb = 1.f / 1260.f + t2 * (-1.f / 30240.f + t2 * (1.f / 1663200.f));
-  } else {
-    const float it2 = 1.f / t2;
+  const float it2 = 1.f / fmaxf(t2, SE3_SERIES_T2);   // read from the switch on only; finite at t2 = 0
+  if (t2 < SE3_SERIES_T2)
+    r.dBb = 1.f / 180.f + t2 * (-1.f / 3360.f + t2 * (1.f / 151200.f + t2 * (-1.f / 11975040.f + t2 * (1.f / 1452971520.f + t2 * (-1.f / 249080832000.f)))));
+  else
     r.dBb = (0.5f * r.c.Ab - 2.f * r.c.Bb) * it2;
+  if (t2 < SE3_SERIES_DCB_T2)
+    r.dCb = 1.f / 1260.f + t2 * (-1.f / 30240.f + t2 * (1.f / 1663200.f + t2 * (-1.f / 155675520.f + t2 * (1.f / 21794572800.f + t2 * (-1.f / 4234374144000.f + t2 * (1.f / 1086116967936000.f))))));
+  else
     r.dCb = (0.5f * r.c.Bb - 2.5f * r.c.Cb) * it2;
-  }
   return r;
 }
 // the Dual coefficients along a direction whose t2 tangent is t2d (= 2 w . wd)

@@ -698,14 +698,26 @@ __global__ __launch_bounds__(256) void elastic_kernel(const ElasticArgs A) {
           const float log_eps = logf(A.eps);
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
-            const float mu = D[k][k], lam = 1.f + mu;
+            float mu = D[k][k], lam = 1.f + mu;
+            bool refined = false;
+            if (lam < 0.5f) {
+              // a singular value below 0.7: 1 + mu is what is left of entries of size |J|^2 (absolute error 6e-8 |J|^2), and
+              // (d sq / d s_k) / s_k ~ 1 / lam makes this the dominant term.  |J v_k|^2 is the same eigenvalue, stationary in v_k, as a
+              // sum of squares (tests/test_gpu_se3_regimes.py).  Below 1e-4 (s_k < 0.01) J is singular to the accuracy of its own
+              // float32 entries and 1 / lam is noise either way: such rows keep the plain value, which cannot come out below 1e-7.
+              const float j0 = Vm[0][k] + (E[0][0] * Vm[0][k] + E[0][1] * Vm[1][k] + E[0][2] * Vm[2][k]);
+              const float j1 = Vm[1][k] + (E[1][0] * Vm[0][k] + E[1][1] * Vm[1][k] + E[1][2] * Vm[2][k]);
+              const float j2 = Vm[2][k] + (E[2][0] * Vm[0][k] + E[2][1] * Vm[1][k] + E[2][2] * Vm[2][k]);
+              const float lr = j0 * j0 + j1 * j1 + j2 * j2;
+              if (lr >= 1e-4f) { lam = lr; mu = lr - 1.f; refined = true; }
+            }
             if (A.loss_type == NRF_ELASTIC_SVALS) {
               const float sk = sqrtf(fmaxf(lam, 0.f)), sm1 = mu / (sk + 1.f);   // s - 1 without cancellation
               sq += sm1 * sm1;
               m[k] = sk > 1e-20f ? 2.f * sm1 / sk : 0.f;
             } else {
               const bool live = lam > A.eps * A.eps;     // s_k > eps (training.py:88)
-              const float ls = live ? 0.5f * log1pf(mu) : log_eps;
+              const float ls = live ? 0.5f * (refined ? logf(lam) : log1pf(mu)) : log_eps;
               sq += ls * ls;
               m[k] = live ? 2.f * ls / lam : 0.f;         // (d sq / d s_k) / s_k
             }

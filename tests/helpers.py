@@ -769,3 +769,123 @@ def assert_d_raw(got, ref, regime, label, last_at_infinity=True):
   assert w_ray <= tol['w_ray'], (label, w_ray)
   assert c_ray <= tol['c_ray'], (label, c_ray)
   return dict(w_rel=worst, held=held, excluded=share, w_ray=w_ray, c_ray=c_ray)
+
+
+# ---------------------------------------------------------------------------------------------
+# Rotation regimes (tests/test_se3_regimes_host.py, tests/test_gpu_se3_regimes.py, profiles/se3_regimes.md)
+#
+# oracle.init_params(trained_like=True) draws the SE3 heads from U[0, 0.3): one unexamined distribution of the rotation angle
+# theta = |w|.  A regime rewrites warp_field/branches_w/logit (kernel x K, a new bias) so that chosen statistics of theta, measured on
+# the float64 oracle over the batch's sample points (both levels), land at chosen values, and scales branches_v so that the median |v|
+# is 0.05 (a capture's deformations, tests/test_gpu_bf16_warp.py).  With u the head's bias-free output minus its mean over the rows and
+# m the direction of that mean, the new head is w = K u + beta m: beta places theta, K spreads it.
+# ---------------------------------------------------------------------------------------------
+ROTATION_REGIMES = ('init', 'tiny', 'seam', 'trained', 'large')
+ROTATION_SHAPE = dict(REGIME_SHAPE, use_warp=True, num_warp_freqs=4, num_warp_features=8)
+ROTATION_SHAPE_3 = dict(REGIME_SHAPE_3, use_warp=True, num_warp_freqs=4, num_warp_features=8)
+ROTATION_ALPHA = 2.5
+V_MEDIAN = 0.05
+_ROTATION_CACHE = {}
+
+
+def _warp_heads(params, spec, batch, alpha=ROTATION_ALPHA):
+  """One float64 oracle evaluation: {level: dict(w (rows,3), v (rows,3))}, the SE3 heads' outputs at the level's sample points."""
+  wf = params['warp_field']
+  key = {id(wf['branches_w']['logit']): 'w', id(wf['branches_v']['logit']): 'v'}
+  seen = {'w': [], 'v': []}
+
+  def hook(p, x):
+    y = x @ p['kernel'] + p['bias']
+    if id(p) in key:
+      seen[key[id(p)]].append(y.detach().reshape(-1, 3))
+    return y
+  with torch.no_grad(), O.dense_hook(hook):
+    O.nerf_model_apply(params, spec, batch, warp_alpha=alpha)
+  assert len(seen['w']) == 2 and len(seen['v']) == 2   # the coarse pass, then the fine pass
+  return {lv: dict(w=seen['w'][i], v=seen['v'][i]) for i, lv in enumerate(LEVELS)}
+
+
+def rotation_stats(heads):
+  """What the regime conditions are stated on: per level, quantiles and shares of theta = |w| over ALL of the level's rows."""
+  out = {}
+  for lv, h in heads.items():
+    th = torch.linalg.norm(h['w'], dim=-1)
+    t2 = th * th
+    n = float(th.numel())
+    share = lambda m: m.sum().item() / n
+    out[lv] = dict(
+        rows=int(n), min=th.min().item(), q10=_quantile(th, 0.10), median=_quantile(th, 0.5), q90=_quantile(th, 0.90), max=th.max().item(),
+        v_median=_quantile(torch.linalg.norm(h['v'], dim=-1), 0.5),
+        init_band=share((th > 1e-6) & (th < 1e-2)), below_015=share(th < 0.15),
+        seam_below=share((t2 >= 0.0256) & (t2 < 0.04)), seam_above=share((t2 >= 0.04) & (t2 <= 0.0625)),
+        seam_rest_ok=share(((t2 >= 0.0256) & (t2 <= 0.0625)) | ((t2 >= 0.01) & (t2 <= 0.09))),
+        below_pi=share(th < np.pi), above_pi=share(th > np.pi))
+  return out
+
+
+# (location statistic, its target, spread statistic, its target) of theta per regime
+_ROTATION_TARGETS = {
+    'tiny': (lambda t: _quantile(t, 0.5), 0.03, lambda t: _quantile(t, 0.95) - _quantile(t, 0.5), 0.06),
+    'seam': (lambda t: _quantile(t, 0.5), 0.2, lambda t: (t - _quantile(t, 0.5)).abs().max().item(), 0.035),
+    'trained': (lambda t: _quantile(t, 0.5), 0.6, lambda t: _quantile(t, 0.9) - _quantile(t, 0.1), 0.7),
+    'large': (lambda t: _quantile(t, 0.5), np.pi, lambda t: t.max().item() - _quantile(t, 0.5), 7.1 - np.pi),
+}
+
+
+def rotation_regime(params, spec, batch, regime):
+  """(tree, stats): `params` (a float64 oracle tree, left untouched) with the SE3 heads rewritten into `regime`, and rotation_stats of
+  the result.  'init' takes the tree as it is (the caller passes the reference initialisation).  No random numbers are drawn."""
+  tree = O.tree_map(lambda t: t.clone(), params)
+  if regime != 'init':
+    loc, t_loc, spread, t_spread = _ROTATION_TARGETS[regime]
+    for _ in range(2):   # the fine depths follow the coarse weights, which follow the warp: place, re-measure, place again
+      wl, vl = tree['warp_field']['branches_w']['logit'], tree['warp_field']['branches_v']['logit']
+      heads = _warp_heads(tree, spec, batch)
+      w = torch.cat([heads[lv]['w'] for lv in LEVELS]) - wl['bias']
+      mean = w.mean(0)
+      m, u = mean / mean.norm(), w - mean
+      K, beta = t_spread / max(spread(u @ m), 1e-30), t_loc
+      for _ in range(50):
+        th = torch.linalg.norm(K * u + beta * m, dim=-1)
+        K, beta = K * t_spread / max(spread(th), 1e-30), beta + t_loc - loc(th)
+      # w = K (kernel^T h - mean) + beta m
+      wl['kernel'], wl['bias'] = wl['kernel'] * K, beta * m - K * mean
+      kv = V_MEDIAN / _quantile(torch.linalg.norm(torch.cat([heads[lv]['v'] for lv in LEVELS]), dim=-1), 0.5)
+      vl['kernel'], vl['bias'] = vl['kernel'] * kv, vl['bias'] * kv
+  stats = rotation_stats(_warp_heads(tree, spec, batch))
+  assert_rotation_regime(regime, stats)
+  return tree, stats
+
+
+def assert_rotation_regime(regime, stats):
+  """The regime's defining conditions on theta, per level, over all of the level's rows (none excluded)."""
+  for lv in LEVELS:
+    s = stats[lv]
+    if regime == 'init':
+      assert s['init_band'] >= 0.90, (lv, s)
+    elif regime == 'tiny':
+      assert 0.01 <= s['median'] <= 0.05 and s['below_015'] >= 0.95, (lv, s)
+    elif regime == 'seam':
+      assert s['seam_below'] >= 0.30 and s['seam_above'] >= 0.30 and s['seam_rest_ok'] == 1.0, (lv, s)
+    elif regime == 'trained':
+      assert 0.2 <= s['q10'] and s['q90'] <= 1.2, (lv, s)
+    elif regime == 'large':
+      assert s['below_pi'] >= 0.20 and s['above_pi'] >= 0.20 and 2 * np.pi <= max(stats[l]['max'] for l in LEVELS) <= 8.0, (lv, s)
+      assert s['max'] <= 8.0, (lv, s)
+    else:
+      raise ValueError(regime)
+    if regime != 'init':
+      assert 0.03 <= s['v_median'] <= 0.08, (lv, s)
+
+
+def rotation_case(regime, three=False):
+  """(spec, B, float64 tree in `regime`, float64 batch, {level: rotation_stats}); B = 7 rays of 24 + 56 samples, or 5 of 64 + 128."""
+  key = (regime, three)
+  if key not in _ROTATION_CACHE:
+    spec = O.ModelSpec(sigma_activation='softplus', **(ROTATION_SHAPE_3 if three else ROTATION_SHAPE))
+    B = 5 if three else 7
+    p64 = O.init_params(spec, seed=REGIME_SEED, trained_like=regime != 'init', dtype=torch.float64)
+    b64 = regime_batch(B)
+    tree, stats = rotation_regime(p64, spec, b64, regime)
+    _ROTATION_CACHE[key] = (spec, B, tree, b64, stats)
+  return _ROTATION_CACHE[key]

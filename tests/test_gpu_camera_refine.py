@@ -145,8 +145,8 @@ def _compose64(table, deltas):
 
 
 def test_compose_against_float64():
-  """Five cameras, |omega| in {0, 1e-7, 1e-3, 0.3, 2.5} (the series and the closed forms of se3_math.h, both sides of
-  |omega|^2 = 0.04).  The intrinsics are of unit magnitude (normalised image coordinates): the forward tolerance is absolute, and
+  """Five cameras, |omega| in {0, 1e-7, 1e-3, 0.3, 2.5} (the series and the closed forms of se3_math.h, which switches at
+  |omega|^2 = 4; tests/test_gpu_se3_regimes.py holds both sides of it to the float32 floor).  The intrinsics are of unit magnitude (normalised image coordinates): the forward tolerance is absolute, and
   float32 itself is 3e-5 apart at a focal length of 500 pixels."""
   from nerfies_amd import camera, lib as L
   g = torch.Generator().manual_seed(11)
