@@ -563,6 +563,56 @@ int nrf_query_grid_grad(nrf_handle h, const float* params, const nrf_rays* group
                         int32_t level, const nrf_step_scalars* scalars, uint32_t flags, const nrf_field_grad_out* out, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---- The warp field inverted: canonical points into a frame (float32 mode) ----
+ * x with W(x; id) = y for canonical targets y: what carries one template surface (a canonical mesh, tracked points) into every
+ * frame with its topology and vertex identity intact.  The field has no closed-form inverse; this is Newton's iteration around
+ * the launches of a gradient query's warp part, on the device, with no host round trip.  Announced by NRF_HAS_UNWARP (NRF_VERSION
+ * is unchanged).
+ *
+ * The algorithm.  x starts at `guess` (NULL: at the target).  Each of num_steps rounds runs the SE3 trunk's primal pass at the
+ * current x keeping its stash (explicit points, one id per point), its forward-mode tangent pass, and one kernel with one thread
+ * per row:
+ *   r = W(x) - y, res = |r|_2 (float32);
+ *   a row that has stopped does nothing;
+ *   res <= tolerance: the row stops as converged;
+ *   else E = J - I from (w, v), their tangents and x (the Dual evaluation of exp_se3 the warp Jacobian output uses), and
+ *     (I + E) dx = r solved in closed form (adjugate over determinant, float32); the Jacobian never goes to memory;
+ *   the determinant 0 or not finite, a component of dx not finite, or x - dx not finite: the row stops (status 2) at its current x;
+ *   else dx is shortened to length max_step if it is longer, and x -= dx.
+ * After the last round one more primal pass -- the same kernel as the rounds', so the bits agree -- gives `residual` and decides
+ * status 0 or 1 at the returned x.  num_steps == 0 returns the guess (or the target) with its residual.  Stopped rows still ride
+ * through the trunk in later rounds: no compaction, a fixed launch sequence whatever the data.  A row's result depends only on its
+ * own target, id (or code row), guess and the scalars -- not on its position or on the other rows.  Where the field folds (a
+ * singular value of J near 0) the iteration may land on another preimage or run out of steps: the status and the residual say so.
+ *
+ * warp_codes == NULL: warp_ids index the model's embedding table.  Else warp_codes is a DEVICE (num_codes, num_warp_features)
+ * table and warp_ids index ITS rows: the field at interpolated, in-between-frame codes.
+ *
+ * Refused before any HIP call, nrf_last_error naming the entry and the rule: a NULL handle, params, targets, warp_ids, scalars, out
+ * or workspace (NRF_E_NULL); a model without a warp field, the time encoder (NRF_E_UNSUPPORTED, as nrf_warp_points); num_points
+ * outside 1..NRF_UNWARP_MAX_POINTS, num_steps outside 0..NRF_UNWARP_MAX_STEPS, tolerance negative or NaN, max_step not positive
+ * (INFINITY: no limit), num_codes <= 0 with warp_codes (NRF_E_SHAPE); a short workspace (NRF_E_WORKSPACE).  Asynchronous on
+ * `stream`, no allocation, no synchronisation, capturable into a hipGraph; a plan of its own (the other plans and the digests of
+ * nrf_debug_plan_digest do not move); handed the workspace of a ray plan it makes the handle forget that plan's upload and stash,
+ * as the queries above. */
+#define NRF_HAS_UNWARP 1
+#define NRF_UNWARP_MAX_POINTS (1 << 20) /* points of one call (the stash is ~0.5 KB per row; callers chunk); more is NRF_E_SHAPE */
+#define NRF_UNWARP_MAX_STEPS 32
+
+/* Device outputs, N = num_points rows each; any may be NULL. */
+typedef struct nrf_unwarp_out {
+  float* points;    /* (N,3) x with W(x; id) ~= target */
+  float* residual;  /* (N,)  |W(x) - target|_2 at the RETURNED x, float32 */
+  int32_t* status;  /* (N,)  0 ran out of steps, 1 converged (residual <= tolerance), 2 stopped: singular or non-finite step */
+} nrf_unwarp_out;
+
+/* Workspace of a call of num_points points.  Needs no GPU. */
+int nrf_unwarp_workspace_bytes(nrf_handle h, int32_t num_points, size_t* bytes);
+/* targets (N,3), warp_ids (N,), guess (N,3) or NULL: device arrays. */
+int nrf_unwarp_points(nrf_handle h, const float* params, const float* targets, const int32_t* warp_ids, const float* warp_codes,
+                      int32_t num_codes, const float* guess, int32_t num_points, const nrf_step_scalars* scalars, int32_t num_steps,
+                      float tolerance, float max_step, const nrf_unwarp_out* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Mesh extraction: a triangle mesh of the level set sigma = threshold of a device density grid (surface nets) ----
  * Handle-free, like the camera tables: the grid may come from nrf_query_grid or from anywhere.  An indexed mesh with shared
  * vertices, the same bits on every run (no atomic, no claimed slot: every output position is a rank in the order below).

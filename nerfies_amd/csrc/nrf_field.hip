@@ -64,6 +64,49 @@ WarpPointsPlan warp_points_plan(nrf_handle h, int n) {
   return q;
 }
 
+// ---- The field inverted (nrf_unwarp_points): Newton's iteration on W(x; id) = y around the SE3 trunk's primal and tangent passes,
+// the launches of a gradient query's warp part.  Workspace, every per-row buffer of ntiles * 64 rows:
+// [pack descriptors | packed trunk | x | trunk-input stash | sign words | (w, v) | tangent (dw, dv) | warped | per-row state ||
+//  embed table, padded params (narrow / translation trunks)]
+// The caller's ids are read where they are (one per point: the kernel's own prologue), and the SE3 kernels hand their tiles out
+// statically: the plan holds no copy of the ids and no tile counter.
+struct UnwarpPlan : PaddedImage {
+  size_t desc_f, wpk_f, x_f, win_f, bits_f, wv_f, twv_f, warped_f, state_f, total_f;
+  int ntiles;
+  size_t rows_pad() const { return (size_t)ntiles * TILE_ROWS; }
+};
+UnwarpPlan unwarp_plan(const nrf_handle_s* h, int n) {
+  UnwarpPlan q;
+  q.ntiles = (n + TILE_ROWS - 1) / TILE_ROWS;
+  const size_t rows_pad = q.rows_pad();
+  const int PKSw = (h->PKw + 31) / 32 * 32;
+  Carve c;
+  q.desc_f = c.take(16 * sizeof(PackDesc) / 4);
+  q.wpk_f = c.take(h->wpk.total);
+  q.x_f = c.take(rows_pad * 3);
+  q.win_f = c.take((size_t)q.ntiles * PKSw * TILE_ROWS);
+  q.bits_f = c.take((size_t)WARP_DEPTH * q.ntiles * 4 * 64);
+  q.wv_f = c.take(rows_pad * 8);
+  q.twv_f = c.take(3 * rows_pad * 8);   // 3 tangent tiles per primal tile
+  q.warped_f = c.take(rows_pad * 3);
+  q.state_f = c.take(rows_pad);
+  if (h->d.warp_field_type == NRF_WARP_TRANSLATION || h->wxdepth != WARP_DEPTH || h->wxwidth != WARP_W) q.carve(c, h);   // as WarpPointsPlan
+  q.total_f = c.o;
+  return q;
+}
+
+// what both unwarp entries check of the handle and the count
+int unwarp_model(const char* entry, const nrf_handle_s* h, int n) {
+  const auto refuse = [&](int code, const char* rule) {
+    snprintf(g_err, sizeof(g_err), "%s: %s", entry, rule);
+    return code;
+  };
+  if (!h->warp) return refuse(NRF_E_UNSUPPORTED, "the model has no warp field");
+  if (h->time_enc) return refuse(NRF_E_UNSUPPORTED, "takes warp ids or codes: not built for the time encoder");
+  if (n <= 0 || n > NRF_UNWARP_MAX_POINTS) return refuse(NRF_E_SHAPE, "num_points must be in 1..NRF_UNWARP_MAX_POINTS (1 << 20); callers chunk");
+  return NRF_OK;
+}
+
 // ---- Field queries, value (nrf_query_points / nrf_query_grid) and gradient (nrf_query_points_grad / nrf_query_grid_grad): what both
 // plans hold, in this order, before their own tails:
 // [pack descriptors | embed table | padded params | images of one MLP | SE3 trunk image | tile counters |
@@ -442,6 +485,79 @@ int nrf_warp_points(nrf_handle h, const float* params, const float* points, cons
   a.tile_counter = tile_counter_or_null(ws + q.ctr_f, 0);
   launch_warp_fwd(a, nullptr, false, tile_grid(a.ntiles, 2, h->num_cus), st);
   return finish_entry("nrf_warp_points", warped, ws + q.out_f, num_points, st);
+}
+
+int nrf_unwarp_workspace_bytes(nrf_handle h, int32_t num_points, size_t* bytes) {
+  if (!h) return fail(NRF_E_NULL, "nrf_unwarp_workspace_bytes: handle is null");
+  if (!bytes) return fail(NRF_E_NULL, "nrf_unwarp_workspace_bytes: bytes is null");
+  CK(unwarp_model("nrf_unwarp_workspace_bytes", h, num_points));
+  *bytes = unwarp_plan(h, num_points).total_f * sizeof(float);
+  return NRF_OK;
+}
+
+int nrf_unwarp_points(nrf_handle h, const float* params, const float* targets, const int32_t* warp_ids, const float* warp_codes,
+                      int32_t num_codes, const float* guess, int32_t num_points, const nrf_step_scalars* scalars, int32_t num_steps,
+                      float tolerance, float max_step, const nrf_unwarp_out* out, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* null_arg = !h ? "handle" : !params ? "params" : !targets ? "targets" : !warp_ids ? "warp_ids" : !scalars ? "scalars (nrf_step_scalars)"
+                         : !out ? "out (nrf_unwarp_out)" : !workspace ? "workspace" : nullptr;
+  if (null_arg) {
+    snprintf(g_err, sizeof(g_err), "nrf_unwarp_points: %s is null", null_arg);
+    return NRF_E_NULL;
+  }
+  CK(unwarp_model("nrf_unwarp_points", h, num_points));
+  if (num_steps < 0 || num_steps > NRF_UNWARP_MAX_STEPS) return fail(NRF_E_SHAPE, "nrf_unwarp_points: num_steps must be in 0..NRF_UNWARP_MAX_STEPS (32)");
+  if (!(tolerance >= 0.f)) return fail(NRF_E_SHAPE, "nrf_unwarp_points: tolerance must be >= 0 (and not NaN)");
+  if (!(max_step > 0.f)) return fail(NRF_E_SHAPE, "nrf_unwarp_points: max_step must be positive (INFINITY: no limit)");
+  if (warp_codes && num_codes <= 0) return fail(NRF_E_SHAPE, "nrf_unwarp_points: num_codes must be positive with warp_codes");
+  const UnwarpPlan q = unwarp_plan(h, num_points);
+  if (workspace_bytes < q.total_f * sizeof(float)) return fail(NRF_E_WORKSPACE, "nrf_unwarp_points: workspace too small (see nrf_unwarp_workspace_bytes)");
+  query_device(h);
+  float* ws = (float*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  forget_workspace(h, ws);
+  const bool padded = q.ip_f != 0;
+  if (padded && !(params = embed_side(h, params, ws, q, st))) return NRF_E_HIP;
+  const WarpParamOffsets& wo = padded ? h->wpo : h->xwpo;   // as nrf_warp_points
+  SidePack& pack = h->un_pack;
+  refresh(pack, (int64_t)q.wpk_f, [&](std::vector<PackDesc>& v) { warp_pack_descs(h, wo, (int64_t)q.wpk_f, false, v); });
+  CK(upload_pack_table(pack, ws + q.desc_f, "upload unwarp pack table", st));
+  launch_pack(reinterpret_cast<const PackDesc*>(ws + q.desc_f), (int)pack.descs.size(), params, ws, st);
+  float* x = ws + q.x_f;
+  int32_t* state = reinterpret_cast<int32_t*>(ws + q.state_f);
+  launch_unwarp_init(guess ? guess : targets, num_points, x, state, st);
+  // the primal pass at x keeping what a frozen ray plan keeps, and its tangent pass: a gradient query's two SE3 launches
+  WarpFwdArgs wa = warp_points_args(h, params, wo, ws + q.wpk_f, scalars, x, warp_ids, num_points, ws + q.warped_f);
+  if (warp_codes) wa.embed_table = warp_codes;
+  wa.st_win = ws + q.win_f; wa.st_wv = reinterpret_cast<float4*>(ws + q.wv_f); wa.bits = reinterpret_cast<uint32_t*>(ws + q.bits_f);
+  WarpFwdArgs ta = wa;
+  ta.nt_prim = q.ntiles; ta.prim_win = wa.st_win; ta.prim_bits = wa.bits;
+  ta.ntiles = 3 * q.ntiles; ta.rows = ta.ntiles * TILE_ROWS;
+  ta.st_win = nullptr; ta.bits = nullptr; ta.points_out = nullptr; ta.st_wv = reinterpret_cast<float4*>(ws + q.twv_f);
+  UnwarpArgs ua;
+  memset(&ua, 0, sizeof(ua));
+  ua.prim_win = wa.st_win; ua.prim_wv = wa.st_wv; ua.tan_wv = ta.st_wv; ua.warped = wa.points_out; ua.targets = targets;
+  ua.x = x; ua.state = state;
+  ua.rows = num_points; ua.rows_pad = (int)q.rows_pad(); ua.PKS = (h->PKw + 31) / 32 * 32;
+  ua.tolerance = tolerance; ua.max_step = max_step;
+  const int grid = tile_grid(wa.ntiles, warp_grid_mul(), h->num_cus), tgrid = tile_grid(ta.ntiles, warp_grid_mul(), h->num_cus);
+  const double flops = warp_fwd_flops_row(h) * num_points;
+  Prof& pf = h->prof;
+  for (int k = 0; k <= num_steps; ++k) {   // the closing pass is the rounds' own launch: the same bits at the same x
+    pf.begin("unwarp_warp", flops, st);
+    launch_warp_fwd(wa, nullptr, true, grid, st, true);
+    pf.end(st);
+    if (k == num_steps) break;
+    pf.begin("unwarp_tangent", 3.0 * flops, st);
+    launch_warp_fwd(ta, nullptr, true, tgrid, st, true);
+    pf.end(st);
+    pf.begin("unwarp_step", 0, st);
+    launch_unwarp_step(ua, st);
+    pf.end(st);
+  }
+  pf.begin("unwarp_step", 0, st);   // the closing kernel: residual and status at the returned x
+  launch_unwarp_finish(ua, out->points, out->residual, out->status, st);
+  pf.end(st);
+  return check_launch("nrf_unwarp_points");
 }
 
 int nrf_query_workspace_bytes(nrf_handle h, int32_t num_groups, int32_t points_per_group, uint32_t flags, size_t* bytes) {

@@ -254,6 +254,7 @@ struct nrf_handle_s {
   nrf::api::Modes stashed_modes;
   nrf::api::SidePack wp_pack, q_pack;   // nrf_warp_points (key: its image's offset) / the field queries (key: the level)
   nrf::api::SidePack qg_pack;           // the gradient queries (key: the level)
+  nrf::api::SidePack un_pack;           // nrf_unwarp_points (key: its image's offset)
 };
 
 namespace nrf {

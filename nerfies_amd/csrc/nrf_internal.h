@@ -352,6 +352,19 @@ struct JacobianArgs {
   int rows, rows_pad, PKS;
 };
 
+// One Newton round of nrf_unwarp_points (warp_chain.hip unwarp_step_kernel) on the stashes of the primal and tangent passes at x
+struct UnwarpArgs {
+  const float* prim_win;     // as JacobianArgs: x = features 0..2 of the trunk-input stash
+  const float4* prim_wv;
+  const float4* tan_wv;
+  const float* warped;       // [rows_pad][3] W(x) of the primal pass
+  const float* targets;      // [rows][3] y
+  float* x;                  // [rows_pad][3] the iterate
+  int32_t* state;            // [rows_pad] 0 running, 1 converged, 2 stopped (singular or non-finite step)
+  int rows, rows_pad, PKS;
+  float tolerance, max_step;
+};
+
 // One split-K slice of a weight-gradient GEMM  dW[k][n] = sum_rows X[row][k] dY[row][n].
 enum { SRC_FRAG256 = 0, SRC_FRAG128 = 1, SRC_PLAIN = 2 };
 struct WgradTask {
@@ -461,6 +474,10 @@ void launch_warp_fwd(const WarpFwdArgs& a, const WarpFwdArgs* a1, bool stash, in
 void launch_warp_bwd(const WarpBwdArgs& a, const WarpBwdArgs* a1, const WarpBwdArgs* a2, int grid, hipStream_t stream);
 void launch_elastic(const ElasticArgs& a, hipStream_t stream);
 void launch_jacobian(const JacobianArgs& a, hipStream_t stream);
+// nrf_unwarp_points: x <- start, state <- 0; one round; the outputs behind the closing primal pass (any of them may be nullptr)
+void launch_unwarp_init(const float* start, int rows, float* x, int32_t* state, hipStream_t stream);
+void launch_unwarp_step(const UnwarpArgs& a, hipStream_t stream);
+void launch_unwarp_finish(const UnwarpArgs& a, float* points, float* residual, int32_t* status, hipStream_t stream);
 void launch_median_coef(const float* weights, int B, int S, float* coef, hipStream_t stream);
 void launch_wgrad(const WgradGroup* d_groups, const WgradSegment* d_segs, const int* d_seg_begin, int nwg, float* ws,
                   unsigned long long* seg_clock, hipStream_t stream);

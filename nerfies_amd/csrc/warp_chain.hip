@@ -820,6 +820,102 @@ void launch_jacobian(const JacobianArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(jacobian_kernel, dim3((a.rows + 255) / 256), dim3(256), 0, stream, a);
 }
 
+// ---------------------------------------------------------------------------------------------
+// inverse warp (nrf_unwarp_points): Newton's iteration on W(x) = y, one thread per row
+// ---------------------------------------------------------------------------------------------
+// r = W(x) - y and |r|_2, one rounding per step: the round kernel and the closing kernel decide "converged" on the same bits
+__device__ __forceinline__ float unwarp_residual(const float* __restrict__ warped, const float* __restrict__ targets, int row, V3& r) {
+  const size_t o = 3 * (size_t)row;
+  r = v3(__fsub_rn(warped[o], targets[o]), __fsub_rn(warped[o + 1], targets[o + 1]), __fsub_rn(warped[o + 2], targets[o + 2]));
+  return sqrtf(fmaf(r.z, r.z, fmaf(r.y, r.y, __fmul_rn(r.x, r.x))));
+}
+__device__ __forceinline__ bool finite3(V3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
+
+// x <- the guess (or the target), every row running
+__global__ void unwarp_init_kernel(const float* __restrict__ start, int rows, float* __restrict__ x, int32_t* __restrict__ state) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) x[3 * (size_t)row + c] = start[3 * (size_t)row + c];
+  state[row] = 0;
+}
+
+// One round behind the primal and tangent passes at x: jacobian_kernel's E = J - I kept in registers, (I + E) dx = r solved by the
+// adjugate, x -= dx.  A stopped row (state 1 converged, 2 singular / non-finite) is left as it is
+__global__ __launch_bounds__(256) void unwarp_step_kernel(const UnwarpArgs A) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= A.rows) return;
+  if (A.state[row] != 0) return;
+  V3 r;
+  const float res = unwarp_residual(A.warped, A.targets, row, r);
+  if (res <= A.tolerance) { A.state[row] = 1; return; }
+  const int tile = row / TILE_ROWS, p = row % TILE_ROWS;
+  const float* sw = A.prim_win + (size_t)tile * A.PKS * TILE_ROWS;
+  const V3 x = v3(sw[frag_index(0, p)], sw[frag_index(1, p)], sw[frag_index(2, p)]);
+  const float4 w4 = A.prim_wv[2 * (size_t)row], v4 = A.prim_wv[2 * (size_t)row + 1];
+  V3 wd[3], vd[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const size_t tr = (size_t)c * A.rows_pad + row;
+    const float4 a = A.tan_wv[2 * tr], b = A.tan_wv[2 * tr + 1];
+    wd[c] = v3(a.x, a.y, a.z); vd[c] = v3(b.x, b.y, b.z);
+  }
+  float J[3][3];
+  const V3 wj = v3(w4.x, w4.y, w4.z);
+  warp_jacobian_minus_identity(se3_coef_d(dot(wj, wj)), wj, v3(v4.x, v4.y, v4.z), x, wd, vd, J);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) J[i][i] += 1.f;
+  float Cf[3][3];   // cofactors: J^-1 = Cf^T / det
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+      Cf[i][k] = J[i1][k1] * J[i2][k2] - J[i1][k2] * J[i2][k1];
+    }
+  const float det = J[0][0] * Cf[0][0] + J[0][1] * Cf[0][1] + J[0][2] * Cf[0][2];
+  V3 dx = v3((Cf[0][0] * r.x + Cf[1][0] * r.y + Cf[2][0] * r.z) / det, (Cf[0][1] * r.x + Cf[1][1] * r.y + Cf[2][1] * r.z) / det,
+             (Cf[0][2] * r.x + Cf[1][2] * r.y + Cf[2][2] * r.z) / det);
+  if (!isfinite(det) || det == 0.f || !finite3(dx)) { A.state[row] = 2; return; }
+  // |dx| scaled by its largest component: finite whenever dx is
+  const float m = fmaxf(fabsf(dx.x), fmaxf(fabsf(dx.y), fabsf(dx.z)));
+  if (m > 0.f) {
+    const V3 u = v3(dx.x / m, dx.y / m, dx.z / m);
+    const float len = m * sqrtf(dot(u, u));
+    if (len > A.max_step) { const float s = A.max_step / len; dx = v3(dx.x * s, dx.y * s, dx.z * s); }
+  }
+  const V3 xn = v3(x.x - dx.x, x.y - dx.y, x.z - dx.z);
+  if (!finite3(xn)) { A.state[row] = 2; return; }   // an unlimited step that leaves float32: the row stops where it is
+  float* xo = A.x + 3 * (size_t)row;
+  xo[0] = xn.x; xo[1] = xn.y; xo[2] = xn.z;
+}
+
+// behind the closing primal pass: the residual at the returned x, and the status it decides
+__global__ void unwarp_finish_kernel(const UnwarpArgs A, float* __restrict__ points, float* __restrict__ residual, int32_t* __restrict__ status) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= A.rows) return;
+  V3 r;
+  const float res = unwarp_residual(A.warped, A.targets, row, r);
+  if (points) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) points[3 * (size_t)row + c] = A.x[3 * (size_t)row + c];
+  }
+  if (residual) residual[row] = res;
+  if (status) status[row] = A.state[row] == 2 ? 2 : res <= A.tolerance ? 1 : 0;
+}
+
+void launch_unwarp_init(const float* start, int rows, float* x, int32_t* state, hipStream_t stream) {
+  hipLaunchKernelGGL(unwarp_init_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, start, rows, x, state);
+}
+
+void launch_unwarp_step(const UnwarpArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(unwarp_step_kernel, dim3((a.rows + 255) / 256), dim3(256), 0, stream, a);
+}
+
+void launch_unwarp_finish(const UnwarpArgs& a, float* points, float* residual, int32_t* status, hipStream_t stream) {
+  hipLaunchKernelGGL(unwarp_finish_kernel, dim3((a.rows + 255) / 256), dim3(256), 0, stream, a, points, residual, status);
+}
+
 void launch_elastic(const ElasticArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(elastic_kernel, dim3((a.rows_pad + 255) / 256), dim3(256), 0, stream, a);
 }

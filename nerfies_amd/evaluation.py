@@ -393,6 +393,33 @@ def extract_mesh(model, params, bbox_min, bbox_max, resolution, threshold, level
   return out
 
 
+def animate_mesh(model, params, vertices, warp_ids, warp_extra=None, steps=8, tolerance=1e-6, warm_start=True):
+  """A canonical (template) surface carried into frames: for each of the K `warp_ids`, in order, the observation-space points x_k
+  with warp_points(x_k, id_k) = `vertices` (V, 3), e.g. those of extract_mesh(warp_id=None) -- NerfModel.unwarp_points, `steps`
+  Newton rounds per frame.  The faces are the template's: every frame keeps its topology and vertex order.  With `warm_start` frame
+  k + 1 starts from frame k's solution (adjacent frames are close), frame 0 from the template itself.  `tolerance`: the residual
+  |W(x) - vertex| at which a vertex counts as converged; the default is about four times the float32 forward's own error at scene
+  scale.  Returns device tensors {'vertices' (K, V, 3), 'residual' (K, V), 'status' (K, V) int32: 1 converged, 0 ran out of
+  steps, 2 stopped where the field is singular}; a vertex with another status than 1 is returned as it is, for the caller to see."""
+  vertices = torch.as_tensor(vertices)
+  device = vertices.device
+  ids = [int(i) for i in warp_ids]
+  V = vertices.shape[0]
+  out = {'vertices': torch.empty(len(ids), V, 3, dtype=torch.float32, device=device),
+         'residual': torch.empty(len(ids), V, dtype=torch.float32, device=device),
+         'status': torch.empty(len(ids), V, dtype=torch.int32, device=device)}
+  guess = None
+  for k, wid in enumerate(ids):
+    if V == 0:
+      break
+    got = model.unwarp_points(params, vertices, torch.full((V,), wid, dtype=torch.int32, device=device), warp_extra, guess=guess,
+                              steps=steps, tolerance=tolerance)
+    out['vertices'][k], out['residual'][k], out['status'][k] = got['points'], got['residual'], got['status']
+    if warm_start:
+      guess = got['points']
+  return out
+
+
 def compute_psnr(mse):
   """utils.compute_psnr (utils.py:283-293): -10 log10(mse)."""
   return -10.0 * torch.log10(torch.as_tensor(mse))

@@ -150,6 +150,11 @@ class FieldGradOut(C.Structure):
   _fields_ = [('sigma', C.c_void_p), ('grad_sigma', C.c_void_p), ('normals', C.c_void_p), ('warped_points', C.c_void_p)]
 
 
+class UnwarpOut(C.Structure):
+  """nrf_unwarp_out: the device outputs of nrf_unwarp_points, N rows each; a NULL pointer skips that output."""
+  _fields_ = [('points', C.c_void_p), ('residual', C.c_void_p), ('status', C.c_void_p)]
+
+
 class MeshStatus(C.Structure):
   """nrf_mesh_status: the first 16 bytes of a mesh workspace (device memory) after nrf_mesh_count / nrf_mesh_emit."""
   _fields_ = [('num_vertices', C.c_int32), ('num_triangles', C.c_int32), ('emitted_vertices', C.c_int32), ('emitted_triangles', C.c_int32)]
@@ -158,6 +163,9 @@ class MeshStatus(C.Structure):
 NRF_QUERY_MAX_POINTS = 1 << 24   # points of one nrf_query_points / nrf_query_grid call
 NRF_QUERY_GRAD_MAX_POINTS = 1 << 20   # points of one nrf_query_points_grad / nrf_query_grid_grad call
 NRF_GRID_MAX_POINTS = 1 << 40    # points of a whole nrf_grid
+NRF_HAS_UNWARP = 1
+NRF_UNWARP_MAX_POINTS = 1 << 20  # points of one nrf_unwarp_points call
+NRF_UNWARP_MAX_STEPS = 32        # Newton rounds of one nrf_unwarp_points call
 NRF_MESH_MAX_CELLS = 1 << 28     # cells of a grid handed to nrf_mesh_count / nrf_mesh_emit (triangle indices stay in int32)
 NRF_OPT_CHAIN_TILE_ROWS = 1
 NRF_OPT_BF16_WGRAD_MERGE = 2
@@ -177,6 +185,7 @@ EXPORTS = [
     'nrf_loss_grad_rays',
     'nrf_query_workspace_bytes', 'nrf_query_points', 'nrf_query_grid',
     'nrf_query_grad_workspace_bytes', 'nrf_query_points_grad', 'nrf_query_grid_grad',
+    'nrf_unwarp_workspace_bytes', 'nrf_unwarp_points',
     'nrf_mesh_workspace_bytes', 'nrf_mesh_count', 'nrf_mesh_emit', 'nrf_mesh_snap',
 ]
 
@@ -245,6 +254,8 @@ def load_library(path=None):
                                 C.c_size_t, vp],
       'nrf_query_grid_grad': [vp, vp, C.POINTER(Rays), C.POINTER(Grid), i64, i32, i32, C.POINTER(StepScalars), u32,
                               C.POINTER(FieldGradOut), vp, C.c_size_t, vp],
+      'nrf_unwarp_workspace_bytes': [vp, i32, C.POINTER(C.c_size_t)],
+      'nrf_unwarp_points': [vp, vp, vp, vp, vp, i32, vp, i32, C.POINTER(StepScalars), i32, f32, f32, C.POINTER(UnwarpOut), vp, C.c_size_t, vp],
       'nrf_mesh_workspace_bytes': [C.POINTER(Grid), C.POINTER(C.c_size_t)],
       'nrf_mesh_count': [vp, C.POINTER(Grid), f32, vp, vp, C.c_size_t, vp],
       'nrf_mesh_emit': [vp, C.POINTER(Grid), f32, i32, i32, vp, vp, vp, vp, C.c_size_t, vp],

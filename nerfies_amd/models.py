@@ -831,6 +831,63 @@ class NerfModel:
                                      ws.numel() * 4, _stream(device)), self.lib)
     return out.reshape(torch.as_tensor(points).shape)
 
+  UNWARP_OUTPUTS = ('points', 'residual', 'status')
+
+  def unwarp_points(self, variables, points, warp_ids, warp_extra, guess=None, steps=8, tolerance=0.0, max_step=float('inf'),
+                    warp_codes=None, outputs=('points', 'residual', 'status')):
+    """The warp field inverted (nrf_unwarp_points): x with warp_points(x, id) = `points`, canonical points (..., 3) with one warp id
+    each, by `steps` Newton rounds on the device from `guess` (None: from the points themselves).  A row stops once its residual
+    |W(x) - point| is <= `tolerance`; a step longer than `max_step` is shortened to it.  `warp_codes` (num_codes, features): the ids
+    index ITS rows instead of the model's embedding table (in-between-frame codes).  `outputs` selects among 'points', 'residual'
+    (at the returned x) and 'status' (int32: 0 ran out of steps, 1 converged, 2 stopped at a singular or non-finite step).  More
+    than NRF_UNWARP_MAX_POINTS points run as chunks through one cached workspace.  Returns a dict of device tensors shaped like
+    points[..., 0] (a trailing 3 for 'points')."""
+    device = torch.as_tensor(points).device
+    if device.type != 'cuda':
+      raise L.NrfError('points must live on the GPU: the hot path has no CPU fallback')
+    return self._unwarp_chunks(variables, points, warp_ids, warp_extra, guess, steps, tolerance, max_step, warp_codes, outputs, device)
+
+  def _unwarp_chunks(self, variables, points, warp_ids, warp_extra, guess, steps, tolerance, max_step, warp_codes, outputs, device):
+    """`unwarp_points` behind its device rule: the calls into the library, one per chunk."""
+    outputs = tuple(outputs)
+    if not outputs or set(outputs) - set(self.UNWARP_OUTPUTS):
+      raise L.NrfError(f'outputs must be a non-empty selection of {self.UNWARP_OUTPUTS}, got {outputs}')
+    y = _f32(points, device)
+    if y.dim() < 1 or y.shape[-1] != 3:
+      raise L.NrfError(f'points must be (..., 3), got {tuple(y.shape)}')
+    lead = tuple(y.shape[:-1])
+    y = y.reshape(-1, 3)
+    n = y.shape[0]
+    ids = _ids(warp_ids, device).reshape(-1)
+    if ids.numel() != n:
+      raise L.NrfError(f'warp_ids must hold one id per point ({n}), got {ids.numel()}')
+    x0 = None
+    if guess is not None:
+      x0 = _f32(guess, device).reshape(-1, 3)
+      if x0.shape[0] != n:
+        raise L.NrfError(f'guess must be shaped like points ({n} rows), got {x0.shape[0]}')
+    codes = None if warp_codes is None else _f32(warp_codes, device).reshape(-1, self.num_warp_features)
+    fp = self.flat_params(variables, device)
+    scal = _scalars(warp_extra)
+    stream = _stream(device) if device.type == 'cuda' else None   # not cuda: a recording stand-in for the library only, as in _grid_call
+    ret = {k: torch.empty(n, *((3,) if k == 'points' else ()), dtype=torch.int32 if k == 'status' else torch.float32, device=device)
+           for k in outputs}
+    cap = L.NRF_UNWARP_MAX_POINTS
+    key = ('unwarp', min(n, cap), str(device))   # the first chunk is the largest
+    ws = self._ws.get(key)
+    if ws is None:
+      nbytes = C.c_size_t(0)
+      L.check(self.lib.nrf_unwarp_workspace_bytes(self.handle, min(n, cap), C.byref(nbytes)), self.lib)
+      ws = self._ws[key] = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=device)
+    for r0 in range(0, n, cap):
+      r1 = min(n, r0 + cap)
+      uo = L.UnwarpOut(*(_ptr(ret[k][r0:r1]) if k in ret else None for k in self.UNWARP_OUTPUTS))
+      L.check(self.lib.nrf_unwarp_points(self.handle, _ptr(fp.flat), _ptr(y[r0:r1]), _ptr(ids[r0:r1]), _ptr(codes),
+                                         0 if codes is None else codes.shape[0], None if x0 is None else _ptr(x0[r0:r1]), r1 - r0,
+                                         C.byref(scal), int(steps), float(tolerance), float(max_step), C.byref(uo), _ptr(ws),
+                                         ws.numel() * 4, stream), self.lib)
+    return {k: v.reshape(*lead, *v.shape[1:]) for k, v in ret.items()}
+
   def profile_enable(self, on=True):
     L.check(self.lib.nrf_profile_enable(self.handle, int(bool(on))), self.lib)
 

@@ -17,7 +17,12 @@ With --normals (evaluation.normal_grid -> nrf_query_grid_grad: the density's gra
 With --mesh (evaluation.extract_mesh -> nrf_mesh_count / nrf_mesh_emit / nrf_mesh_snap: surface nets on the device grid, the vertices
 pulled onto the level set sigma = --threshold by --mesh_refine Newton steps along the field's own gradient):
   mesh_<name>.ply      binary little-endian triangle mesh: vertices x y z nx ny nz red green blue, faces as vertex_indices lists.
-The .npy grid and the point cloud stay what they were; the mesh is the iso-surface they stopped short of."""
+The .npy grid and the point cloud stay what they were; the mesh is the iso-surface they stopped short of.
+With --mesh --canonical --animate ITEM_ID [ITEM_ID ...] (evaluation.animate_mesh -> nrf_unwarp_points: the warp field inverted at the
+template's vertices, Newton's iteration on the device, each frame started from the one before):
+  mesh_canonical_at_<item_id>.ply   the template carried into that frame: the same vertex_indices and colours, the vertices x with
+                       warp(x, frame) = template vertex, the normals of the field there.  Vertices that did not converge are counted
+                       in the printed summary and written as they are."""
 import argparse
 import os
 import sys
@@ -47,10 +52,15 @@ def parse_flags(argv=None):
   p.add_argument('--normals', action='store_true', help='also export the surface normals -grad sigma / |grad sigma| (npy, and nx ny nz in the PLY)')
   p.add_argument('--mesh', action='store_true', help='also extract the triangle mesh of the level set sigma = --threshold (mesh_<name>.ply)')
   p.add_argument('--mesh_refine', type=int, default=2, metavar='K', help='Newton steps of the mesh vertices onto the level set')
+  p.add_argument('--animate', nargs='+', default=None, metavar='ITEM_ID',
+                 help='with --mesh --canonical: carry the template mesh into these frames (mesh_canonical_at_<item_id>.ply each)')
+  p.add_argument('--animate_steps', type=int, default=8, metavar='K', help='Newton rounds per frame of --animate')
   p.add_argument('--margin', type=float, default=0.0, help="grow the scene points' box by this fraction of its size on every side")
   own, rest = p.parse_known_args(argv)
   if len(own.resolution) not in (1, 3):
     p.error('--resolution takes one number or three')
+  if own.animate is not None and not (own.mesh and own.canonical):
+    p.error('--animate carries the canonical mesh into frames: it needs --mesh --canonical')
   flags = train_driver.parse_flags(rest)
   for k, v in vars(own).items():
     setattr(flags, k, v)
@@ -91,6 +101,35 @@ def write_mesh_ply(path, vertices, normals, rgb, faces):
     f.write(head.encode('ascii'))
     f.write(vert.tobytes())
     f.write(face.tobytes())
+
+
+def animate(flags, model, target, warp_extra, datasource, mesh, alpha_app, exp_dir):
+  """--animate: the template `mesh` carried into every frame of flags.animate; {item id: its PLY}."""
+  if not model.use_warp or model.warp_metadata_encoder_type == 'time':
+    raise SystemExit('--animate: needs a model with a warp field driven by warp ids (not the time encoder)')
+  known = list(datasource.train_ids) + list(datasource.val_ids)
+  for item in flags.animate:
+    if item not in known:
+      raise SystemExit(f'--animate {item}: not an item of the capture')
+  ids = [datasource.get_warp_id(item) for item in flags.animate]
+  frames = evaluation.animate_mesh(model, target, mesh['vertices'], ids, warp_extra=warp_extra, steps=flags.animate_steps)
+  faces, rgb = mesh['faces'].cpu().numpy(), mesh['rgb'].cpu().numpy()
+  nv, written = mesh['vertices'].shape[0], {}
+  for k, (item, wid) in enumerate(zip(flags.animate, ids)):
+    verts = frames['vertices'][k]
+    normals = torch.zeros(0, 3)
+    if nv:   # the field's normals where the vertices now are, through that frame's warp
+      md = evaluation._one_group_metadata(wid, alpha_app, None, verts.device)
+      normals = model.query_gradient(target, verts, metadata=md, warp_extra=warp_extra, level=flags.level, outputs=('normals',))['normals']
+    path = os.path.join(exp_dir, f'mesh_canonical_at_{item}.ply')
+    write_mesh_ply(path, verts.cpu().numpy(), normals.cpu().numpy(), rgb, faces)
+    status = frames['status'][k]
+    left, stopped = int((status == 0).sum()), int((status == 2).sum())
+    worst = float(frames['residual'][k].max()) if nv else 0.0
+    print(f'mesh_canonical_at_{item}: {nv} vertices, {nv - left - stopped} converged, {left} out of steps, {stopped} stopped at a singular '
+          f'step, largest residual {worst:.3g} -> {path}', flush=True)
+    written[item] = path
+  return written
 
 
 def main(argv=None):
@@ -177,6 +216,8 @@ def main(argv=None):
     print(f'mesh_{name}: {mesh["vertices"].shape[0]} vertices, {mesh["faces"].shape[0]} faces at sigma = {flags.threshold:g}, '
           f'{flags.mesh_refine} refine steps -> {mesh_ply}', flush=True)
     ret.update(mesh_ply=mesh_ply, num_mesh_vertices=int(mesh['vertices'].shape[0]), num_mesh_faces=int(mesh['faces'].shape[0]))
+    if flags.animate is not None:
+      ret['animated'] = animate(flags, model, target, state.warp_extra, datasource, mesh, alpha_app, exp_dir)
   return ret
 
 
