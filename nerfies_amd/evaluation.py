@@ -6,6 +6,9 @@ from typing import Any, Callable, Dict, Optional
 import torch
 import torch.distributed as dist
 
+from nerfies_amd import lib as L
+from nerfies_amd.models import _stream_arg, grid_chunks  # noqa: F401 (grid_chunks is public here as well)
+
 
 def _tree_map(fn, tree):
   if isinstance(tree, dict):
@@ -94,7 +97,6 @@ class GraphedChunkRenderer:
 def _check_same_tree(dst, src, path='rays'):
   """The replay path copies new rays into the captured static buffers: same keys, same shapes, same dtypes -- or a clear error
   (a missing sub-dict used to surface as a TypeError on None)."""
-  from nerfies_amd import lib as L
   if isinstance(dst, dict):
     if not isinstance(src, dict) or set(dst) != set(src):
       have = sorted(src) if isinstance(src, dict) else type(src).__name__
@@ -239,11 +241,6 @@ def rays_from_camera(camera, metadata: Optional[Dict[str, int]] = None, device='
   return rays
 
 
-def grid_chunks(total: int, chunk: int):
-  """(first, count) pieces that cover [0, total) exactly once, in order, `chunk` points at most each."""
-  return [(first, min(chunk, total - first)) for first in range(0, total, chunk)]
-
-
 def _box_grid(bbox_min, bbox_max, resolution):
   """(res, origin, step): `resolution` voxels per axis (an int, or (X, Y, Z)) over the box, sampled at the voxel centres."""
   res = (int(resolution),) * 3 if isinstance(resolution, int) else tuple(int(r) for r in resolution)
@@ -262,6 +259,22 @@ def _one_group_metadata(warp_id, appearance_id, camera_id, device):
   return {k: torch.tensor([[int(v)]], dtype=torch.int32, device=device) for k, v in ids.items() if v is not None}
 
 
+def _walk_grid(query, widths, cap, params, bbox_min, bbox_max, resolution, level, warp_id, appearance_id, warp_extra, chunk, device):
+  """The grid entry `query` (NerfModel.query_grid or .query_grid_gradient) over the voxel centres of the box, `chunk` (at most `cap`)
+  points per call through one workspace: {name: (X, Y, Z, *widths[name]) float32 device tensor, x fastest in memory}."""
+  res, origin, step = _box_grid(bbox_min, bbox_max, resolution)
+  if device is None:
+    device = params.flat.device if hasattr(params, 'flat') else 'cuda'
+  metadata = _one_group_metadata(warp_id, appearance_id, None, device)
+  total = res[0] * res[1] * res[2]
+  chunk = max(1, min(int(chunk), total, cap))
+  flat = {k: torch.empty(total, *w, dtype=torch.float32, device=device) for k, w in widths.items()}
+  for first, count in grid_chunks(total, chunk):
+    query(params, origin, step, res, first, count, {k: v[first:first + count] for k, v in flat.items()}, metadata=metadata,
+          warp_extra=warp_extra, level=level, use_warp=warp_id is not None, workspace_points=chunk)
+  return {k: flat[k].view(res[2], res[1], res[0], *w).permute(2, 1, 0, *range(3, 3 + len(w))) for k, w in widths.items()}
+
+
 def density_grid(model, params, bbox_min, bbox_max, resolution, level='fine', warp_id=None, appearance_id=None, warp_extra=None,
                  chunk=1 << 21, device=None):
   """Activated density of the field on a regular grid over the box [bbox_min, bbox_max]: an (X, Y, Z) float32 device tensor, `x`
@@ -269,17 +282,8 @@ def density_grid(model, params, bbox_min, bbox_max, resolution, level='fine', wa
   canonical (template) volume (NRF_FLAG_NO_WARP); an id queries that frame's observation volume through the warp field.
   `appearance_id`: the appearance code of a use_alpha_condition model (its density depends on it).  The points are formed on the
   device by nrf_query_grid, `chunk` of them per call through one workspace; the density-only kernel runs (no colour is computed)."""
-  res, origin, step = _box_grid(bbox_min, bbox_max, resolution)
-  if device is None:
-    device = params.flat.device if hasattr(params, 'flat') else 'cuda'
-  metadata = _one_group_metadata(warp_id, appearance_id, None, device)
-  total = res[0] * res[1] * res[2]
-  chunk = max(1, min(int(chunk), total, 1 << 24))
-  sigma = torch.empty(total, dtype=torch.float32, device=device)
-  for first, count in grid_chunks(total, chunk):
-    model.query_grid(params, origin, step, res, first, count, {'sigma': sigma[first:first + count]}, metadata=metadata,
-                     warp_extra=warp_extra, level=level, use_warp=warp_id is not None, workspace_points=chunk)
-  return sigma.view(res[2], res[1], res[0]).permute(2, 1, 0)
+  return _walk_grid(model.query_grid, {'sigma': ()}, 1 << 24, params, bbox_min, bbox_max, resolution, level, warp_id, appearance_id,
+                    warp_extra, chunk, device)['sigma']
 
 
 def normal_grid(model, params, bbox_min, bbox_max, resolution, level='fine', warp_id=None, appearance_id=None, warp_extra=None,
@@ -288,20 +292,9 @@ def normal_grid(model, params, bbox_min, bbox_max, resolution, level='fine', war
   arguments): (sigma (X, Y, Z), normals (X, Y, Z, 3)), float32 device tensors.  A normal is exactly 0 where the gradient vanishes.
   With a `warp_id` the gradient is taken with respect to the observation-space point, through the warp field.  The points are formed
   on the device by nrf_query_grid_grad, `chunk` (at most NRF_QUERY_GRAD_MAX_POINTS) of them per call through one workspace."""
-  from nerfies_amd import lib as L
-  res, origin, step = _box_grid(bbox_min, bbox_max, resolution)
-  if device is None:
-    device = params.flat.device if hasattr(params, 'flat') else 'cuda'
-  metadata = _one_group_metadata(warp_id, appearance_id, None, device)
-  total = res[0] * res[1] * res[2]
-  chunk = max(1, min(int(chunk), total, L.NRF_QUERY_GRAD_MAX_POINTS))
-  sigma = torch.empty(total, dtype=torch.float32, device=device)
-  normals = torch.empty(total, 3, dtype=torch.float32, device=device)
-  for first, count in grid_chunks(total, chunk):
-    model.query_grid_gradient(params, origin, step, res, first, count,
-                              {'sigma': sigma[first:first + count], 'normals': normals[first:first + count]}, metadata=metadata,
-                              warp_extra=warp_extra, level=level, use_warp=warp_id is not None, workspace_points=chunk)
-  return sigma.view(res[2], res[1], res[0]).permute(2, 1, 0), normals.view(res[2], res[1], res[0], 3).permute(2, 1, 0, 3)
+  out = _walk_grid(model.query_grid_gradient, {'sigma': (), 'normals': (3,)}, L.NRF_QUERY_GRAD_MAX_POINTS, params, bbox_min, bbox_max,
+                   resolution, level, warp_id, appearance_id, warp_extra, chunk, device)
+  return out['sigma'], out['normals']
 
 
 MESH_VIEW_DIRECTION = (0.0, 0.0, 1.0)   # the direction every exported colour is queried along
@@ -309,15 +302,10 @@ MESH_VIEW_DIRECTION = (0.0, 0.0, 1.0)   # the direction every exported colour is
 
 def _mesh_grid(sigma, origin, step):
   """(the x-fastest flat view of an (X, Y, Z) density tensor, its nrf_grid)."""
-  from nerfies_amd import lib as L
   if sigma.dim() != 3 or sigma.dtype != torch.float32:
     raise ValueError(f'sigma must be a float32 (X, Y, Z) tensor, got {sigma.dtype} {tuple(sigma.shape)}')
   flat = sigma.permute(2, 1, 0).contiguous().reshape(-1)   # no copy for a tensor laid out as density_grid returns it
   return flat, L.grid(origin, step, sigma.shape)
-
-
-def _dev_stream(device):
-  return torch.cuda.current_stream(device).cuda_stream if device.type == 'cuda' else None   # not cuda: a recording stand-in only
 
 
 def extract_mesh_from_grid(sigma, origin, step, threshold, lib=None):
@@ -327,11 +315,10 @@ def extract_mesh_from_grid(sigma, origin, step, threshold, lib=None):
   device tensors {'vertices' (V, 3) float32, 'vertex_cell' (V,) int32, 'faces' (F, 3) int32}: one vertex per active cell, shared by
   its faces, counter-clockwise faces whose normals point from high density to low, the same bits on every run.  The two counts are
   read back once, to size the outputs; an empty mesh is (0, 3) tensors."""
-  from nerfies_amd import lib as L
   lib = lib or L.load_library()
   flat, grid = _mesh_grid(sigma, origin, step)
   device = flat.device
-  stream = _dev_stream(device)
+  stream = _stream_arg(device)
   nbytes = C.c_size_t(0)
   L.check(lib.nrf_mesh_workspace_bytes(C.byref(grid), C.byref(nbytes)), lib)
   ws = torch.empty((nbytes.value + 3) // 4, dtype=torch.int32, device=device)
@@ -357,7 +344,6 @@ def extract_mesh(model, params, bbox_min, bbox_max, resolution, threshold, level
   `appearance_id` / `camera_id`: the codes the colour is queried with (and, for a use_alpha_condition model, the density).
   Returns device tensors {'vertices' (V, 3), 'faces' (F, 3) int32, 'normals' (V, 3) = -grad sigma / |grad sigma| at the final
   vertices, 'sigma' (V,) there, and with `colors` 'rgb' (V, 3) along MESH_VIEW_DIRECTION}."""
-  from nerfies_amd import lib as L
   res, origin, step = _box_grid(bbox_min, bbox_max, resolution)
   alpha_app = appearance_id if getattr(model, 'use_alpha_condition', False) else None
   sigma = density_grid(model, params, bbox_min, bbox_max, res, level=level, warp_id=warp_id, appearance_id=alpha_app,
@@ -380,7 +366,7 @@ def extract_mesh(model, params, bbox_min, bbox_max, resolution, threshold, level
   for _ in range(int(refine_steps)):
     q = model.query_gradient(params, vertices, outputs=('sigma', 'grad_sigma'), **kw)
     L.check(lib.nrf_mesh_snap(vertices.data_ptr(), vertex_cell.data_ptr(), q['sigma'].data_ptr(), q['grad_sigma'].data_ptr(), C.byref(grid),
-                              float(threshold), nv, _dev_stream(device)), lib)
+                              float(threshold), nv, _stream_arg(device)), lib)
   q = model.query_gradient(params, vertices, outputs=('sigma', 'normals'), **kw)
   out.update(normals=q['normals'], sigma=q['sigma'])
   if colors:

@@ -31,6 +31,28 @@ def _stream(device):
   return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _stream_arg(device):
+  """The `stream` argument of a library call on tensors of `device`, where no device rule stands in front of the call."""
+  # a device other than the GPU is reached only under a recording stand-in for the library (the host tests drive the chunking on CPU
+  # tensors): the library itself follows these pointers on the GPU alone
+  return _stream(device) if device.type == 'cuda' else None
+
+
+def _gpu_reader(what, t):
+  """The device rule: (device, `stream` argument) of `t`, a tensor the library will read; `what` names it in the refusal.  Everything
+  behind it takes the pair as it comes, so a host test that installs a recording stand-in for the library lifts the rule by
+  replacing this one function."""
+  device = torch.as_tensor(t).device
+  if device.type != 'cuda':
+    raise L.NrfError(f'{what} must live on the GPU: the hot path has no CPU fallback')
+  return device, _stream(device)
+
+
+def _ws_tail(ws, stream):
+  """The last three arguments of every entry that runs in a workspace."""
+  return _ptr(ws), ws.numel() * 4, stream
+
+
 def _f32(t, device):
   return torch.as_tensor(t, device=device).to(torch.float32).contiguous()
 
@@ -68,11 +90,49 @@ class CallRecord(NamedTuple):
   generation: int    # NerfModel.generation at the call: it moves when a workspace option replaces the plans
 
 
-def _ray_grad_names(names, allowed, where, what):
+def grid_chunks(total: int, chunk: int):
+  """(first, count) pieces that cover [0, total) exactly once, in order, `chunk` points at most each."""
+  return [(first, min(chunk, total - first)) for first in range(0, total, chunk)]
+
+
+def _select_outputs(outputs, allowed):
+  """`outputs` as a tuple: a non-empty selection of `allowed`."""
+  outputs = tuple(outputs)
+  if not outputs or set(outputs) - set(allowed):
+    raise L.NrfError(f'outputs must be a non-empty selection of {allowed}, got {outputs}')
+  return outputs
+
+
+def _out_struct(out_type, allowed, tensors):
+  """The library's `out_type` over `tensors` ({name: tensor or slice of one}): the fields in the order of `allowed`, a NULL pointer
+  (that output is skipped) for a name that is absent."""
+  return out_type(*(_ptr(tensors.get(k)) for k in allowed))
+
+
+def _require_out(where, name, t, shape, dtype=torch.float32):
+  """`t` is what the library writes a caller-supplied output `name` of `where` into: contiguous, of `dtype` and `shape`."""
+  if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
+    raise L.NrfError(f'{where}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)}')
+
+
+RAY_GRADS = ('origins', 'directions', 'viewdirs')   # the rays' differentiable entries, in the order of lib.RayGrads
+
+
+def _ray_grads_out(where, names, given, num_rays, device, allowed=RAY_GRADS,
+                   what="the rays' differentiable entries are 'origins', 'directions', 'viewdirs'"):
+  """The ray gradients `names` (out of `allowed`, or an NrfError that ends in `what`) of the method `where`: -> ({name: (B, 3) tensor,
+  taken from `given` = the caller's ray_grads_out or allocated}, the lib.RayGrads over them)."""
   names = tuple(names)
   if set(names) - set(allowed):
     raise L.NrfError(f"{where}(ray_grads=...): {sorted(names)} -- {what}")
-  return names
+  out = {}
+  for k in names:
+    out[k] = (given or {}).get(k)
+    if out[k] is None:
+      out[k] = torch.empty(num_rays, 3, device=device)
+    else:
+      _require_out(f'{where}(ray_grads_out=...)', repr(k), out[k], (num_rays, 3))
+  return out, _out_struct(L.RayGrads, RAY_GRADS, out)
 
 
 def _background_struct(background, device):
@@ -249,7 +309,6 @@ class NerfModel:
       'translation': dict(skips=(4,), min_freq_log2=0, max_freq_log2=None, use_identity_map=True, metadata_encoder_num_freqs=1),
   }
   _WARP_KW_TRUNK = {'se3': ('trunk_depth', 'trunk_width'), 'translation': ('depth', 'hidden_channels')}
-  _train_ws = property(lambda self: self.stash)   # the stash under its earlier, private name
 
   def _warp_trunk_shape(self):
     kw = dict(self.warp_kwargs or {})
@@ -368,13 +427,20 @@ class NerfModel:
     elif not plan & L.NRF_FLAG_TRAIN:   # only the TRAINING layout depends on bf16 (bf16 stashes instead of the fp32 ones)
       plan &= ~(L.NRF_FLAG_BF16 | L.NRF_FLAG_WARP_F32)
     key = (plan, int(num_rays), str(device), int(num_background_points), bool(elastic))
+    ws = self._workspace(key, device, self.lib.nrf_workspace_bytes_ex, num_rays, plan, int(num_background_points), int(bool(elastic)))
+    return CallRecord(int(num_rays), ws, flags, self.generation)
+
+  def _workspace(self, key, device, sizer, *args) -> torch.Tensor:
+    """The workspace `sizer(handle, *args, &bytes)` asks for, as float32 words on `device`: the one cached under `key`, made at the
+    first call and kept until a workspace option drops the cache -- or, with key=None, a new one that is not kept."""
     ws = self._ws.get(key)
     if ws is None:
       nbytes = C.c_size_t(0)
-      L.check(self.lib.nrf_workspace_bytes_ex(self.handle, num_rays, plan, int(num_background_points), int(bool(elastic)),
-                                              C.byref(nbytes)), self.lib)
-      ws = self._ws[key] = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=device)
-    return CallRecord(int(num_rays), ws, flags, self.generation)
+      L.check(sizer(self.handle, *args, C.byref(nbytes)), self.lib)
+      ws = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=device)
+      if key is not None:
+        self._ws[key] = ws
+    return ws
 
   def flat_params(self, variables, device) -> P.FlatParams:
     params = variables['params'] if isinstance(variables, dict) and 'params' in variables else variables
@@ -469,9 +535,7 @@ class NerfModel:
         jac_levels.add('fine')
     if train and metadata_encoded:
       raise L.NrfError('metadata_encoded=True is an inference input (the reference never trains with it)')
-    device = torch.as_tensor(rays_dict['origins']).device
-    if device.type != 'cuda':
-      raise L.NrfError('rays must live on the GPU: the hot path has no CPU fallback')
+    device, stream = _gpu_reader('rays', rays_dict['origins'])
     fp = self.flat_params(variables, device)
     rays, keep = self._rays_struct(rays_dict, device, metadata_encoded)
     B = rays.num_rays
@@ -506,8 +570,8 @@ class NerfModel:
     rec = self.last_call = self._record(B, flags, device)
     if train:
       self.stash = rec   # what `backward` differentiates (fp32 or bf16 layout), and the batch size it is for
-    L.check(self.lib.nrf_forward(self.handle, _ptr(fp.flat), C.byref(rays), C.byref(scal), C.byref(rnd), C.byref(out),
-                                 flags, _ptr(rec.ws), rec.ws.numel() * 4, _stream(device)), self.lib)
+    L.check(self.lib.nrf_forward(self.handle, _ptr(fp.flat), C.byref(rays), C.byref(scal), C.byref(rnd), C.byref(out), flags,
+                                 *_ws_tail(rec.ws, stream)), self.lib)
     del keep, keep2
     return ret
 
@@ -516,17 +580,11 @@ class NerfModel:
   QUERY_OUTPUTS = ('sigma', 'rgb', 'warped_points')
   GRADIENT_OUTPUTS = ('sigma', 'grad_sigma', 'normals', 'warped_points')
 
-  def _side_record(self, kind, num_groups, points_per_group, flags, device) -> CallRecord:
-    """The CallRecord of a field query of `kind` ('query' / 'query_grad'), its workspace from the cache of `_record` (keys of its
-    own: a query has a plan of its own), sized by nrf_<kind>_workspace_bytes."""
-    key = (kind, int(num_groups), int(points_per_group), str(device))
-    ws = self._ws.get(key)
-    if ws is None:
-      nbytes = C.c_size_t(0)
-      sizer = getattr(self.lib, f'nrf_{kind}_workspace_bytes')
-      L.check(sizer(self.handle, int(num_groups), int(points_per_group), flags, C.byref(nbytes)), self.lib)
-      ws = self._ws[key] = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=device)
-    return CallRecord(int(num_groups), ws, flags, self.generation)
+  def _query_workspace(self, kind, num_groups, points_per_group, flags, device) -> torch.Tensor:
+    """The workspace of a field query of `kind` ('query' / 'query_grad') from the cache of `_record` (keys of its own: a query has a
+    plan of its own), sized by nrf_<kind>_workspace_bytes."""
+    return self._workspace((kind, int(num_groups), int(points_per_group), str(device)), device,
+                           getattr(self.lib, f'nrf_{kind}_workspace_bytes'), int(num_groups), int(points_per_group), flags)
 
   @staticmethod
   def _point_groups(points, device):
@@ -545,9 +603,7 @@ class NerfModel:
     the level's index, the outputs as a tuple out of `allowed`)."""
     if level not in ('coarse', 'fine'):
       raise L.NrfError(f"level must be 'coarse' or 'fine', got {level!r}")
-    outputs = tuple(outputs)
-    if not outputs or set(outputs) - set(allowed):
-      raise L.NrfError(f'outputs must be a non-empty selection of {allowed}, got {outputs}')
+    outputs = _select_outputs(outputs, allowed)
     fp = self.flat_params(variables, device)
     rows = {}
     for k, v in (metadata or {}).items():   # one row per group, whatever leading dimensions the caller's points had
@@ -571,28 +627,18 @@ class NerfModel:
     self._metadata_into(groups, rows, device, metadata_encoded, keep)
     return groups, keep
 
-  @staticmethod
-  def _check_grid_out(name, out, outputs, count):
-    """Every tensor of `out` named in `outputs` is what a grid call of the public method `name` writes `count` points into."""
-    for k in outputs:
-      want = (count,) if k == 'sigma' else (count, 3)
-      if tuple(out[k].shape) != want or out[k].dtype != torch.float32 or not out[k].is_contiguous():
-        raise L.NrfError(f'{name}: out[{k!r}] must be a contiguous float32 tensor of shape {want}')
-
   def _grid_call(self, name, kind, entry, out_type, allowed, variables, origin, step, dims, first, count, out, viewdirs, metadata,
                  warp_extra, level, use_warp, metadata_encoded, workspace_points):
     """The public method `name`: points [first, first + count) of a grid through `entry`, into the tensors of `out`."""
     device = next(iter(out.values())).device
     fp, rows, scal, flags, lv, outputs = self._query_setup(variables, 1, metadata, warp_extra, level, use_warp, out, allowed, device)
     groups, keep = self._group_rays(1, viewdirs, rows, metadata_encoded, device)
-    self._check_grid_out(name, out, outputs, count)
-    fo = out_type(*(_ptr(out.get(k)) for k in allowed))
-    rec = self._side_record(kind, 1, max(int(workspace_points or 0), int(count)), flags, device)
-    # a device other than the GPU is reached only under a recording stand-in for the library (the host tests drive the chunking on CPU
-    # tensors): the library itself follows these pointers on the GPU alone
-    stream = _stream(device) if device.type == 'cuda' else None
+    for k in outputs:   # what a grid call writes `count` points into
+      _require_out(name, f'out[{k!r}]', out[k], (count,) if k == 'sigma' else (count, 3))
+    fo = _out_struct(out_type, allowed, out)
+    ws = self._query_workspace(kind, 1, max(int(workspace_points or 0), int(count)), flags, device)
     L.check(getattr(self.lib, entry)(self.handle, _ptr(fp.flat), C.byref(groups), C.byref(L.grid(origin, step, dims)), int(first),
-                                     int(count), lv, C.byref(scal), flags, C.byref(fo), _ptr(rec.ws), rec.ws.numel() * 4, stream), self.lib)
+                                     int(count), lv, C.byref(scal), flags, C.byref(fo), *_ws_tail(ws, _stream_arg(device))), self.lib)
     del keep
     return out
 
@@ -604,18 +650,16 @@ class NerfModel:
     row of `viewdirs` (G, 3) and of every `metadata` entry ((G, 1) ids, or (G, features) codes with metadata_encoded).  `outputs`
     selects among 'sigma' (activated density), 'rgb' and 'warped_points'; without 'rgb' the density-only kernel runs.  Returns a
     dict of device tensors shaped like points[..., 0] (with a trailing 3 for 'rgb' / 'warped_points')."""
-    device = torch.as_tensor(points).device
-    if device.type != 'cuda':
-      raise L.NrfError('points must live on the GPU: the hot path has no CPU fallback')
+    device, stream = _gpu_reader('points', points)
     pts, lead, G, S = self._point_groups(points, device)
     fp, rows, scal, flags, lv, outputs = self._query_setup(variables, G, metadata, warp_extra, level, use_warp, outputs,
                                                            self.QUERY_OUTPUTS, device)
     groups, keep = self._group_rays(G, viewdirs, rows, metadata_encoded, device)
     ret = {k: torch.empty(*lead, S, *(() if k == 'sigma' else (3,)), dtype=torch.float32, device=device) for k in outputs}
-    fo = L.FieldOut(*(_ptr(ret.get(k)) for k in self.QUERY_OUTPUTS))
-    rec = self._side_record('query', G, S, flags, device)
+    fo = _out_struct(L.FieldOut, self.QUERY_OUTPUTS, ret)
+    ws = self._query_workspace('query', G, S, flags, device)
     L.check(self.lib.nrf_query_points(self.handle, _ptr(fp.flat), C.byref(groups), _ptr(pts), S, lv, C.byref(scal), flags, C.byref(fo),
-                                      _ptr(rec.ws), rec.ws.numel() * 4, _stream(device)), self.lib)
+                                      *_ws_tail(ws, stream)), self.lib)
     del keep
     return ret
 
@@ -635,33 +679,25 @@ class NerfModel:
     grouped as in `query_points`; no view direction is read.  `outputs` selects among 'sigma', 'grad_sigma', 'normals' and
     'warped_points'.  More than NRF_QUERY_GRAD_MAX_POINTS points run as chunks of whole groups (or, one group, of points) through
     one cached workspace.  Returns a dict of device tensors shaped like points[..., 0] (a trailing 3 for all but 'sigma')."""
-    device = torch.as_tensor(points).device
-    if device.type != 'cuda':
-      raise L.NrfError('points must live on the GPU: the hot path has no CPU fallback')
-    return self._query_gradient_chunks(variables, points, metadata, warp_extra, level, use_warp, metadata_encoded, outputs, device)
-
-  def _query_gradient_chunks(self, variables, points, metadata, warp_extra, level, use_warp, metadata_encoded, outputs, device):
-    """`query_gradient` behind its device rule: the calls into the library, one per chunk."""
+    device, stream = _gpu_reader('points', points)
     pts, lead, G, S = self._point_groups(points, device)
     fp, rows, scal, flags, lv, outputs = self._query_setup(variables, G, metadata, warp_extra, level, use_warp, outputs,
                                                            self.GRADIENT_OUTPUTS, device)
-    stream = _stream(device) if device.type == 'cuda' else None   # not cuda: a recording stand-in for the library only, as in _grid_call
     pts = pts.reshape(G, S, 3)
     ret = {k: torch.empty(G, S, *(() if k == 'sigma' else (3,)), dtype=torch.float32, device=device) for k in outputs}
     cap = L.NRF_QUERY_GRAD_MAX_POINTS
     if S <= cap:   # chunks of whole groups
-      per = cap // S
-      pieces = [(g0, min(per, G - g0), 0, S) for g0 in range(0, G, per)]
+      pieces = [(g0, ng, 0, S) for g0, ng in grid_chunks(G, cap // S)]
     elif G == 1:   # one long group: chunks of its points
-      pieces = [(0, 1, s0, min(cap, S - s0)) for s0 in range(0, S, cap)]
+      pieces = [(0, 1, s0, ns) for s0, ns in grid_chunks(S, cap)]
     else:
       raise L.NrfError(f'query_gradient: groups of more than NRF_QUERY_GRAD_MAX_POINTS = {cap} points are chunked only when there is one group')
-    rec = self._side_record('query_grad', pieces[0][1], pieces[0][3], flags, device)   # the first piece is the largest
+    ws = self._query_workspace('query_grad', pieces[0][1], pieces[0][3], flags, device)   # the first piece is the largest
     for g0, ng, s0, ns in pieces:   # every slice below is contiguous: whole groups, or a run of the one group's points
       groups, keep = self._group_rays(ng, None, {k: v[g0:g0 + ng] for k, v in rows.items()}, metadata_encoded, device)
-      fo = L.FieldGradOut(*(_ptr(ret[k][g0:g0 + ng, s0:s0 + ns]) if k in ret else None for k in self.GRADIENT_OUTPUTS))
+      fo = _out_struct(L.FieldGradOut, self.GRADIENT_OUTPUTS, {k: v[g0:g0 + ng, s0:s0 + ns] for k, v in ret.items()})
       L.check(self.lib.nrf_query_points_grad(self.handle, _ptr(fp.flat), C.byref(groups), _ptr(pts[g0:g0 + ng, s0:s0 + ns]), ns, lv,
-                                             C.byref(scal), flags, C.byref(fo), _ptr(rec.ws), rec.ws.numel() * 4, stream), self.lib)
+                                             C.byref(scal), flags, C.byref(fo), *_ws_tail(ws, stream)), self.lib)
       del keep
     return {k: v.reshape(*lead, S, *v.shape[2:]) for k, v in ret.items()}
 
@@ -696,14 +732,11 @@ class NerfModel:
     frozen = bool(stash.flags & L.NRF_FLAG_FROZEN)   # no parameter gradient: NULL (a grad_out is the library's to refuse, NRF_E_STATE)
     grad = grad_out if grad_out is not None or frozen else torch.empty_like(fp.flat)
     og, keep2 = self._output_grads(d_out or {}, {'coarse': d_rgb_coarse, 'fine': d_rgb_fine}, B, device)
-    tail = (_ptr(grad), _ptr(ws), ws.numel() * 4, _stream(device))
+    tail = (_ptr(grad), *_ws_tail(ws, _stream(device)))
     if ray_grads:
       if ray_grads is True:
         ray_grads = ('origins', 'directions') + (('viewdirs',) if self.use_viewdirs and 'viewdirs' in rays_dict else ())
-      names = _ray_grad_names(ray_grads, ('origins', 'directions', 'viewdirs'), 'backward',
-                              "the rays' differentiable entries are 'origins', 'directions', 'viewdirs'")
-      rg_out = {k: torch.empty(B, 3, device=device) for k in names}
-      rg = L.RayGrads(*(_ptr(rg_out.get(k)) for k in ('origins', 'directions', 'viewdirs')))
+      rg_out, rg = _ray_grads_out('backward', ray_grads, None, B, device)
       L.check(self.lib.nrf_backward_rays(self.handle, _ptr(fp.flat), C.byref(rays), C.byref(og), C.byref(rg), *tail), self.lib)
     else:
       L.check(self.lib.nrf_backward_ex(self.handle, _ptr(fp.flat), C.byref(rays), C.byref(og), *tail), self.lib)
@@ -768,21 +801,15 @@ class NerfModel:
     el, wr = _elastic_struct(elastic), _warp_reg_struct(warp_reg)
     flags = self.flags(True, bf16, ray_grads=ray_grads is not None)
     rec = self.stash = self.last_call = self._record(rays.num_rays, flags, device, nbg, el is not None)
-    head = (self.handle, _ptr(fp.flat), C.byref(rays), _ptr(target), C.byref(scal), C.byref(rnd), _ref(bg), _ref(el), _ref(wr))
-    tail = (_ptr(grad), _ptr(stats), _ptr(rec.ws), rec.ws.numel() * 4, _stream(device))
     # each entry takes the word without the bits its ABI implies: _ex the bf16 bits, _rays (float32 only) none
     if ray_grads is None:
-      L.check(self.lib.nrf_train_step_loss_grad_ex(*head, flags & ~L.NRF_FLAG_TRAIN, *tail), self.lib)
+      entry, mid = self.lib.nrf_train_step_loss_grad_ex, (flags & ~L.NRF_FLAG_TRAIN,)
     else:
-      names = _ray_grad_names(ray_grads, ('origins', 'directions'), 'loss_and_grad', "the fused step returns 'origins' and 'directions'")
-      rg_out = {k: (ray_grads_out or {}).get(k) for k in names}
-      for k in names:
-        if rg_out[k] is None:
-          rg_out[k] = torch.empty(rays.num_rays, 3, device=device)
-        elif tuple(rg_out[k].shape) != (rays.num_rays, 3) or rg_out[k].dtype != torch.float32 or not rg_out[k].is_contiguous():
-          raise L.NrfError(f'loss_and_grad(ray_grads_out=...): {k!r} must be a contiguous float32 ({rays.num_rays}, 3) tensor')
-      rg = L.RayGrads(_ptr(rg_out.get('origins')), _ptr(rg_out.get('directions')), None)
-      L.check(self.lib.nrf_train_step_loss_grad_rays(*head, flags & ~(L.NRF_FLAG_TRAIN | L.NRF_FLAG_RAY_GRADS), C.byref(rg), *tail), self.lib)
+      rg_out, rg = _ray_grads_out('loss_and_grad', ray_grads, ray_grads_out, rays.num_rays, device, RAY_GRADS[:2],
+                                  "the fused step returns 'origins' and 'directions'")
+      entry, mid = self.lib.nrf_train_step_loss_grad_rays, (flags & ~(L.NRF_FLAG_TRAIN | L.NRF_FLAG_RAY_GRADS), C.byref(rg))
+    L.check(entry(self.handle, _ptr(fp.flat), C.byref(rays), _ptr(target), C.byref(scal), C.byref(rnd), _ref(bg), _ref(el), _ref(wr), *mid,
+                  _ptr(grad), _ptr(stats), *_ws_tail(rec.ws, _stream(device))), self.lib)
     del keep, keep2, keep3
     return (grad, stats) if ray_grads is None else (grad, stats, rg_out)
 
@@ -799,18 +826,10 @@ class NerfModel:
     target = _f32(batch['rgb'], device)[..., :3].contiguous()
     stats = stats_out if stats_out is not None else torch.empty(L.NRF_NUM_STATS, device=device)
     scal = _scalars(warp_extra, dynamic)
-    names = _ray_grad_names(ray_grads, ('origins', 'directions', 'viewdirs'), 'loss_and_ray_grads',
-                            "the rays' differentiable entries are 'origins', 'directions', 'viewdirs'")
-    rg_out = {k: (ray_grads_out or {}).get(k) for k in names}
-    for k in names:
-      if rg_out[k] is None:
-        rg_out[k] = torch.empty(rays.num_rays, 3, device=device)
-      elif tuple(rg_out[k].shape) != (rays.num_rays, 3) or rg_out[k].dtype != torch.float32 or not rg_out[k].is_contiguous():
-        raise L.NrfError(f'loss_and_ray_grads(ray_grads_out=...): {k!r} must be a contiguous float32 ({rays.num_rays}, 3) tensor')
-    rg = L.RayGrads(*(_ptr(rg_out.get(k)) for k in ('origins', 'directions', 'viewdirs')))
+    rg_out, rg = _ray_grads_out('loss_and_ray_grads', ray_grads, ray_grads_out, rays.num_rays, device)
     rec = self.stash = self.last_call = self._record(rays.num_rays, self.flags(True, ray_grads=True, frozen=True), device)
     L.check(self.lib.nrf_loss_grad_rays(self.handle, _ptr(fp.flat), C.byref(rays), _ptr(target), C.byref(scal), C.byref(rnd), C.byref(rg),
-                                        _ptr(stats), _ptr(rec.ws), rec.ws.numel() * 4, _stream(device)), self.lib)
+                                        _ptr(stats), *_ws_tail(rec.ws, _stream(device))), self.lib)
     del keep, keep2
     return stats, rg_out
 
@@ -822,13 +841,12 @@ class NerfModel:
     pts = _f32(points, device).reshape(-1, 3)
     ids = _ids(warp_ids, device).reshape(-1)
     n = pts.shape[0]
-    nbytes = C.c_size_t(0)
-    L.check(self.lib.nrf_warp_points_workspace_bytes(self.handle, n, C.byref(nbytes)), self.lib)
-    ws = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=device)
+    # no cache key: callers pass arbitrary point counts, and a workspace kept per count would only pile up
+    ws = self._workspace(None, device, self.lib.nrf_warp_points_workspace_bytes, n)
     out = torch.empty(n, 3, device=device)
     scal = _scalars(warp_extra)
-    L.check(self.lib.nrf_warp_points(self.handle, _ptr(fp.flat), _ptr(pts), _ptr(ids), n, C.byref(scal), _ptr(out), _ptr(ws),
-                                     ws.numel() * 4, _stream(device)), self.lib)
+    L.check(self.lib.nrf_warp_points(self.handle, _ptr(fp.flat), _ptr(pts), _ptr(ids), n, C.byref(scal), _ptr(out),
+                                     *_ws_tail(ws, _stream(device))), self.lib)
     return out.reshape(torch.as_tensor(points).shape)
 
   UNWARP_OUTPUTS = ('points', 'residual', 'status')
@@ -842,16 +860,8 @@ class NerfModel:
     (at the returned x) and 'status' (int32: 0 ran out of steps, 1 converged, 2 stopped at a singular or non-finite step).  More
     than NRF_UNWARP_MAX_POINTS points run as chunks through one cached workspace.  Returns a dict of device tensors shaped like
     points[..., 0] (a trailing 3 for 'points')."""
-    device = torch.as_tensor(points).device
-    if device.type != 'cuda':
-      raise L.NrfError('points must live on the GPU: the hot path has no CPU fallback')
-    return self._unwarp_chunks(variables, points, warp_ids, warp_extra, guess, steps, tolerance, max_step, warp_codes, outputs, device)
-
-  def _unwarp_chunks(self, variables, points, warp_ids, warp_extra, guess, steps, tolerance, max_step, warp_codes, outputs, device):
-    """`unwarp_points` behind its device rule: the calls into the library, one per chunk."""
-    outputs = tuple(outputs)
-    if not outputs or set(outputs) - set(self.UNWARP_OUTPUTS):
-      raise L.NrfError(f'outputs must be a non-empty selection of {self.UNWARP_OUTPUTS}, got {outputs}')
+    device, stream = _gpu_reader('points', points)
+    outputs = _select_outputs(outputs, self.UNWARP_OUTPUTS)
     y = _f32(points, device)
     if y.dim() < 1 or y.shape[-1] != 3:
       raise L.NrfError(f'points must be (..., 3), got {tuple(y.shape)}')
@@ -869,23 +879,17 @@ class NerfModel:
     codes = None if warp_codes is None else _f32(warp_codes, device).reshape(-1, self.num_warp_features)
     fp = self.flat_params(variables, device)
     scal = _scalars(warp_extra)
-    stream = _stream(device) if device.type == 'cuda' else None   # not cuda: a recording stand-in for the library only, as in _grid_call
     ret = {k: torch.empty(n, *((3,) if k == 'points' else ()), dtype=torch.int32 if k == 'status' else torch.float32, device=device)
            for k in outputs}
-    cap = L.NRF_UNWARP_MAX_POINTS
-    key = ('unwarp', min(n, cap), str(device))   # the first chunk is the largest
-    ws = self._ws.get(key)
-    if ws is None:
-      nbytes = C.c_size_t(0)
-      L.check(self.lib.nrf_unwarp_workspace_bytes(self.handle, min(n, cap), C.byref(nbytes)), self.lib)
-      ws = self._ws[key] = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=device)
-    for r0 in range(0, n, cap):
-      r1 = min(n, r0 + cap)
-      uo = L.UnwarpOut(*(_ptr(ret[k][r0:r1]) if k in ret else None for k in self.UNWARP_OUTPUTS))
+    first = min(n, L.NRF_UNWARP_MAX_POINTS)   # the first chunk is the largest
+    ws = self._workspace(('unwarp', first, str(device)), device, self.lib.nrf_unwarp_workspace_bytes, first)
+    for r0, nr in grid_chunks(n, L.NRF_UNWARP_MAX_POINTS):
+      r1 = r0 + nr
+      uo = _out_struct(L.UnwarpOut, self.UNWARP_OUTPUTS, {k: v[r0:r1] for k, v in ret.items()})
       L.check(self.lib.nrf_unwarp_points(self.handle, _ptr(fp.flat), _ptr(y[r0:r1]), _ptr(ids[r0:r1]), _ptr(codes),
-                                         0 if codes is None else codes.shape[0], None if x0 is None else _ptr(x0[r0:r1]), r1 - r0,
-                                         C.byref(scal), int(steps), float(tolerance), float(max_step), C.byref(uo), _ptr(ws),
-                                         ws.numel() * 4, stream), self.lib)
+                                         0 if codes is None else codes.shape[0], None if x0 is None else _ptr(x0[r0:r1]), nr,
+                                         C.byref(scal), int(steps), float(tolerance), float(max_step), C.byref(uo),
+                                         *_ws_tail(ws, stream)), self.lib)
     return {k: v.reshape(*lead, *v.shape[1:]) for k, v in ret.items()}
 
   def profile_enable(self, on=True):

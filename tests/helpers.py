@@ -1,4 +1,6 @@
 """Shared test plumbing: oracle ModelSpec -> nerfies_amd model on the GPU with identical parameters."""
+import ctypes as C
+import functools
 import os
 import types
 
@@ -45,6 +47,79 @@ def gpu_model(spec, oparams, batch_size=0):
       list(range(spec.num_camera_embeddings)), list(range(spec.num_warp_embeddings)), spec.near, spec.far)
   P.flat_from_tree(O.tree_map(lambda t: t.float(), oparams), model.layout, DEV, out=fp.flat)
   return model, fp
+
+
+# ---------------------------------------------------------------------------------------------
+# The Python host without a GPU: a model on CPU tensors whose library records the entries that would follow device pointers
+# ---------------------------------------------------------------------------------------------
+_ENTRY_ARGS = {   # entry -> (its `fn` in a record, the names of its arguments in the header's order)
+    'nrf_query_points': ('points', 'h params groups points S level scalars flags out ws nbytes stream'),
+    'nrf_query_points_grad': ('grad', 'h params groups points S level scalars flags out ws nbytes stream'),
+    'nrf_query_grid': ('grid', 'h params groups grid first count level scalars flags out ws nbytes stream'),
+    'nrf_query_grid_grad': ('grid_grad', 'h params groups grid first count level scalars flags out ws nbytes stream'),
+    'nrf_unwarp_points': ('unwarp', 'h params targets ids codes num_codes guess n scalars steps tolerance max_step out ws nbytes stream'),
+    'nrf_mesh_count': ('count', 'sigma grid thr counts ws nbytes stream'),
+    'nrf_mesh_emit': ('emit', 'sigma grid thr mv mt vertices cell tris ws nbytes stream'),
+    'nrf_mesh_snap': ('snap', 'vertices cell sigma_at grad_at grid thr n stream'),
+}
+_FIELD_NAMES = {'grad_sigma': 'grad', 'warped_points': 'warped', 'warp_alpha': 'alpha'}   # struct fields under the records' shorter names
+
+
+class RecordingLib:
+  """The library with the entries `names` replaced by recorders that return 0; every other entry (handle, layout, workspace sizes)
+  is the real one.  A record is a dict: `fn`, every scalar argument and pointer value under the argument's name, and the fields
+  of every struct argument (lib.Rays, lib.Grid, the out struct, lib.StepScalars) under their own (_FIELD_NAMES).  No recorder
+  follows a pointer, so the host code runs on CPU tensors; the one of nrf_mesh_count reports `found` = (vertices, triangles)
+  through its counts pointer (host memory then).  `peek(record)` sees a record while the call's tensors are still alive."""
+
+  def __init__(self, real, names, found=(0, 0), peek=None):
+    self._real, self._names, self.found, self.peek = real, tuple(names), found, peek
+    self.calls = []
+
+  def __getattr__(self, name):
+    return functools.partial(self._record, name) if name in self._names else getattr(self._real, name)
+
+  def _record(self, name, *args):
+    fn, argnames = _ENTRY_ARGS.get(name, (name, ''))
+    call = dict(fn=fn) if argnames else dict(fn=fn, args=args)
+    for k, v in zip(argnames.split(), args):
+      v = getattr(v, '_obj', v)   # ctypes.byref(struct)
+      if isinstance(v, C.Structure):
+        for f, _ in v._fields_:
+          x = getattr(v, f)
+          call[_FIELD_NAMES.get(f, f)] = tuple(x) if isinstance(x, C.Array) else x
+      else:
+        call[k] = v.value if isinstance(v, C.c_void_p) else v
+    if name == 'nrf_mesh_count':
+      out = C.cast(call['counts'], C.POINTER(C.c_int32))
+      out[0], out[1] = self.found
+    if self.peek is not None:
+      self.peek(call)
+    self.calls.append(call)
+    return 0
+
+
+def cpu_field_model(lib, **cfg):
+  """(model, FlatParams) on the CPU for the host tests of the field entries: a small SE3 model with three warp ids and two appearance
+  and camera ids, its library `lib` (a RecordingLib)."""
+  from nerfies_amd import models
+  cfg = types.SimpleNamespace(**dict(dict(use_warp=True, warp_field_type='se3', num_warp_freqs=4, num_nerf_point_freqs=6,
+                                          sigma_activation='softplus', use_stratified_sampling=False), **cfg))
+  model, fp = models.construct_nerf(0, cfg, 0, [0, 1], [0, 1], [0, 1, 2], 0.1, 1.0, device='cpu')
+  model._lib = lib
+  return model, fp
+
+
+def lift_device_rule(monkeypatch):
+  """NerfModel's device rule (models._gpu_reader) lifted for a test: a tensor of any device passes, and the call gets no stream.  For
+  a model whose library is a RecordingLib: the public methods then run on CPU tensors."""
+  from nerfies_amd import models
+  monkeypatch.setattr(models, '_gpu_reader', lambda what, t: (torch.as_tensor(t).device, None))
+
+
+def ws_bytes(nbytes):
+  """The bytes of the float32 workspace NerfModel allocates for a sizer's answer `nbytes` (rounded up to whole floats)."""
+  return 4 * ((nbytes + 3) // 4)
 
 
 def gpu_batch(batch):

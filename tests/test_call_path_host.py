@@ -141,3 +141,49 @@ def test_backward_without_a_stash():
                    ((), {'ray_grads': True}), ((), {'d_out': {}, 'ray_grads': ('origins',)})):
     with pytest.raises(L.NrfError, match=r'backward\(\) needs a preceding apply\(\.\.\., train=True\)'):
       model.backward(variables, rays, *args, **kw)
+
+
+def _recording_model(names, **cfg):
+  """tests/helpers.py::cpu_field_model behind a RecordingLib for the entries `names`."""
+  import helpers as H
+  from nerfies_amd import lib as L
+  rec = H.RecordingLib(L.load_library(), names)
+  return (*H.cpu_field_model(rec, **cfg), rec)
+
+
+@pytest.mark.parametrize('bad', ['shape', 'dtype', 'stride'])
+def test_fused_steps_refuse_a_ray_gradient_output_they_cannot_write(bad):
+  from nerfies_amd import lib as L
+  model, fp, rec = _recording_model(['nrf_train_step_loss_grad_ex', 'nrf_train_step_loss_grad_rays', 'nrf_loss_grad_rays'],
+                                    num_coarse_samples=8, num_fine_samples=6)
+  batch = {'origins': torch.zeros(B, 3), 'directions': torch.ones(B, 3), 'rgb': torch.zeros(B, 3),
+           'metadata': {'warp': torch.zeros(B, 1, dtype=torch.int32)}}
+  out = {'shape': torch.zeros(B + 1, 3), 'dtype': torch.zeros(B, 3, dtype=torch.float64), 'stride': torch.zeros(3, B).t()}[bad]
+  for step in (model.loss_and_grad, model.loss_and_ray_grads):
+    with pytest.raises(L.NrfError, match=rf"{step.__name__}\(ray_grads_out=\.\.\.\): 'directions' .*\({B}, 3\)"):
+      step(fp, batch, ray_grads=('origins', 'directions'), ray_grads_out={'directions': out})
+  assert rec.calls == []
+
+
+def test_workspace_options_drop_the_field_workspaces_with_the_rest(monkeypatch):
+  import helpers as H
+  model, fp, rec = _recording_model(['nrf_query_points', 'nrf_query_points_grad', 'nrf_unwarp_points'])
+  H.lift_device_rule(monkeypatch)
+  pts, ids = torch.zeros(5, 3), torch.zeros(5, dtype=torch.int32)
+  keys = [('query', 1, 5, 'cpu'), ('query_grad', 1, 5, 'cpu'), ('unwarp', 5, 'cpu')]
+
+  def run():
+    """One call of each kind -> the workspace each ran in."""
+    rec.calls.clear()
+    model.query_points(fp, pts, metadata={'warp': ids[:1]}, outputs=('sigma',))
+    model.query_gradient(fp, pts, metadata={'warp': ids[:1]}, outputs=('sigma',))
+    model.unwarp_points(fp, pts, ids, None, outputs=('points',))
+    assert [c['ws'] for c in rec.calls] == [model._ws[k].data_ptr() for k in keys] and len(model._ws) == 3
+    return [c['ws'] for c in rec.calls]
+
+  first = run()
+  assert run() == first   # the cached ones, handed out again
+  held, g0 = dict(model._ws), model.generation   # the old tensors stay alive here: a new one cannot be given one's address
+  model.set_chain_tile_rows(32)
+  assert model._ws == {} and model.generation == g0 + 1
+  assert not set(run()) & set(first) and all(model._ws[k] is not held[k] for k in keys)

@@ -11,6 +11,8 @@ import subprocess
 
 import pytest
 
+import helpers as H
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'nerfies_amd.h')
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
@@ -267,47 +269,11 @@ def test_other_plans_stay_behind_a_gradient_plan(lib, handles):
     assert mod.sizes(lib) == json.load(fp)['sizes']
 
 
-class _RecordingLib:
-  """The library with the two gradient entries replaced by recorders: every other entry (handle, layout, workspace size) is the real one."""
-
-  def __init__(self, real):
-    self._real = real
-    self.calls = []
-
-  def __getattr__(self, name):
-    return getattr(self._real, name)
-
-  @staticmethod
-  def _out(o):
-    return dict(sigma=o.sigma, grad=o.grad_sigma, normals=o.normals, warped=o.warped_points)
-
-  def nrf_query_grid_grad(self, h, params, group, grid, first, count, level, scalars, flags, out, ws, nbytes, stream):
-    g = grid._obj
-    self.calls.append(dict(first=int(first), count=int(count), level=int(level), flags=int(flags), dims=tuple(g.dims), origin=tuple(g.origin),
-                           step=tuple(g.step), nbytes=int(nbytes), num_rays=group._obj.num_rays, warp_ids=group._obj.warp_ids,
-                           **self._out(out._obj)))
-    return 0
-
-  def nrf_query_points_grad(self, h, params, groups, points, S, level, scalars, flags, out, ws, nbytes, stream):
-    self.calls.append(dict(points=points.value, S=int(S), level=int(level), flags=int(flags), nbytes=int(nbytes), ws=ws.value,
-                           num_rays=groups._obj.num_rays, warp_ids=groups._obj.warp_ids, **self._out(out._obj)))
-    return 0
-
-
-def _cpu_model(lib):
-  import types
-  from nerfies_amd import models
-  cfg = types.SimpleNamespace(use_warp=True, warp_field_type='se3', num_warp_freqs=4, num_nerf_point_freqs=6, sigma_activation='softplus',
-                              use_stratified_sampling=False)
-  model, fp = models.construct_nerf(0, cfg, 0, [0], [0], [0, 1, 2], 0.1, 1.0, device='cpu')
-  rec = model._lib = _RecordingLib(lib)
-  return model, fp, rec
-
-
 def test_normal_grid_chunks_cover_the_grid_once(lib):
   import torch
   from nerfies_amd import evaluation, lib as L
-  model, fp, rec = _cpu_model(lib)
+  rec = H.RecordingLib(lib, ['nrf_query_grid_grad', 'nrf_query_points_grad'])
+  model, fp = H.cpu_field_model(rec)
   res, chunk = (5, 3, 7), 32                                   # 105 points: 32 + 32 + 32 + 9
   sigma, normals = evaluation.normal_grid(model, fp, (-1.0, 0.0, 1.0), (1.0, 3.0, 2.0), res, level='coarse', warp_id=2, chunk=chunk)
   assert tuple(sigma.shape) == res and sigma.stride() == (1, 5, 15) and sigma.dtype == torch.float32   # x fastest in memory, as density_grid
@@ -323,6 +289,8 @@ def test_normal_grid_chunks_cover_the_grid_once(lib):
   assert [(c['first'], c['count']) for c in rec.calls] == evaluation.grid_chunks(105, chunk)
   assert bool((seen == 1).all())
   assert len({c['nbytes'] for c in rec.calls}) == 1              # one workspace serves every chunk
+  n = C.c_size_t(0)                                              # ... of the size the library asks for one whole chunk
+  assert lib.nrf_query_grad_workspace_bytes(model.handle, 1, chunk, 0, C.byref(n)) == 0 and rec.calls[0]['nbytes'] == H.ws_bytes(n.value)
   # the canonical volume: no warp id, NRF_FLAG_NO_WARP; a chunk larger than the cap is cut down to it
   rec.calls.clear()
   evaluation.normal_grid(model, fp, (0, 0, 0), (1, 1, 1), 4, chunk=1 << 30)
@@ -337,13 +305,14 @@ def test_query_gradient_chunks_cover_the_points_once(lib, monkeypatch):
   so the chunking runs on CPU tensors."""
   import torch
   from nerfies_amd import lib as L
-  model, fp, rec = _cpu_model(lib)
+  rec = H.RecordingLib(lib, ['nrf_query_grid_grad', 'nrf_query_points_grad'])
+  model, fp = H.cpu_field_model(rec)
   with pytest.raises(L.NrfError, match='GPU'):
     model.query_gradient(fp, torch.zeros(4, 3))
   assert rec.calls == []
   monkeypatch.setattr(L, 'NRF_QUERY_GRAD_MAX_POINTS', 100)     # the Python side's chunk size; the library's own cap is tested above
-  cpu = torch.device('cpu')
-  run = lambda pts, md, use_warp, outputs: model._query_gradient_chunks(fp, pts, md, None, 'fine', use_warp, False, outputs, cpu)
+  H.lift_device_rule(monkeypatch)
+  run = lambda pts, md, use_warp, outputs: model.query_gradient(fp, pts, metadata=md, use_warp=use_warp, outputs=outputs)
   G, S = 7, 37                                                 # 2 groups per call: 2 + 2 + 2 + 1
   ids = torch.arange(G, dtype=torch.int32).reshape(G, 1) % 3
   out = run(torch.zeros(G, S, 3), {'warp': ids}, True, ('sigma', 'grad_sigma'))
@@ -356,6 +325,8 @@ def test_query_gradient_chunks_cover_the_points_once(lib, monkeypatch):
     g0 += c['num_rays']
   assert g0 == G
   assert len({(c['ws'], c['nbytes']) for c in rec.calls}) == 1  # one cached workspace, sized for the largest piece
+  n = C.c_size_t(0)                                            # ... by the library itself: two groups of 37 points
+  assert lib.nrf_query_grad_workspace_bytes(model.handle, 2, S, 0, C.byref(n)) == 0 and rec.calls[0]['nbytes'] == H.ws_bytes(n.value)
   # leading dimensions are flattened into groups and restored
   rec.calls.clear()
   out = run(torch.zeros(2, 3, 5, 3), {'warp': ids[:6].reshape(2, 3, 1)}, True, ('normals',))
@@ -366,5 +337,7 @@ def test_query_gradient_chunks_cover_the_points_once(lib, monkeypatch):
   assert tuple(out['normals'].shape) == (250, 3)
   assert [(c['num_rays'], c['S'], c['normals'] - out['normals'].data_ptr()) for c in rec.calls] == [(1, 100, 0), (1, 100, 1200), (1, 50, 2400)]
   assert all(c['flags'] == L.NRF_FLAG_NO_WARP and c['warp_ids'] is None for c in rec.calls)
+  assert lib.nrf_query_grad_workspace_bytes(model.handle, 1, 100, L.NRF_FLAG_NO_WARP, C.byref(n)) == 0
+  assert {c['nbytes'] for c in rec.calls} == {H.ws_bytes(n.value)}  # one group's first 100 points
   with pytest.raises(L.NrfError, match='outputs'):
     run(torch.zeros(4, 3), {}, False, ('rgb',))

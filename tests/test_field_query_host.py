@@ -11,6 +11,8 @@ import subprocess
 
 import pytest
 
+import helpers as H
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'nerfies_amd.h')
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
@@ -264,33 +266,11 @@ def test_side_plan_sizes_match_the_record(lib):
   assert all(v > 0 for v in want.values())                    # no entry refuses a listed case
 
 
-class _RecordingLib:
-  """The library with nrf_query_grid replaced by a recorder: every other entry (handle, layout, workspace size) is the real one."""
-
-  def __init__(self, real):
-    self._real = real
-    self.calls = []
-
-  def __getattr__(self, name):
-    return getattr(self._real, name)
-
-  def nrf_query_grid(self, h, params, group, grid, first, count, level, scalars, flags, out, ws, nbytes, stream):
-    g = grid._obj
-    o = out._obj
-    self.calls.append(dict(first=int(first), count=int(count), level=int(level), flags=int(flags), dims=tuple(g.dims), origin=tuple(g.origin),
-                           step=tuple(g.step), sigma=o.sigma, rgb=o.rgb, warped=o.warped_points, nbytes=int(nbytes),
-                           num_rays=group._obj.num_rays, warp_ids=group._obj.warp_ids))
-    return 0
-
-
 def test_density_grid_chunks_cover_the_grid_once(lib):
   import torch
-  import types
-  from nerfies_amd import evaluation, lib as L, models
-  cfg = types.SimpleNamespace(use_warp=True, warp_field_type='se3', num_warp_freqs=4, num_nerf_point_freqs=6, sigma_activation='softplus',
-                              use_stratified_sampling=False)
-  model, fp = models.construct_nerf(0, cfg, 0, [0], [0], [0, 1, 2], 0.1, 1.0, device='cpu')
-  rec = model._lib = _RecordingLib(lib)
+  from nerfies_amd import evaluation, lib as L
+  rec = H.RecordingLib(lib, ['nrf_query_grid'])
+  model, fp = H.cpu_field_model(rec)
   res, chunk = (5, 3, 7), 32                                   # 105 points: 32 + 32 + 32 + 9
   assert evaluation.grid_chunks(105, 32) == [(0, 32), (32, 32), (64, 32), (96, 9)]
   out = evaluation.density_grid(model, fp, (-1.0, 0.0, 1.0), (1.0, 3.0, 2.0), res, level='coarse', warp_id=2, chunk=chunk)
@@ -305,6 +285,8 @@ def test_density_grid_chunks_cover_the_grid_once(lib):
   assert [(c['first'], c['count']) for c in rec.calls] == evaluation.grid_chunks(105, chunk)
   assert bool((seen == 1).all())
   assert len({c['nbytes'] for c in rec.calls}) == 1              # one workspace serves every chunk
+  n = C.c_size_t(0)                                              # ... of the size the library asks for one whole chunk
+  assert lib.nrf_query_workspace_bytes(model.handle, 1, chunk, 0, C.byref(n)) == 0 and rec.calls[0]['nbytes'] == H.ws_bytes(n.value)
   # the canonical volume: no warp id, NRF_FLAG_NO_WARP; a chunk larger than the grid is one call
   rec.calls.clear()
   evaluation.density_grid(model, fp, (0, 0, 0), (1, 1, 1), 4, chunk=1 << 21)
@@ -313,3 +295,38 @@ def test_density_grid_chunks_cover_the_grid_once(lib):
     pieces = evaluation.grid_chunks(total, ch)
     assert pieces[0][0] == 0 and sum(n for _, n in pieces) == total and all(0 < n <= ch for _, n in pieces)
     assert all(a + n == b for (a, n), (b, _) in zip(pieces, pieces[1:]))
+
+
+def test_query_points_runs_in_the_librarys_workspace(lib, monkeypatch):
+  """NerfModel.query_points behind its device rule (CPU points raise before anything else): one call, in a cached workspace of the
+  size the library asks for its groups."""
+  import torch
+  from nerfies_amd import lib as L
+  rec = H.RecordingLib(lib, ['nrf_query_points'])
+  model, fp = H.cpu_field_model(rec)
+  pts, view, ids = torch.zeros(3, 5, 3), torch.zeros(3, 3), torch.arange(3, dtype=torch.int32).reshape(3, 1)
+  with pytest.raises(L.NrfError, match='GPU'):
+    model.query_points(fp, pts, viewdirs=view, metadata={'warp': ids})
+  assert rec.calls == []
+  H.lift_device_rule(monkeypatch)
+  run = lambda: model.query_points(fp, pts, viewdirs=view, metadata={'warp': ids})
+  out = run()
+  (c,) = rec.calls
+  assert (c['num_rays'], c['S'], c['level'], c['flags']) == (3, 5, 1, 0) and c['points'] == pts.data_ptr()
+  assert c['sigma'] == out['sigma'].data_ptr() and c['rgb'] == out['rgb'].data_ptr() and c['warped'] is None
+  n = C.c_size_t(0)
+  assert lib.nrf_query_workspace_bytes(model.handle, 3, 5, 0, C.byref(n)) == 0 and c['nbytes'] == H.ws_bytes(n.value)
+  run()
+  assert rec.calls[1]['ws'] == c['ws'] == model._ws['query', 3, 5, 'cpu'].data_ptr()   # the cached one, handed out again
+
+
+@pytest.mark.parametrize('bad', ['shape', 'dtype', 'stride'])
+def test_query_grid_refuses_an_output_it_cannot_write(lib, bad):
+  import torch
+  from nerfies_amd import lib as L
+  rec = H.RecordingLib(lib, ['nrf_query_grid'])
+  model, fp = H.cpu_field_model(rec)
+  rgb = {'shape': torch.zeros(9, 3), 'dtype': torch.zeros(8, 3, dtype=torch.float64), 'stride': torch.zeros(3, 8).t()}[bad]
+  with pytest.raises(L.NrfError, match=r"query_grid: out\['rgb'\].*\(8, 3\)"):
+    model.query_grid(fp, (0, 0, 0), (1, 1, 1), (2, 2, 2), 0, 8, {'sigma': torch.zeros(8), 'rgb': rgb}, viewdirs=torch.zeros(3), use_warp=False)
+  assert rec.calls == []

@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import helpers as H
 import mesh_reference as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -183,61 +184,6 @@ def test_recorded_side_plan_sizes_still_hold(lib):
     assert mod.sizes(lib) == json.load(fp)['sizes']
 
 
-class _RecordingLib:
-  """The library with the grid, gradient and mesh entries replaced by recorders; the count recorder reports
-  `found` = (vertices, triangles) through the counts pointer (host memory here)."""
-
-  def __init__(self, real, found):
-    self._real = real
-    self.found = found
-    self.calls = []
-
-  def __getattr__(self, name):
-    return getattr(self._real, name)
-
-  @staticmethod
-  def _grid(g):
-    g = g._obj
-    return dict(dims=tuple(g.dims), origin=tuple(g.origin), step=tuple(g.step))
-
-  def nrf_query_grid(self, h, params, group, grid, first, count, level, scalars, flags, out, ws, nbytes, stream):
-    self.calls.append(dict(fn='grid', first=int(first), count=int(count), level=int(level), flags=int(flags), sigma=out._obj.sigma,
-                           rgb=out._obj.rgb, warp_ids=group._obj.warp_ids, appearance_ids=group._obj.appearance_ids, **self._grid(grid)))
-    return 0
-
-  def nrf_mesh_count(self, sigma, grid, thr, counts, ws, nbytes, stream):
-    self.calls.append(dict(fn='count', sigma=sigma, thr=thr, ws=ws, nbytes=int(nbytes), **self._grid(grid)))
-    out = C.cast(counts, C.POINTER(C.c_int32))
-    out[0], out[1] = self.found
-    return 0
-
-  def nrf_mesh_emit(self, sigma, grid, thr, mv, mt, vertices, cell, tris, ws, nbytes, stream):
-    self.calls.append(dict(fn='emit', sigma=sigma, thr=thr, mv=int(mv), mt=int(mt), vertices=vertices, cell=cell, tris=tris, ws=ws,
-                           nbytes=int(nbytes), **self._grid(grid)))
-    return 0
-
-  def nrf_mesh_snap(self, vertices, cell, sigma_at, grad_at, grid, thr, n, stream):
-    self.calls.append(dict(fn='snap', vertices=vertices, cell=cell, sigma_at=sigma_at, grad_at=grad_at, thr=thr, n=int(n), **self._grid(grid)))
-    return 0
-
-  def nrf_query_points_grad(self, h, params, groups, points, S, level, scalars, flags, out, ws, nbytes, stream):
-    o = out._obj
-    self.calls.append(dict(fn='grad', points=points.value, S=int(S), level=int(level), flags=int(flags), num_rays=groups._obj.num_rays,
-                           warp_ids=groups._obj.warp_ids, appearance_ids=groups._obj.appearance_ids, sigma=o.sigma, grad=o.grad_sigma,
-                           normals=o.normals))
-    return 0
-
-
-def _cpu_model(lib, found):
-  import types
-  from nerfies_amd import models
-  cfg = types.SimpleNamespace(use_warp=True, warp_field_type='se3', num_warp_freqs=4, num_nerf_point_freqs=6, sigma_activation='softplus',
-                              use_stratified_sampling=False, use_appearance_metadata=True, use_camera_metadata=True)
-  model, fp = models.construct_nerf(0, cfg, 0, [0, 1], [0, 1], [0, 1, 2], 0.1, 1.0, device='cpu')
-  rec = model._lib = _RecordingLib(lib, found)
-  return model, fp, rec
-
-
 def test_extract_mesh_calls(lib, monkeypatch):
   """density_grid's chunks, then count and emit on the same grid, workspace and threshold, then per refine step one gradient query
   at the vertices and one snap, a last gradient query for the normals and the colour query along the fixed view direction.  The
@@ -245,19 +191,14 @@ def test_extract_mesh_calls(lib, monkeypatch):
   import torch
   from nerfies_amd import evaluation, lib as L
   V, F = 37, 70
-  model, fp, rec = _cpu_model(lib, (V, F))
-  monkeypatch.setattr(type(model), 'query_gradient', lambda self, variables, points, metadata=None, warp_extra=None, level='fine',
-                      use_warp=True, metadata_encoded=False, outputs=('sigma', 'grad_sigma', 'normals'):
-                      self._query_gradient_chunks(variables, points, metadata, warp_extra, level, use_warp, metadata_encoded, outputs,
-                                                  torch.device('cpu')))
+  def peek(c):   # host memory here: what the colour query's group holds while the call runs
+    if c['fn'] == 'points':
+      c['view'] = list((C.c_float * 3).from_address(c['viewdirs']))
+      c['appearance'], c['camera'] = (C.c_int32.from_address(c[k]).value for k in ('appearance_ids', 'camera_ids'))
 
-  def query_points(self, variables, points, viewdirs=None, metadata=None, warp_extra=None, level='fine', use_warp=True,
-                   metadata_encoded=False, outputs=('sigma', 'rgb')):   # NerfModel.query_points refuses CPU points: recorded here
-    rec.calls.append(dict(fn='points', points=points.data_ptr(), S=points.shape[0], level=level, use_warp=use_warp, outputs=tuple(outputs),
-                          viewdirs=viewdirs.tolist(), metadata={k: v.tolist() for k, v in metadata.items()}))
-    return {'rgb': torch.zeros(points.shape[0], 3)}
-
-  monkeypatch.setattr(type(model), 'query_points', query_points)
+  rec = H.RecordingLib(lib, ['nrf_query_grid', 'nrf_query_points', 'nrf_query_points_grad', *ENTRIES[1:]], found=(V, F), peek=peek)
+  model, fp = H.cpu_field_model(rec, use_appearance_metadata=True, use_camera_metadata=True)
+  H.lift_device_rule(monkeypatch)
   res, lo, hi = (5, 3, 7), (-1.0, 0.0, 1.0), (1.0, 3.0, 2.0)
   mesh = evaluation.extract_mesh(model, fp, lo, hi, res, 0.75, level='coarse', warp_id=2, appearance_id=1, camera_id=1, refine_steps=2,
                                  colors=False, chunk=32)
@@ -297,8 +238,9 @@ def test_extract_mesh_calls(lib, monkeypatch):
   pts = [c for c in rec.calls if c['fn'] == 'points']
   assert [(c['points'] - mesh['vertices'].data_ptr(), c['S']) for c in pts] == [(0, 20), (240, 17)]
   for c in pts:
-    assert c['viewdirs'] == [list(evaluation.MESH_VIEW_DIRECTION)] and c['metadata'] == {'appearance': [[1]], 'camera': [[0]]}
-    assert c['outputs'] == ('rgb',) and c['level'] == 'fine' and c['use_warp'] is False
+    assert c['view'] == list(evaluation.MESH_VIEW_DIRECTION) and (c['warp_ids'], c['appearance'], c['camera']) == (None, 1, 0)
+    assert c['rgb'] and c['sigma'] is None and c['warped'] is None and c['level'] == 1 and c['flags'] == L.NRF_FLAG_NO_WARP
+    assert c['num_rays'] == 1
   assert tuple(mesh['rgb'].shape) == (V, 3) and set(mesh) == {'vertices', 'faces', 'normals', 'sigma', 'rgb'}
 
   # an empty mesh: nothing is queried behind the emit
@@ -313,7 +255,7 @@ def test_extract_mesh_calls(lib, monkeypatch):
 def test_extract_mesh_from_grid_takes_any_memory_order(lib):
   import torch
   from nerfies_amd import evaluation
-  rec = _RecordingLib(lib, (0, 0))
+  rec = H.RecordingLib(lib, ENTRIES[1:])
   native = torch.zeros(7, 3, 5).permute(2, 1, 0)                  # (5, 3, 7), x fastest in memory: what density_grid returns
   evaluation.extract_mesh_from_grid(native, (0, 0, 0), (1, 1, 1), 0.5, lib=rec)
   assert rec.calls[0]['sigma'] == native.data_ptr() and rec.calls[0]['dims'] == (5, 3, 7)

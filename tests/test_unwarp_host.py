@@ -13,6 +13,8 @@ import sys
 
 import pytest
 
+import helpers as H
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'nerfies_amd.h')
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
@@ -209,48 +211,20 @@ def test_other_plans_stay_behind_an_unwarp_plan(lib, handles):
     assert mod.sizes(lib) == json.load(fp)['sizes']
 
 
-class _RecordingLib:
-  """The library with nrf_unwarp_points replaced by a recorder: every other entry (handle, layout, workspace size) is the real one."""
-
-  def __init__(self, real):
-    self._real = real
-    self.calls = []
-
-  def __getattr__(self, name):
-    return getattr(self._real, name)
-
-  def nrf_unwarp_points(self, h, params, targets, ids, codes, num_codes, guess, n, scalars, steps, tolerance, max_step, out, ws, nbytes, stream):
-    o = out._obj
-    val = lambda p: None if p is None else p.value
-    self.calls.append(dict(targets=val(targets), ids=val(ids), codes=val(codes), num_codes=int(num_codes), guess=val(guess), n=int(n),
-                           steps=int(steps), tolerance=float(tolerance), max_step=float(max_step), points=o.points, residual=o.residual,
-                           status=o.status, ws=val(ws), nbytes=int(nbytes), alpha=scalars._obj.warp_alpha))
-    return 0
-
-
-def _cpu_model(lib):
-  import types
-  from nerfies_amd import models
-  cfg = types.SimpleNamespace(use_warp=True, warp_field_type='se3', num_warp_freqs=4, num_nerf_point_freqs=6, sigma_activation='softplus',
-                              use_stratified_sampling=False)
-  model, fp = models.construct_nerf(0, cfg, 0, [0], [0], [0, 1, 2], 0.1, 1.0, device='cpu')
-  rec = model._lib = _RecordingLib(lib)
-  return model, fp, rec
-
-
 def test_unwarp_chunks_cover_the_points_once(lib, monkeypatch):
   """NerfModel.unwarp_points behind its device rule (CPU points raise before anything else): the recorder never follows a pointer, so
   the chunking runs on CPU tensors."""
   import torch
   from nerfies_amd import lib as L
-  model, fp, rec = _cpu_model(lib)
+  rec = H.RecordingLib(lib, ['nrf_unwarp_points'])
+  model, fp = H.cpu_field_model(rec)
   with pytest.raises(L.NrfError, match='GPU'):
     model.unwarp_points(fp, torch.zeros(4, 3), torch.zeros(4, dtype=torch.int32), {'alpha': 1.0})
   assert rec.calls == []
   monkeypatch.setattr(L, 'NRF_UNWARP_MAX_POINTS', 100)        # the Python side's chunk size; the library's own cap is tested above
-  cpu = torch.device('cpu')
-  run = lambda pts, ids, guess=None, codes=None, outputs=('points', 'residual', 'status'), **kw: model._unwarp_chunks(
-      fp, pts, ids, {'alpha': 2.5}, guess, kw.get('steps', 8), kw.get('tolerance', 0.0), kw.get('max_step', math.inf), codes, outputs, cpu)
+  H.lift_device_rule(monkeypatch)
+  run = lambda pts, ids, guess=None, codes=None, outputs=('points', 'residual', 'status'), **kw: model.unwarp_points(
+      fp, pts, ids, {'alpha': 2.5}, guess=guess, warp_codes=codes, outputs=outputs, **kw)
   n = 250                                                      # 100 + 100 + 50
   pts, ids, guess = torch.zeros(n, 3), torch.arange(n, dtype=torch.int32) % 3, torch.ones(n, 3)
   out = run(pts, ids, guess, steps=5, tolerance=1e-6, max_step=0.5)
@@ -271,6 +245,8 @@ def test_unwarp_chunks_cover_the_points_once(lib, monkeypatch):
   for key, per in (('targets', 12), ('ids', 4), ('guess', 12)):
     assert [c[key] - rec.calls[0][key] for c in rec.calls] == [0, 100 * per, 200 * per], key
   assert len({(c['ws'], c['nbytes']) for c in rec.calls}) == 1   # one cached workspace, sized for the largest chunk
+  nb = C.c_size_t(0)                                             # ... by the library itself: 100 points
+  assert lib.nrf_unwarp_workspace_bytes(model.handle, 100, C.byref(nb)) == 0 and rec.calls[0]['nbytes'] == H.ws_bytes(nb.value)
   # leading dimensions are kept; no guess, a code table, a selection of the outputs
   rec.calls.clear()
   codes = torch.zeros(7, model.num_warp_features)
