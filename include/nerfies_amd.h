@@ -677,6 +677,69 @@ int nrf_mesh_emit(const float* sigma, const nrf_grid* grid, float threshold, int
 int nrf_mesh_snap(float* vertices, const int32_t* vertex_cell, const float* sigma_at, const float* grad_at, const nrf_grid* grid,
                   float threshold, int32_t num_vertices, void* stream);
 
+/* ---- Mesh clean-up: connected components of an indexed triangle mesh, their table, and the compaction to a submesh ----
+ * Handle-free and for any mesh, whatever made it and in whatever vertex and triangle order: triangles (F,3) int32, vertices (V,3)
+ * float32, DEVICE arrays.  Every output position is a rank, the same bits on every run.  Announced by NRF_HAS_MESH_COMPONENTS
+ * (NRF_VERSION is unchanged).
+ *
+ * Components.  The graph has the vertices 0 .. V-1.  A triangle is VALID iff its three indices are all in [0, V).  A valid triangle
+ *   (a, b, c) joins a-b and b-c; a repeated index is allowed.  An invalid triangle joins nothing and belongs to no component
+ *   (triangle indices cannot be validated without a synchronisation and are not: the camera tables' rule for an index outside the
+ *   table).  A vertex no valid triangle names is a component of its own.  Component ids are dense, 0 .. C-1, in increasing order of
+ *   each component's smallest vertex index.
+ * Table.  Per component: its vertices, its valid triangles (a triangle counts for the component of its FIRST index), and the box of
+ *   its vertices.  The counts are integer adds; the box is integer min / max on the monotone key of a float32 with the bits u,
+ *     key(u) = (u & 0x80000000) ? ~u : (u | 0x80000000)   compared as uint32,
+ *   whose order is the floats' order with -0 below +0.  A NaN coordinate is skipped; a component whose coordinates are all NaN gets
+ *   (+inf, -inf).  No float is ever summed atomically, so the table too has the same bits on every run.
+ * Submesh.  keep (V,) uint8, nonzero = kept.  vertex_map[v] is v's rank among the kept vertices, or -1.  A triangle is kept iff it is
+ *   valid and all three of its vertices are kept; kept triangles keep their relative order and are written with mapped indices.
+ *   General: the mask may select components, the rows whose animate status is 1, a box, a density cut.
+ *
+ * Every refusal is decided before any HIP call and names the entry and the rule in nrf_last_error: a NULL pointer where one is
+ * required (NRF_E_NULL), a negative count or capacity, a row width below 1 (NRF_E_SHAPE), a workspace that is short or not 16-byte
+ * aligned (NRF_E_WORKSPACE).  A buffer may be NULL where its count or capacity is 0.  Capacities are held against the scanned totals
+ * ON THE DEVICE: when one is short nothing at all is written and the status words say 0; no write ever lands at or past a capacity.
+ * Zero vertices and / or zero triangles is no error (C = 0, or C = V).  Asynchronous on `stream`, nothing allocated or synchronised. */
+#define NRF_HAS_MESH_COMPONENTS 1
+
+/* The first 16 bytes of a components workspace (DEVICE memory; the caller may copy them). */
+typedef struct nrf_mesh_components_status {
+  int32_t num_components;     /* what nrf_mesh_components found (also in its `counts`) */
+  int32_t table_components;   /* what the last nrf_mesh_component_table wrote: C rows, or 0 when max_components was short */
+  int32_t error;              /* 0, or nonzero when a labelling loop ran into its hard cap (V steps; cannot happen for parent[v] <= v) */
+  int32_t reserved;
+} nrf_mesh_components_status;
+/* The first 16 bytes of a submesh workspace are an nrf_mesh_status: the kept totals, and what the last nrf_mesh_submesh_emit wrote
+ * (the totals, or 0 and 0 when a capacity was short).  The submesh kernels have no loop to cap. */
+
+/* Bytes of workspace (about 4 bytes per vertex and a total per 1024 vertices).  Needs no GPU. */
+int nrf_mesh_components_workspace_bytes(int32_t num_vertices, int32_t num_triangles, size_t* bytes);
+
+/* vertex_component (V,) int32; counts: DEVICE int32[1] = C.  The workspace then serves nrf_mesh_component_table. */
+int nrf_mesh_components(const int32_t* triangles, int32_t num_triangles, int32_t num_vertices, int32_t* vertex_component,
+                        int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* comp_counts (C,2) int32 = [vertices, valid triangles] (a triangle counts for the component of its first index);
+ * comp_bbox (C,6) float32 = min x y z, max x y z over the component's vertices, or NULL together with `vertices`.
+ * max_components is held against C on the device.  A vertex_component entry outside [0, C) is counted nowhere. */
+int nrf_mesh_component_table(const int32_t* triangles, int32_t num_triangles, const float* vertices, int32_t num_vertices,
+                             const int32_t* vertex_component, int32_t max_components, int32_t* comp_counts, float* comp_bbox,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* Bytes of workspace (a total per 1024 vertices and per 1024 triangles).  Needs no GPU. */
+int nrf_mesh_submesh_workspace_bytes(int32_t num_vertices, int32_t num_triangles, size_t* bytes);
+/* counts: DEVICE int32[2] = kept vertices, kept triangles.  The workspace then serves nrf_mesh_submesh_emit for the same mesh and keep. */
+int nrf_mesh_submesh_count(const uint8_t* keep, int32_t num_vertices, const int32_t* triangles, int32_t num_triangles, int32_t* counts,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* vertex_map (V,) int32 and triangles_out (kept triangles, 3) int32; both capacities are held against the kept totals. */
+int nrf_mesh_submesh_emit(const uint8_t* keep, int32_t num_vertices, const int32_t* triangles, int32_t num_triangles,
+                          int32_t max_vertices, int32_t max_triangles, int32_t* vertex_map, int32_t* triangles_out, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* dst[vertex_map[v]] = src[v] for every v with 0 <= vertex_map[v] < max_rows: rows of `width` 4-byte words, copied byte for byte. */
+int nrf_mesh_gather_rows(const void* src, int32_t width, const int32_t* vertex_map, int32_t num_vertices, void* dst, int32_t max_rows,
+                         void* stream);
+
 /* flax.optim.Adam.apply_gradient (training.py:268-269; flax 0.3.4 optim/adam.py):
  * g = grad*grad_scale (grad_scale = 1/world_size folds lax.pmean, training.py:266),
  * m,v updated in place, step = number of updates already applied.  Hyper-parameters are doubles

@@ -9,6 +9,7 @@
 // per-workgroup totals, a one-workgroup kernel scans them, the emit kernels read the scan.
 //
 // Every float operation below is a single rounding in the order the header states: contraction is off for the whole file.
+#include "mesh_scan.h"
 #include "nrf_handle.h"
 
 #include <cmath>
@@ -25,7 +26,6 @@ constexpr int MESH_WAVES = MESH_THREADS / 64;
 constexpr int MESH_ROUNDS = 4;
 constexpr int MESH_BLOCK_CELLS = MESH_THREADS * MESH_ROUNDS;
 constexpr int MESH_SLOTS = MESH_ROUNDS * MESH_WAVES;   // (round, wave) pairs of a workgroup, in cell order
-constexpr int SCAN_THREADS = 1024;
 constexpr size_t MESH_HEADER_BYTES = 256;              // nrf_mesh_status, padded
 constexpr size_t MESH_ALIGN = 256;
 
@@ -124,38 +124,14 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_classify_kernel(const float
   }
 }
 
-// Stage 2: exclusive scans of the workgroup totals, in place, by ONE workgroup (each thread a contiguous run); the totals go to the
-// workspace's status words and to the caller's counts.
+// Stage 2: exclusive scans of the workgroup totals, in place, by ONE workgroup (mesh_scan.h); the totals go to the workspace's status
+// words and to the caller's counts.
 __global__ __launch_bounds__(SCAN_THREADS) void mesh_scan_kernel(int* __restrict__ block_v, int* __restrict__ block_q, const int nblocks,
                                                                  int* __restrict__ status, int* __restrict__ counts) {
-  __shared__ int tv[SCAN_THREADS], tq[SCAN_THREADS];
-  const int t = threadIdx.x;
-  const int per = (nblocks + SCAN_THREADS - 1) / SCAN_THREADS;
-  const long long first = (long long)t * per;
-  const int b0 = first < nblocks ? (int)first : nblocks;
-  const int b1 = b0 + per < nblocks ? b0 + per : nblocks;
-  int mv = 0, mq = 0;
-  for (int b = b0; b < b1; ++b) { mv += block_v[b]; mq += block_q[b]; }
-  tv[t] = mv;
-  tq[t] = mq;
-  __syncthreads();
-  for (int off = 1; off < SCAN_THREADS; off <<= 1) {
-    const int av = t >= off ? tv[t - off] : 0, aq = t >= off ? tq[t - off] : 0;
-    __syncthreads();
-    tv[t] += av;
-    tq[t] += aq;
-    __syncthreads();
-  }
-  int rv = tv[t] - mv, rq = tq[t] - mq;
-  for (int b = b0; b < b1; ++b) {
-    const int v = block_v[b], q = block_q[b];
-    block_v[b] = rv;
-    block_q[b] = rq;
-    rv += v;
-    rq += q;
-  }
-  if (t == SCAN_THREADS - 1) {
-    const int nv = tv[t], nt = 2 * tq[t];
+  int nv, nq;
+  mesh_scan_totals(block_v, nblocks, block_q, nblocks, nv, nq);
+  if (threadIdx.x == SCAN_THREADS - 1) {
+    const int nt = 2 * nq;
     status[0] = nv;
     status[1] = nt;
     status[2] = 0;

@@ -334,8 +334,154 @@ def extract_mesh_from_grid(sigma, origin, step, threshold, lib=None):
   return {'vertices': vertices, 'vertex_cell': vertex_cell, 'faces': faces}
 
 
+def _mesh_workspace(lib, sizer, num_vertices, num_triangles, device):
+  nbytes = C.c_size_t(0)
+  L.check(sizer(num_vertices, num_triangles, C.byref(nbytes)), lib)
+  return torch.empty((nbytes.value + 3) // 4, dtype=torch.int32, device=device)
+
+
+def _faces_arg(faces):
+  faces = torch.as_tensor(faces)
+  if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+    raise ValueError(f'faces must be an (F, 3) int32 tensor, got {faces.dtype} {tuple(faces.shape)}')
+  return faces.contiguous()
+
+
+def mesh_components(vertices, faces, lib=None, num_vertices=None):
+  """Connected components of an indexed triangle mesh on the device (nrf_mesh_components, then nrf_mesh_component_table; the
+  definitions are in include/nerfies_amd.h): `faces` (F, 3) int32 of any mesh in any order, `vertices` (V, 3) float32, or None to
+  skip the boxes (then V is `num_vertices`, or by default one more than the largest index of `faces`).  A triangle with an index
+  outside [0, V) joins nothing; a vertex no triangle names is a component of its own; ids are dense in increasing order of each
+  component's smallest vertex.  Returns device tensors {'labels' (V,) int32, 'num_vertices' (C,) int32, 'num_triangles' (C,) int32
+  (a triangle counts for its first index's component), and with vertices 'bbox_min' (C, 3), 'bbox_max' (C, 3) float32}, the same
+  bits on every run.  C is read back once, to size the table."""
+  lib = lib or L.load_library()
+  faces = _faces_arg(faces)
+  device = faces.device
+  if vertices is not None:
+    vertices = torch.as_tensor(vertices)
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+      raise ValueError(f'vertices must be a (V, 3) float32 tensor, got {vertices.dtype} {tuple(vertices.shape)}')
+    vertices = vertices.contiguous()
+    if num_vertices is not None and int(num_vertices) != vertices.shape[0]:
+      raise ValueError(f'num_vertices = {num_vertices} but vertices has {vertices.shape[0]} rows')
+    V = vertices.shape[0]
+  elif num_vertices is not None:
+    V = int(num_vertices)
+  else:
+    V = int(faces.max()) + 1 if faces.numel() else 0
+  F = faces.shape[0]
+  stream = _stream_arg(device)
+  ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+  ws = _mesh_workspace(lib, lib.nrf_mesh_components_workspace_bytes, V, F, device)
+  labels = torch.empty(V, dtype=torch.int32, device=device)
+  count = torch.zeros(1, dtype=torch.int32, device=device)
+  L.check(lib.nrf_mesh_components(ptr(faces), F, V, ptr(labels), count.data_ptr(), ws.data_ptr(), ws.numel() * 4, stream), lib)
+  nc = int(count.item())
+  comp_counts = torch.empty(nc, 2, dtype=torch.int32, device=device)
+  bbox = torch.empty(nc, 6, dtype=torch.float32, device=device) if vertices is not None else None
+  L.check(lib.nrf_mesh_component_table(ptr(faces), F, vertices.data_ptr() if vertices is not None else None, V, ptr(labels), nc,
+                                       ptr(comp_counts), bbox.data_ptr() if bbox is not None else None, ws.data_ptr(), ws.numel() * 4,
+                                       stream), lib)
+  out = {'labels': labels, 'num_vertices': comp_counts[:, 0].contiguous(), 'num_triangles': comp_counts[:, 1].contiguous()}
+  if bbox is not None:
+    out.update(bbox_min=bbox[:, :3].contiguous(), bbox_max=bbox[:, 3:].contiguous())
+  return out
+
+
+def _gather_rows(lib, src, vertex_map, kept, stream):
+  """src (V, ...) -> (kept, ...): the rows whose vertex_map is not -1, in order (nrf_mesh_gather_rows)."""
+  src = src.contiguous()
+  V = src.shape[0]
+  row_bytes = (src.numel() // V) * src.element_size() if V else 0
+  dst = torch.empty((kept,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+  if V == 0 or kept == 0 or row_bytes == 0:
+    return dst
+  if row_bytes % 4:
+    raise ValueError(f'submesh gathers rows of 4-byte words; a row of {src.dtype} {tuple(src.shape[1:])} has {row_bytes} bytes')
+  L.check(lib.nrf_mesh_gather_rows(src.data_ptr(), row_bytes // 4, vertex_map.data_ptr(), V, dst.data_ptr(), kept, stream), lib)
+  return dst
+
+
+def submesh(mesh, keep_vertices, lib=None):
+  """The mesh restricted to the vertices a mask keeps (nrf_mesh_submesh_count / _emit, nrf_mesh_gather_rows): `mesh` is a dict as
+  extract_mesh / extract_mesh_from_grid return it, or any dict with 'faces' (F, 3) int32; `keep_vertices` a (V,) bool or uint8
+  device tensor.  A triangle is kept iff all three of its vertices are (and its indices are in [0, V)); kept vertices and triangles
+  keep their order.  Every tensor of the dict whose first dimension is V is gathered -- 'vertices', 'vertex_cell', 'normals',
+  'sigma', 'rgb', anything the caller added -- and a (K, V, ...) tensor (an animate_mesh result) along its second; 'faces' is
+  re-indexed; everything else is passed on as it is.  Adds 'vertex_map' (V,) int32: each old vertex's new index, or -1.  The mask
+  may come from anywhere: components (clean_mesh), animate_mesh's status == 1, a box, a density cut."""
+  lib = lib or L.load_library()
+  faces = _faces_arg(mesh['faces'])
+  device = faces.device
+  keep = torch.as_tensor(keep_vertices)
+  if keep.dim() != 1 or keep.dtype not in (torch.bool, torch.uint8):
+    raise ValueError(f'keep_vertices must be a (V,) bool or uint8 tensor, got {keep.dtype} {tuple(keep.shape)}')
+  keep = keep.to(device=device, dtype=torch.uint8).contiguous()
+  V, F = keep.shape[0], faces.shape[0]
+  stream = _stream_arg(device)
+  ptr = lambda t: t.data_ptr() if t.numel() else None
+  ws = _mesh_workspace(lib, lib.nrf_mesh_submesh_workspace_bytes, V, F, device)
+  counts = torch.zeros(2, dtype=torch.int32, device=device)
+  L.check(lib.nrf_mesh_submesh_count(ptr(keep), V, ptr(faces), F, counts.data_ptr(), ws.data_ptr(), ws.numel() * 4, stream), lib)
+  nv, nt = (int(v) for v in counts.tolist())
+  vertex_map = torch.empty(V, dtype=torch.int32, device=device)
+  faces_out = torch.empty(nt, 3, dtype=torch.int32, device=device)
+  L.check(lib.nrf_mesh_submesh_emit(ptr(keep), V, ptr(faces), F, nv, nt, ptr(vertex_map), ptr(faces_out), ws.data_ptr(), ws.numel() * 4,
+                                    stream), lib)
+  out = {}
+  for key, value in mesh.items():
+    if key == 'faces':
+      out[key] = faces_out
+    elif not torch.is_tensor(value) or value.dim() == 0 or key == 'vertex_map':
+      out[key] = value
+    elif value.shape[0] == V:
+      out[key] = _gather_rows(lib, value, vertex_map, nv, stream)
+    elif value.dim() >= 2 and value.shape[1] == V:
+      out[key] = torch.stack([_gather_rows(lib, value[k], vertex_map, nv, stream) for k in range(value.shape[0])], 0) if value.shape[0] \
+          else value.new_empty((0, nv) + tuple(value.shape[2:]))
+    else:
+      out[key] = value
+  out['vertex_map'] = vertex_map
+  return out
+
+
+def select_components(num_triangles, keep='largest', min_triangles=1):
+  """The component ids clean_mesh keeps, from the (C,) triangle counts as a list: those with at least `min_triangles` triangles, and of
+  them all (`keep='all'`), the one (`'largest'`) or the `keep` = K >= 1 with the most triangles, ties going to the smaller id."""
+  if keep == 'largest':
+    keep = 1
+  if keep != 'all' and (isinstance(keep, bool) or not isinstance(keep, int) or keep < 1):
+    raise ValueError(f"keep must be 'all', 'largest' or an int >= 1, got {keep!r}")
+  ids = [c for c, n in enumerate(num_triangles) if n >= int(min_triangles)]
+  if keep != 'all':
+    ids = sorted(sorted(ids, key=lambda c: (-num_triangles[c], c))[:keep])
+  return ids
+
+
+def clean_mesh(mesh, keep='largest', min_triangles=1, lib=None):
+  """Drops the floaters of a mesh dict (mesh_components, then submesh): components with fewer than `min_triangles` triangles go first
+  (the default drops the vertices no triangle names), then `keep` = 'all', 'largest' or an int K >= 1 keeps the K components with the
+  most triangles, ties going to the smaller component id.  The selection runs on the (C,) table, read back once.  Returns submesh's
+  dict, with 'components': the table of the mesh as it came in (mesh_components' dict, labels included) and its 'kept' ids."""
+  lib = lib or L.load_library()
+  vertices = mesh.get('vertices')
+  faces = _faces_arg(mesh['faces'])
+  if torch.is_tensor(vertices) and vertices.dim() == 2 and vertices.dtype == torch.float32:
+    comps = mesh_components(vertices, faces, lib=lib)
+  else:   # e.g. an animate_mesh result: no single set of positions to box
+    comps = mesh_components(None, faces, lib=lib, num_vertices=vertices.shape[1] if torch.is_tensor(vertices) else None)
+  ids = select_components(comps['num_triangles'].tolist(), keep, min_triangles)
+  keep_component = torch.zeros(comps['num_triangles'].shape[0], dtype=torch.bool, device=faces.device)
+  if ids:
+    keep_component[torch.tensor(ids, dtype=torch.int64, device=faces.device)] = True
+  out = submesh(mesh, keep_component[comps['labels'].long()], lib=lib)
+  out['components'] = dict(comps, kept=ids)
+  return out
+
+
 def extract_mesh(model, params, bbox_min, bbox_max, resolution, threshold, level='fine', warp_id=None, appearance_id=None, camera_id=None,
-                 warp_extra=None, refine_steps=2, colors=True, chunk=1 << 21):
+                 warp_extra=None, refine_steps=2, colors=True, chunk=1 << 21, clean=None):
   """A triangle mesh of the field's level set sigma = threshold over the box [bbox_min, bbox_max], all on the device: `density_grid`
   (same arguments; its voxel centres are the mesh's samples, so `resolution` R gives R - 1 cells per axis), surface nets
   (`extract_mesh_from_grid`), then `refine_steps` rounds of the field's own density and gradient at the vertices
@@ -343,17 +489,25 @@ def extract_mesh(model, params, bbox_min, bbox_max, resolution, threshold, level
   faces do not change).  `warp_id=None` meshes the canonical (template) volume, an id that frame's observation volume.
   `appearance_id` / `camera_id`: the codes the colour is queried with (and, for a use_alpha_condition model, the density).
   Returns device tensors {'vertices' (V, 3), 'faces' (F, 3) int32, 'normals' (V, 3) = -grad sigma / |grad sigma| at the final
-  vertices, 'sigma' (V,) there, and with `colors` 'rgb' (V, 3) along MESH_VIEW_DIRECTION}."""
+  vertices, 'sigma' (V,) there, and with `colors` 'rgb' (V, 3) along MESH_VIEW_DIRECTION}.
+  `clean`: None, or the keyword set of `clean_mesh` as a dict (keep=, min_triangles=), applied right after surface nets and before the
+  refinement, the normals and the colours, so a dropped vertex costs no query; the dict then also has clean_mesh's 'vertex_map' (over
+  the uncleaned vertices) and 'components'.  Every kept row has the bits it has without `clean`: a query's row does not depend on the
+  launch it ran in."""
   res, origin, step = _box_grid(bbox_min, bbox_max, resolution)
   alpha_app = appearance_id if getattr(model, 'use_alpha_condition', False) else None
   sigma = density_grid(model, params, bbox_min, bbox_max, res, level=level, warp_id=warp_id, appearance_id=alpha_app,
                        warp_extra=warp_extra, chunk=chunk)
   lib = model.lib
   mesh = extract_mesh_from_grid(sigma, origin, step, threshold, lib=lib)
+  if clean is not None:
+    mesh = clean_mesh(mesh, lib=lib, **clean)
   vertices, vertex_cell = mesh['vertices'], mesh['vertex_cell']
   device = vertices.device
   nv = vertices.shape[0]
   out = {'vertices': vertices, 'faces': mesh['faces']}
+  if clean is not None:
+    out.update(vertex_map=mesh['vertex_map'], components=mesh['components'])
   if nv == 0:
     out.update(normals=torch.zeros(0, 3, device=device), sigma=torch.zeros(0, device=device))
     if colors:

@@ -160,6 +160,11 @@ class MeshStatus(C.Structure):
   _fields_ = [('num_vertices', C.c_int32), ('num_triangles', C.c_int32), ('emitted_vertices', C.c_int32), ('emitted_triangles', C.c_int32)]
 
 
+class MeshComponentsStatus(C.Structure):
+  """nrf_mesh_components_status: the first 16 bytes of a components workspace (device memory)."""
+  _fields_ = [('num_components', C.c_int32), ('table_components', C.c_int32), ('error', C.c_int32), ('reserved', C.c_int32)]
+
+
 NRF_QUERY_MAX_POINTS = 1 << 24   # points of one nrf_query_points / nrf_query_grid call
 NRF_QUERY_GRAD_MAX_POINTS = 1 << 20   # points of one nrf_query_points_grad / nrf_query_grid_grad call
 NRF_GRID_MAX_POINTS = 1 << 40    # points of a whole nrf_grid
@@ -187,6 +192,8 @@ EXPORTS = [
     'nrf_query_grad_workspace_bytes', 'nrf_query_points_grad', 'nrf_query_grid_grad',
     'nrf_unwarp_workspace_bytes', 'nrf_unwarp_points',
     'nrf_mesh_workspace_bytes', 'nrf_mesh_count', 'nrf_mesh_emit', 'nrf_mesh_snap',
+    'nrf_mesh_components_workspace_bytes', 'nrf_mesh_components', 'nrf_mesh_component_table',
+    'nrf_mesh_submesh_workspace_bytes', 'nrf_mesh_submesh_count', 'nrf_mesh_submesh_emit', 'nrf_mesh_gather_rows',
 ]
 
 _lib = None
@@ -260,6 +267,13 @@ def load_library(path=None):
       'nrf_mesh_count': [vp, C.POINTER(Grid), f32, vp, vp, C.c_size_t, vp],
       'nrf_mesh_emit': [vp, C.POINTER(Grid), f32, i32, i32, vp, vp, vp, vp, C.c_size_t, vp],
       'nrf_mesh_snap': [vp, vp, vp, vp, C.POINTER(Grid), f32, i32, vp],
+      'nrf_mesh_components_workspace_bytes': [i32, i32, C.POINTER(C.c_size_t)],
+      'nrf_mesh_components': [vp, i32, i32, vp, vp, vp, C.c_size_t, vp],
+      'nrf_mesh_component_table': [vp, i32, vp, i32, vp, i32, vp, vp, vp, C.c_size_t, vp],
+      'nrf_mesh_submesh_workspace_bytes': [i32, i32, C.POINTER(C.c_size_t)],
+      'nrf_mesh_submesh_count': [vp, i32, vp, i32, vp, vp, C.c_size_t, vp],
+      'nrf_mesh_submesh_emit': [vp, i32, vp, i32, i32, i32, vp, vp, vp, C.c_size_t, vp],
+      'nrf_mesh_gather_rows': [vp, i32, vp, i32, vp, i32, vp],
       'nrf_camera_pixels_to_rays': [C.POINTER(CameraDesc), vp, i64, vp, vp, vp, vp],
       'nrf_camera_pixels_to_points': [C.POINTER(CameraDesc), vp, vp, i64, vp, vp],
       'nrf_camera_project': [C.POINTER(CameraDesc), vp, i64, vp, vp],

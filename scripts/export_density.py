@@ -18,6 +18,9 @@ With --mesh (evaluation.extract_mesh -> nrf_mesh_count / nrf_mesh_emit / nrf_mes
 pulled onto the level set sigma = --threshold by --mesh_refine Newton steps along the field's own gradient):
   mesh_<name>.ply      binary little-endian triangle mesh: vertices x y z nx ny nz red green blue, faces as vertex_indices lists.
 The .npy grid and the point cloud stay what they were; the mesh is the iso-surface they stopped short of.
+With --mesh_keep largest | K and / or --mesh_min_triangles M (evaluation.clean_mesh -> nrf_mesh_components / nrf_mesh_submesh_*: connected
+components on the device) the floaters are dropped right after surface nets, before any vertex is refined or coloured; the component
+table's head is printed either way, and --animate carries the cleaned template.
 With --mesh --canonical --animate ITEM_ID [ITEM_ID ...] (evaluation.animate_mesh -> nrf_unwarp_points: the warp field inverted at the
 template's vertices, Newton's iteration on the device, each frame started from the one before):
   mesh_canonical_at_<item_id>.ply   the template carried into that frame: the same vertex_indices and colours, the vertices x with
@@ -52,6 +55,9 @@ def parse_flags(argv=None):
   p.add_argument('--normals', action='store_true', help='also export the surface normals -grad sigma / |grad sigma| (npy, and nx ny nz in the PLY)')
   p.add_argument('--mesh', action='store_true', help='also extract the triangle mesh of the level set sigma = --threshold (mesh_<name>.ply)')
   p.add_argument('--mesh_refine', type=int, default=2, metavar='K', help='Newton steps of the mesh vertices onto the level set')
+  p.add_argument('--mesh_keep', default='all', metavar='{all,largest,K}',
+                 help='with --mesh: the connected components to keep: all, the largest, or the K with the most triangles')
+  p.add_argument('--mesh_min_triangles', type=int, default=0, metavar='M', help='with --mesh: drop components with fewer triangles first')
   p.add_argument('--animate', nargs='+', default=None, metavar='ITEM_ID',
                  help='with --mesh --canonical: carry the template mesh into these frames (mesh_canonical_at_<item_id>.ply each)')
   p.add_argument('--animate_steps', type=int, default=8, metavar='K', help='Newton rounds per frame of --animate')
@@ -59,6 +65,12 @@ def parse_flags(argv=None):
   own, rest = p.parse_known_args(argv)
   if len(own.resolution) not in (1, 3):
     p.error('--resolution takes one number or three')
+  if own.mesh_keep not in ('all', 'largest'):
+    if not own.mesh_keep.isdigit() or int(own.mesh_keep) < 1:
+      p.error("--mesh_keep takes 'all', 'largest' or a number K >= 1")
+    own.mesh_keep = int(own.mesh_keep)
+  if own.mesh_min_triangles < 0:
+    p.error('--mesh_min_triangles must not be negative')
   if own.animate is not None and not (own.mesh and own.canonical):
     p.error('--animate carries the canonical mesh into frames: it needs --mesh --canonical')
   flags = train_driver.parse_flags(rest)
@@ -101,6 +113,21 @@ def write_mesh_ply(path, vertices, normals, rgb, faces):
     f.write(head.encode('ascii'))
     f.write(vert.tobytes())
     f.write(face.tobytes())
+
+
+def print_component_table(name, comps, head=8):
+  """The first `head` rows of evaluation.mesh_components' table, largest first; returns the number of components."""
+  nv, nt = comps['num_vertices'].tolist(), comps['num_triangles'].tolist()
+  lo, hi = comps['bbox_min'].cpu().numpy().astype(np.float64), comps['bbox_max'].cpu().numpy().astype(np.float64)
+  kept = comps.get('kept')
+  order = sorted(range(len(nt)), key=lambda c: (-nt[c], c))
+  print(f'mesh_{name}: {len(nt)} connected components' + ('' if kept is None else f', {len(kept)} kept'), flush=True)
+  for c in order[:head]:
+    mark = '' if kept is None else (' kept' if c in kept else ' dropped')
+    print(f'  component {c}: {nv[c]} vertices, {nt[c]} triangles, box {lo[c].round(4).tolist()} .. {hi[c].round(4).tolist()}{mark}', flush=True)
+  if len(order) > head:
+    print(f'  ... and {len(order) - head} smaller', flush=True)
+  return len(nt)
 
 
 def animate(flags, model, target, warp_extra, datasource, mesh, alpha_app, exp_dir):
@@ -209,8 +236,13 @@ def main(argv=None):
   if normals_npy is not None:
     ret['normals_npy'] = normals_npy
   if flags.mesh:
+    clean = None   # --mesh_keep all without a triangle floor: the mesh as it always was
+    if flags.mesh_keep != 'all' or flags.mesh_min_triangles > 0:
+      clean = dict(keep=flags.mesh_keep, min_triangles=flags.mesh_min_triangles)
     mesh = evaluation.extract_mesh(model, target, lo, hi, res, flags.threshold, level=flags.level, warp_id=warp_id, appearance_id=app_id,
-                                   camera_id=cam_id, warp_extra=state.warp_extra, refine_steps=flags.mesh_refine)
+                                   camera_id=cam_id, warp_extra=state.warp_extra, refine_steps=flags.mesh_refine, clean=clean)
+    comps = mesh['components'] if clean is not None else evaluation.mesh_components(mesh['vertices'], mesh['faces'], lib=model.lib)
+    ret['num_mesh_components'] = print_component_table(name, comps)
     mesh_ply = os.path.join(exp_dir, f'mesh_{name}.ply')
     write_mesh_ply(mesh_ply, *(mesh[k].cpu().numpy() for k in ('vertices', 'normals', 'rgb', 'faces')))
     print(f'mesh_{name}: {mesh["vertices"].shape[0]} vertices, {mesh["faces"].shape[0]} faces at sigma = {flags.threshold:g}, '

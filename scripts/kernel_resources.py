@@ -29,7 +29,7 @@ def main():
     for blk in re.findall(r'- \.agpr_count:.*?\.wavefront_size:', text, flags=re.S):
       g = lambda k: (re.search(rf'\.{k}:\s+(\S+)', blk) or [None, '?'])[1]
       name = subprocess.run(['c++filt', g('name')], capture_output=True, text=True).stdout.strip() or g('name')
-      name = re.sub(r'\(.*', '', name)
+      name = re.sub(r'\(.*', '', name.replace('(anonymous namespace)::', ''))
       print(f"| {src} | `{name}` | {g('vgpr_count')} | {g('agpr_count')} | {g('sgpr_count')} | {g('vgpr_spill_count')} | "
             f"{g('sgpr_spill_count')} | {g('private_segment_fixed_size')} | {g('group_segment_fixed_size')} |")
 
