@@ -740,6 +740,71 @@ int nrf_mesh_submesh_emit(const uint8_t* keep, int32_t num_vertices, const int32
 int nrf_mesh_gather_rows(const void* src, int32_t width, const int32_t* vertex_map, int32_t num_vertices, void* dst, int32_t max_rows,
                          void* stream);
 
+/* ---- Mesh rasteriser: which triangle every pixel of a camera sees, its depth and barycentrics ----
+ * Handle-free: screen (V,3) float32 rows (px, py, z) from anywhere (nrf_camera_table_project_depth, or an orthographic view formed
+ * by the caller), triangles (F,3) int32, DEVICE arrays; one camera per call.  Integer coverage, one rounding per float operation in
+ * the order written below, and an order-free 64-bit integer min per pixel: the image has the same bits on every run and for every
+ * order of the triangles.  Announced by NRF_HAS_MESH_RASTER (NRF_VERSION is unchanged).
+ *
+ * Usable vertex.  z > near, |px| <= 1048576 and |py| <= 1048576; all three comparisons are false for NaN.  near must be >= 0 and
+ *   finite (NRF_E_SHAPE otherwise).
+ * Snap.  X = (int64) rintf(px * 256.0f), Y likewise: eight sub-pixel bits.  Pixel (i, j), column i, row j, has its centre at
+ *   (Px, Py) = (256 i + 128, 256 j + 128).
+ * Skipped triangle.  An index outside [0, V); a vertex that is not usable -- there is NO clipping: a triangle that crosses the near
+ *   plane is dropped whole; the area A = (X1-X0)(Y2-Y0) - (Y1-Y0)(X2-X0) (int64; with the bound above every product is below 2^62)
+ *   is 0; or its pixel box is empty.  The pixel box is the set of pixels whose centre lies in [min X, max X] x [min Y, max Y],
+ *   clamped to the image: columns max(0, ceil((min X - 128) / 256)) .. min(W - 1, floor((max X - 128) / 256)), rows likewise.  Both
+ *   orientations are drawn: there is no back-face culling.
+ * Coverage.  s = sign(A).  For edge k from vertex a to vertex b, (a, b) = (1,2), (2,0), (0,1): dx = s (Xb - Xa), dy = s (Yb - Ya),
+ *   E_k = dx (Py - Ya) - dy (Px - Xa), all int64.  The pixel is covered iff for every k: E_k > 0, or E_k == 0 and the edge is
+ *   top-left, i.e. dy < 0, or dy == 0 and dx > 0.  A pixel centre on an edge two triangles share belongs to exactly one of them.
+ * Depth and barycentrics, float32: l_k = (float) E_k / (float)(s A) (int64 -> float32 rounds to nearest; IEEE division),
+ *   q_k = l_k / z_k, w = (q0 + q1) + q2, depth = 1.0f / w, b_k = q_k / w: perspective-correct.  With a distorted camera the edges are
+ *   straight in DISTORTED pixel space: exact at the vertices, second order in the triangle's size between them.
+ * Ownership.  The pixel goes to the covering triangle with the smallest key ((uint64) float_bits(depth) << 32) | face_index; depth is
+ *   positive, so its bits order as the floats do, and equal depth bits go to the lower face index.  One integer atomic min per
+ *   covered pixel: the result does not depend on the order of arrival.
+ * Outputs.  face_id (H,W) int32, depth (H,W), bary (H,W,3) or NULL.  Where no triangle covers the pixel: -1, 0, (0, 0, 0); else depth
+ *   and bary are recomputed for the owner by the device function the draw pass used.
+ * Interpolate.  out[p, c] = (b0 * a0[c] + b1 * a1[c]) + b2 * a2[c] over the owner's corners in the triangle's order; the `background`
+ *   row (NULL = zeros) where face_id[p] < 0 (or face_id[p] >= F, or a corner outside [0, V): nothing is read out of bounds).
+ * Visibility.  visible[v] = 1 iff v is a corner of a face that owns at least one pixel, else 0; the entry clears the array first.
+ *
+ * Launches of nrf_mesh_raster_draw, grids fixed by F, W, H; nothing on the host reads a device value, so the call can be captured:
+ *   clear (keys all ones, status 0); faces (a thread per triangle: one whose pixel box has at most 256 pixels is drawn by its
+ *   thread, a larger one is ranked by ballot into its workgroup's part of a list); scan (the workgroups' totals, one workgroup);
+ *   large (a fixed grid striding over the list by the device-side count, a workgroup of 256 per triangle, its threads striding over
+ *   the pixel box); resolve (a thread per pixel).  Every loop is bounded by a clamped pixel box or by F; no thread waits on another.
+ *   The image does not depend on the 256-pixel constant.
+ *
+ * Every refusal is decided before any HIP call and names the entry and the argument in nrf_last_error: a NULL pointer where one is
+ * required (NRF_E_NULL; a buffer may be NULL where its count is 0); a negative count, a width or height below 1, width * height >
+ * NRF_MESH_RASTER_MAX_PIXELS, a bad near, width_a < 1 (NRF_E_SHAPE); a workspace that is short or not 16-byte aligned
+ * (NRF_E_WORKSPACE).  F == 0 is no error: an empty image.  Asynchronous on `stream`, nothing allocated or synchronised. */
+#define NRF_HAS_MESH_RASTER 1
+#define NRF_MESH_RASTER_MAX_PIXELS (1 << 26)
+
+/* The first 16 bytes of a raster workspace (DEVICE memory; the caller may copy them) after nrf_mesh_raster_draw. */
+typedef struct nrf_mesh_raster_status {
+  int32_t drawn_triangles;     /* triangles that passed every skip rule above */
+  int32_t large_triangles;     /* of those, the ones that took the workgroup-per-triangle path */
+  int32_t covered_pixels;      /* pixels with face_id >= 0 */
+  int32_t reserved;
+} nrf_mesh_raster_status;
+
+/* Bytes of workspace (8 per pixel, about 4 per triangle).  Needs no GPU. */
+int nrf_mesh_raster_workspace_bytes(int32_t num_triangles, int32_t width, int32_t height, size_t* bytes);
+int nrf_mesh_raster_draw(const float* screen, int32_t num_vertices, const int32_t* triangles, int32_t num_triangles, int32_t width,
+                         int32_t height, float near, int32_t* face_id, float* depth, float* bary, void* workspace,
+                         size_t workspace_bytes, void* stream);
+/* attributes (V, width_a) float32 -> out (num_pixels, width_a); bary is required. */
+int nrf_mesh_raster_interpolate(const int32_t* face_id, const float* bary, int64_t num_pixels, const int32_t* triangles,
+                                int32_t num_triangles, const float* attributes, int32_t num_vertices, int32_t width_a,
+                                const float* background, float* out, void* stream);
+/* visible (V,) uint8. */
+int nrf_mesh_raster_visibility(const int32_t* face_id, int64_t num_pixels, const int32_t* triangles, int32_t num_triangles,
+                               int32_t num_vertices, uint8_t* visible, void* stream);
+
 /* flax.optim.Adam.apply_gradient (training.py:268-269; flax 0.3.4 optim/adam.py):
  * g = grad*grad_scale (grad_scale = 1/world_size folds lax.pmean, training.py:266),
  * m,v updated in place, step = number of updates already applied.  Hyper-parameters are doubles
@@ -896,6 +961,13 @@ int nrf_camera_table_rays(const float* cameras, int32_t num_cameras, const int32
 /* points (n,3) -> pixels (n,2). */
 int nrf_camera_table_project(const float* cameras, int32_t num_cameras, const int32_t* camera_index, const float* points, int64_t n,
                              float* pixels, void* stream);
+
+/* points (n,3) -> screen (n,3) = (px, py, z): (px, py) are the bits nrf_camera_table_project writes for the same inputs, z is the
+ * point's coordinate along the row's optical axis, orientation[6..8] . (point - position), the number the projection divides by.
+ * Validation, the camera_index rule (an index outside the table gives a row of zeros) and n == 0 are those of the entries above.
+ * There is NO reverse pass: the entry feeds nrf_mesh_raster_draw, which is not differentiable either. */
+int nrf_camera_table_project_depth(const float* cameras, int32_t num_cameras, const int32_t* camera_index, const float* points, int64_t n,
+                                   float* screen, void* stream);
 
 /* Bytes of workspace the two reverse passes below need for n rays (num_cameras is validated; today the size depends on n alone). */
 int nrf_camera_table_workspace_bytes(int64_t n, int32_t num_cameras, size_t* bytes);

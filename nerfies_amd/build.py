@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_DIR = os.path.join(HERE, '_lib')
 OBJ_DIR = os.path.join(LIB_DIR, 'obj')
 LIB_PATH = os.path.join(LIB_DIR, 'libnerfies_amd.so')
-SOURCES = ['mlp_chain.hip', 'mlp_chain32.hip', 'chain_frozen.hip', 'chain_query.hip', 'chain_query_grad.hip', 'mlp_bf16.hip', 'mlp_bf16x3.hip', 'warp_bf16.hip', 'warp_bf16x3.hip', 'warp_chain.hip', 'wgrad.hip', 'wgrad_bf16.hip', 'ray_kernels.hip', 'camera.hip', 'time_encoder.hip', 'nrf_plan.hip', 'nrf_run.hip', 'nrf_field.hip', 'mesh.hip', 'mesh_components.hip', 'nrf_api.hip']
+SOURCES = ['mlp_chain.hip', 'mlp_chain32.hip', 'chain_frozen.hip', 'chain_query.hip', 'chain_query_grad.hip', 'mlp_bf16.hip', 'mlp_bf16x3.hip', 'warp_bf16.hip', 'warp_bf16x3.hip', 'warp_chain.hip', 'wgrad.hip', 'wgrad_bf16.hip', 'ray_kernels.hip', 'camera.hip', 'time_encoder.hip', 'nrf_plan.hip', 'nrf_run.hip', 'nrf_field.hip', 'mesh.hip', 'mesh_components.hip', 'mesh_raster.hip', 'nrf_api.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
 # per-source extras.  mlp_bf16.hip: every chunk of the bf16 chains is a fully unrolled `#pragma unroll` loop (34-42 MFMA slots with
 # the previous panel's epilogue threaded through); above LLVM's default pragma-unroll threshold (16 k instructions) the loops

@@ -261,6 +261,13 @@ def project_from_table(table, points, camera_index=None):
   return autograd.camera_project(table, points, camera_index)
 
 
+def project_depth_from_table(table, points, camera_index=None):
+  """(px, py, z) [..., 3] of world `points` [..., 3] in row camera_index[...] of `table` (nrf_camera_table_project_depth): the pixel
+  of project_from_table, bit for bit, and the point's coordinate along the optical axis.  Detached: there is no reverse pass."""
+  from . import autograd
+  return autograd.camera_project_depth(table, points, camera_index)
+
+
 def compose_cameras(table, deltas):
   """The camera table (C, 24) that `deltas` (C, 16) make of `table` (nrf_camera_table_compose): per row R = exp(hat omega) R0 (the
   camera turns in its own frame), position + t, focal_length * exp(s), principal point and distortion coefficients added; columns

@@ -60,11 +60,12 @@ __device__ __forceinline__ void ray_direction(const CameraArgs& c, float2 px, fl
   wx *= inv2; wy *= inv2; wz *= inv2;
 }
 
-// (point - position) -> distorted pixel (camera.py:283-315)
-__device__ __forceinline__ float2 project_local(const CameraArgs& c, float tx, float ty, float tz) {
+// (point - position) -> distorted pixel (camera.py:283-315); lz_out, when given, receives the coordinate along the optical axis
+__device__ __forceinline__ float2 project_local(const CameraArgs& c, float tx, float ty, float tz, float* lz_out = nullptr) {
   const float lx = c.R[0] * tx + c.R[1] * ty + c.R[2] * tz;
   const float ly = c.R[3] * tx + c.R[4] * ty + c.R[5] * tz;
   const float lz = c.R[6] * tx + c.R[7] * ty + c.R[8] * tz;
+  if (lz_out) *lz_out = lz;
   float x = lx / lz, y = ly / lz;
   const float r2 = x * x + y * y;
   const float dist = 1.0f + r2 * (c.k1 + r2 * (c.k2 + c.k3 * r2));
@@ -199,10 +200,12 @@ __global__ __launch_bounds__(CAM_THREADS) void camera_table_rays_kernel(const fl
   }
 }
 
+// One kernel for nrf_camera_table_project (pixels (n,2), screen NULL) and nrf_camera_table_project_depth (screen (n,3) = pixel and
+// local z, pixels NULL): the arithmetic is the same instructions for both, so the pixel has the same bits.  No reverse pass takes z.
 __global__ __launch_bounds__(CAM_THREADS) void camera_table_project_kernel(const float* __restrict__ cameras, int num_cameras,
                                                                            const int* __restrict__ camera_index,
                                                                            const float* __restrict__ points, long n,
-                                                                           float2* __restrict__ pixels) {
+                                                                           float2* __restrict__ pixels, float* __restrict__ screen) {
   __shared__ float tile[3 * CAM_THREADS];
   const long base = (long)blockIdx.x * CAM_THREADS;
   const long lim = min((long)3 * CAM_THREADS, 3 * (n - base));
@@ -216,11 +219,18 @@ __global__ __launch_bounds__(CAM_THREADS) void camera_table_project_kernel(const
   if (i >= n) return;
   const int row = camera_row_of(camera_index, i, num_cameras);
   float2 px = make_float2(0.f, 0.f);
+  float z = 0.f;
   if (row >= 0) {
     const CameraArgs c = load_camera_row(cameras, row);
-    px = project_local(c, tile[3 * threadIdx.x] - c.pos[0], tile[3 * threadIdx.x + 1] - c.pos[1], tile[3 * threadIdx.x + 2] - c.pos[2]);
+    px = project_local(c, tile[3 * threadIdx.x] - c.pos[0], tile[3 * threadIdx.x + 1] - c.pos[1], tile[3 * threadIdx.x + 2] - c.pos[2], &z);
   }
-  pixels[i] = px;
+  if (screen) {
+    screen[3 * i + 0] = px.x;
+    screen[3 * i + 1] = px.y;
+    screen[3 * i + 2] = z;
+  } else {
+    pixels[i] = px;
+  }
 }
 
 // d distort / d (x, y) at (x, y), the matrix the forward's Newton step inverts.
@@ -568,7 +578,13 @@ void launch_camera_table_rays(const float* cameras, int num_cameras, const int* 
 void launch_camera_table_project(const float* cameras, int num_cameras, const int* camera_index, const float* points, long n,
                                  float* pixels, hipStream_t stream) {
   const unsigned blocks = (unsigned)((n + CAM_THREADS - 1) / CAM_THREADS);
-  camera_table_project_kernel<<<blocks, CAM_THREADS, 0, stream>>>(cameras, num_cameras, camera_index, points, n, (float2*)pixels);
+  camera_table_project_kernel<<<blocks, CAM_THREADS, 0, stream>>>(cameras, num_cameras, camera_index, points, n, (float2*)pixels, nullptr);
+}
+
+void launch_camera_table_project_depth(const float* cameras, int num_cameras, const int* camera_index, const float* points, long n,
+                                       float* screen, hipStream_t stream) {
+  const unsigned blocks = (unsigned)((n + CAM_THREADS - 1) / CAM_THREADS);
+  camera_table_project_kernel<<<blocks, CAM_THREADS, 0, stream>>>(cameras, num_cameras, camera_index, points, n, nullptr, screen);
 }
 
 void launch_camera_table_rays_backward(const float* cameras, int num_cameras, const int* camera_index, const float* pixels, long n,

@@ -653,6 +653,15 @@ int nrf_camera_table_project(const float* cameras, int32_t num_cameras, const in
   return check_launch("nrf_camera_table_project");
 }
 
+int nrf_camera_table_project_depth(const float* cameras, int32_t num_cameras, const int32_t* camera_index, const float* points, int64_t n,
+                                   float* screen, void* stream) {
+  CK(table_args(cameras, num_cameras, n));
+  if (n == 0) return NRF_OK;
+  if (!points || !screen) return fail(NRF_E_NULL, "points / screen is null");
+  launch_camera_table_project_depth(cameras, num_cameras, camera_index, points, (long)n, screen, (hipStream_t)stream);
+  return check_launch("nrf_camera_table_project_depth");
+}
+
 int nrf_camera_table_rays_backward(const float* cameras, int32_t num_cameras, const int32_t* camera_index, const float* pixels,
                                    int64_t n, const float* d_origins, const float* d_directions, float* d_cameras, float* d_pixels,
                                    void* workspace, size_t workspace_bytes, void* stream) {

@@ -639,6 +639,9 @@ void launch_camera_table_rays(const float* cameras, int num_cameras, const int* 
                               float* origins, float* directions, hipStream_t stream);
 void launch_camera_table_project(const float* cameras, int num_cameras, const int* camera_index, const float* points, long n,
                                  float* pixels, hipStream_t stream);
+// screen (n,3) = (px, py, z): the pixel of launch_camera_table_project and the point's coordinate along the optical axis
+void launch_camera_table_project_depth(const float* cameras, int num_cameras, const int* camera_index, const float* points, long n,
+                                       float* screen, hipStream_t stream);
 void launch_camera_table_rays_backward(const float* cameras, int num_cameras, const int* camera_index, const float* pixels, long n,
                                        const float* d_origins, const float* d_directions, float* d_cameras, float* d_pixels,
                                        void* workspace, hipStream_t stream);

@@ -480,6 +480,88 @@ def clean_mesh(mesh, keep='largest', min_triangles=1, lib=None):
   return out
 
 
+def _raster_rows(t, width, what):
+  t = torch.as_tensor(t)
+  if t.dtype != torch.float32 or t.dim() != 2 or (width is not None and t.shape[1] != width) or t.shape[1] < 1:
+    raise ValueError(f'{what} must be a float32 (V, {width or "A"}) tensor, got {t.dtype} {tuple(t.shape)}')
+  return t.contiguous()
+
+
+def rasterize_screen(screen, faces, image_size, near=0.0, attributes=None, background=0.0, lib=None):
+  """nrf_mesh_raster_draw on a (V, 3) float32 device tensor of (px, py, z) rows from anywhere, then one nrf_mesh_raster_interpolate
+  per entry of `attributes`: what rasterize_mesh runs after its projection (an orthographic view is screen = (x, y, z) scaled by the
+  caller).  image_size is (width, height).  Returns rasterize_mesh's dict, with 'status': the (4,) int32 device tensor of the
+  workspace's nrf_mesh_raster_status (drawn triangles, large triangles, covered pixels, 0)."""
+  lib = lib or L.load_library()
+  screen = _raster_rows(screen, 3, 'screen')
+  faces = _faces_arg(faces).to(screen.device)
+  device = screen.device
+  W, H = int(image_size[0]), int(image_size[1])
+  V, F = screen.shape[0], faces.shape[0]
+  stream = _stream_arg(device)
+  ptr = lambda t: t.data_ptr() if t.numel() else None
+  ws = _mesh_workspace(lib, lambda nv, nt, out: lib.nrf_mesh_raster_workspace_bytes(nt, W, H, out), V, F, device)
+  face_id = torch.empty(H, W, dtype=torch.int32, device=device)
+  depth = torch.empty(H, W, dtype=torch.float32, device=device)
+  bary = torch.empty(H, W, 3, dtype=torch.float32, device=device)
+  L.check(lib.nrf_mesh_raster_draw(ptr(screen), V, ptr(faces), F, W, H, float(near), face_id.data_ptr(), depth.data_ptr(), bary.data_ptr(),
+                                   ws.data_ptr(), ws.numel() * 4, stream), lib)
+  out = {'face_id': face_id, 'depth': depth, 'mask': face_id >= 0, 'bary': bary, 'status': ws[:4].clone()}
+  for name, rows in (attributes or {}).items():
+    if name in out or name == 'screen':
+      raise ValueError(f'attribute name {name!r} is one of the raster outputs')
+    rows = _raster_rows(rows, None, f'attributes[{name!r}]').to(device)
+    if rows.shape[0] != V:
+      raise ValueError(f'attributes[{name!r}] has {rows.shape[0]} rows for {V} vertices')
+    A = rows.shape[1]
+    bg = torch.as_tensor(background[name] if isinstance(background, dict) else background, dtype=torch.float32).to(device)
+    bg = bg.expand(A).contiguous() if bg.dim() <= 1 else bg
+    if tuple(bg.shape) != (A,):
+      raise ValueError(f'background of {name!r} must be a scalar or ({A},), got {tuple(bg.shape)}')
+    value = torch.empty(H, W, A, dtype=torch.float32, device=device)
+    L.check(lib.nrf_mesh_raster_interpolate(face_id.data_ptr(), bary.data_ptr(), H * W, ptr(faces), F, ptr(rows), V, A, bg.data_ptr(),
+                                            value.data_ptr(), stream), lib)
+    out[name] = value
+  return out
+
+
+def rasterize_mesh(vertices, faces, table, image_size, camera_row=0, near=0.0, attributes=None, background=0.0, lib=None):
+  """One frame's mesh seen by one camera, all on the device (nrf_camera_table_project_depth, nrf_mesh_raster_draw, then one
+  nrf_mesh_raster_interpolate per attribute; the definition is in include/nerfies_amd.h): `vertices` (V, 3) float32, `faces` (F, 3)
+  int32, `table` a pack_cameras table of which row `camera_row` is used, image_size (width, height), `near` the plane behind which a
+  vertex drops its triangles whole (no clipping).  `attributes` is a dict name -> (V, A) float32, e.g. {'rgb': ..., 'normals': ...,
+  'points': vertices}; `background` a scalar, an (A,) row, or a dict of those by name.  Returns device tensors {'face_id' (H, W) int32
+  (-1: no triangle), 'depth' (H, W) along the optical axis (0 where empty), 'mask' (H, W) bool, 'bary' (H, W, 3), 'screen' (V, 3),
+  'status' (4,) int32 and one (H, W, A) tensor per attribute}, the same bits on every run and for every order of the faces."""
+  from nerfies_amd import camera as camera_lib
+  lib = lib or L.load_library()
+  vertices = _raster_rows(vertices, 3, 'vertices')
+  row = int(camera_row)
+  if not 0 <= row < table.shape[0]:
+    raise ValueError(f'camera_row = {row} is outside the table of {table.shape[0]} rows')
+  index = torch.full((vertices.shape[0],), row, dtype=torch.int32, device=vertices.device) if row else None
+  screen = camera_lib.project_depth_from_table(table, vertices, index)
+  out = rasterize_screen(screen, faces, image_size, near=near, attributes=attributes, background=background, lib=lib)
+  out['screen'] = screen
+  return out
+
+
+def mesh_visibility(raster, faces, num_vertices, lib=None):
+  """(V,) bool: the vertices that are a corner of a face owning at least one pixel of `raster` (a rasterize_mesh result, or its
+  'face_id' tensor): nrf_mesh_raster_visibility."""
+  lib = lib or L.load_library()
+  face_id = (raster['face_id'] if isinstance(raster, dict) else raster).contiguous()
+  if face_id.dtype != torch.int32:
+    raise ValueError(f'face_id must be int32, got {face_id.dtype}')
+  faces = _faces_arg(faces).to(face_id.device)
+  V = int(num_vertices)
+  visible = torch.empty(V, dtype=torch.uint8, device=face_id.device)
+  ptr = lambda t: t.data_ptr() if t.numel() else None
+  L.check(lib.nrf_mesh_raster_visibility(ptr(face_id), face_id.numel(), ptr(faces), faces.shape[0], V, ptr(visible),
+                                         _stream_arg(face_id.device)), lib)
+  return visible.bool()
+
+
 def extract_mesh(model, params, bbox_min, bbox_max, resolution, threshold, level='fine', warp_id=None, appearance_id=None, camera_id=None,
                  warp_extra=None, refine_steps=2, colors=True, chunk=1 << 21, clean=None):
   """A triangle mesh of the field's level set sigma = threshold over the box [bbox_min, bbox_max], all on the device: `density_grid`

@@ -165,6 +165,11 @@ class MeshComponentsStatus(C.Structure):
   _fields_ = [('num_components', C.c_int32), ('table_components', C.c_int32), ('error', C.c_int32), ('reserved', C.c_int32)]
 
 
+class MeshRasterStatus(C.Structure):
+  """nrf_mesh_raster_status: the first 16 bytes of a raster workspace (device memory) after nrf_mesh_raster_draw."""
+  _fields_ = [('drawn_triangles', C.c_int32), ('large_triangles', C.c_int32), ('covered_pixels', C.c_int32), ('reserved', C.c_int32)]
+
+
 NRF_QUERY_MAX_POINTS = 1 << 24   # points of one nrf_query_points / nrf_query_grid call
 NRF_QUERY_GRAD_MAX_POINTS = 1 << 20   # points of one nrf_query_points_grad / nrf_query_grid_grad call
 NRF_GRID_MAX_POINTS = 1 << 40    # points of a whole nrf_grid
@@ -172,6 +177,8 @@ NRF_HAS_UNWARP = 1
 NRF_UNWARP_MAX_POINTS = 1 << 20  # points of one nrf_unwarp_points call
 NRF_UNWARP_MAX_STEPS = 32        # Newton rounds of one nrf_unwarp_points call
 NRF_MESH_MAX_CELLS = 1 << 28     # cells of a grid handed to nrf_mesh_count / nrf_mesh_emit (triangle indices stay in int32)
+NRF_HAS_MESH_RASTER = 1
+NRF_MESH_RASTER_MAX_PIXELS = 1 << 26   # pixels of one nrf_mesh_raster_draw image
 NRF_OPT_CHAIN_TILE_ROWS = 1
 NRF_OPT_BF16_WGRAD_MERGE = 2
 
@@ -185,7 +192,7 @@ EXPORTS = [
     'nrf_dynamic_scalars_write', 'nrf_adam_step_dynamic', 'nrf_set_option', 'nrf_debug_plan_digest', 'nrf_backward_ex',
     'nrf_backward_rays',
     'nrf_camera_table_rays', 'nrf_camera_table_project', 'nrf_camera_table_workspace_bytes', 'nrf_camera_table_rays_backward',
-    'nrf_camera_table_project_backward',
+    'nrf_camera_table_project_backward', 'nrf_camera_table_project_depth',
     'nrf_train_step_loss_grad_rays', 'nrf_camera_table_compose', 'nrf_camera_table_compose_backward',
     'nrf_loss_grad_rays',
     'nrf_query_workspace_bytes', 'nrf_query_points', 'nrf_query_grid',
@@ -194,6 +201,7 @@ EXPORTS = [
     'nrf_mesh_workspace_bytes', 'nrf_mesh_count', 'nrf_mesh_emit', 'nrf_mesh_snap',
     'nrf_mesh_components_workspace_bytes', 'nrf_mesh_components', 'nrf_mesh_component_table',
     'nrf_mesh_submesh_workspace_bytes', 'nrf_mesh_submesh_count', 'nrf_mesh_submesh_emit', 'nrf_mesh_gather_rows',
+    'nrf_mesh_raster_workspace_bytes', 'nrf_mesh_raster_draw', 'nrf_mesh_raster_interpolate', 'nrf_mesh_raster_visibility',
 ]
 
 _lib = None
@@ -274,11 +282,16 @@ def load_library(path=None):
       'nrf_mesh_submesh_count': [vp, i32, vp, i32, vp, vp, C.c_size_t, vp],
       'nrf_mesh_submesh_emit': [vp, i32, vp, i32, i32, i32, vp, vp, vp, C.c_size_t, vp],
       'nrf_mesh_gather_rows': [vp, i32, vp, i32, vp, i32, vp],
+      'nrf_mesh_raster_workspace_bytes': [i32, i32, i32, C.POINTER(C.c_size_t)],
+      'nrf_mesh_raster_draw': [vp, i32, vp, i32, i32, i32, f32, vp, vp, vp, vp, C.c_size_t, vp],
+      'nrf_mesh_raster_interpolate': [vp, vp, i64, vp, i32, vp, i32, i32, vp, vp, vp],
+      'nrf_mesh_raster_visibility': [vp, i64, vp, i32, i32, vp, vp],
       'nrf_camera_pixels_to_rays': [C.POINTER(CameraDesc), vp, i64, vp, vp, vp, vp],
       'nrf_camera_pixels_to_points': [C.POINTER(CameraDesc), vp, vp, i64, vp, vp],
       'nrf_camera_project': [C.POINTER(CameraDesc), vp, i64, vp, vp],
       'nrf_camera_table_rays': [vp, i32, vp, vp, i64, vp, vp, vp],
       'nrf_camera_table_project': [vp, i32, vp, vp, i64, vp, vp],
+      'nrf_camera_table_project_depth': [vp, i32, vp, vp, i64, vp, vp],
       'nrf_camera_table_workspace_bytes': [i64, i32, C.POINTER(C.c_size_t)],
       'nrf_camera_table_rays_backward': [vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, C.c_size_t, vp],
       'nrf_camera_table_project_backward': [vp, i32, vp, vp, i64, vp, vp, vp, vp, C.c_size_t, vp],

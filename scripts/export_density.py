@@ -25,7 +25,16 @@ With --mesh --canonical --animate ITEM_ID [ITEM_ID ...] (evaluation.animate_mesh
 template's vertices, Newton's iteration on the device, each frame started from the one before):
   mesh_canonical_at_<item_id>.ply   the template carried into that frame: the same vertex_indices and colours, the vertices x with
                        warp(x, frame) = template vertex, the normals of the field there.  Vertices that did not converge are counted
-                       in the printed summary and written as they are."""
+                       in the printed summary and written as they are.
+With --mesh --render_mesh ITEM_ID [ITEM_ID ...] (evaluation.rasterize_mesh -> nrf_camera_table_project_depth / nrf_mesh_raster_draw /
+nrf_mesh_raster_interpolate: the mesh rasterised on the device into that item's own camera, at the capture's image size and near plane;
+an item named by --animate is drawn with the mesh carried into it, any other with the mesh as extracted):
+  mesh_render_<item_id>.png   the mesh over a white background, coloured by its vertices' rgb or, with --render_shading normals, by
+                       its normals (n / 2 + 1 / 2),
+  mesh_depth_<item_id>.npy    float32 (H, W): the distance from the camera's position to the mesh along each pixel's ray, 0 where no
+                       triangle covers the pixel,
+and prints the covered share of pixels and the median of |mesh ray distance - NeRF depth| over the covered pixels, the NeRF depth
+being that of evaluation.render_image for the same camera."""
 import argparse
 import os
 import sys
@@ -37,7 +46,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import train as train_driver   # noqa: E402
-from nerfies_amd import checkpoints, configs, evaluation, models, training   # noqa: E402
+from nerfies_amd import camera as camera_lib, checkpoints, configs, evaluation, models, training   # noqa: E402
+from nerfies_amd import visualization as viz   # noqa: E402
 from nerfies_amd import gin_lite as gin   # noqa: E402
 
 VIEW_DIRECTION = (0.0, 0.0, 1.0)   # the direction every exported colour is queried along
@@ -61,6 +71,12 @@ def parse_flags(argv=None):
   p.add_argument('--animate', nargs='+', default=None, metavar='ITEM_ID',
                  help='with --mesh --canonical: carry the template mesh into these frames (mesh_canonical_at_<item_id>.ply each)')
   p.add_argument('--animate_steps', type=int, default=8, metavar='K', help='Newton rounds per frame of --animate')
+  p.add_argument('--render_mesh', nargs='+', default=None, metavar='ITEM_ID',
+                 help="with --mesh: rasterise the mesh into these items' cameras (mesh_render_<item_id>.png, mesh_depth_<item_id>.npy) and "
+                      "compare it with the NeRF's depth there.  The NeRF's `depth` is a distance along unit rays, not the coordinate z along "
+                      "the optical axis the rasteriser orders by: the mesh side is converted, to |interpolated surface point - camera "
+                      "position|, and that distance is what the .npy holds")
+  p.add_argument('--render_shading', default='rgb', choices=['rgb', 'normals'], help='with --render_mesh: what colours the PNG')
   p.add_argument('--margin', type=float, default=0.0, help="grow the scene points' box by this fraction of its size on every side")
   own, rest = p.parse_known_args(argv)
   if len(own.resolution) not in (1, 3):
@@ -73,6 +89,8 @@ def parse_flags(argv=None):
     p.error('--mesh_min_triangles must not be negative')
   if own.animate is not None and not (own.mesh and own.canonical):
     p.error('--animate carries the canonical mesh into frames: it needs --mesh --canonical')
+  if own.render_mesh is not None and not own.mesh:
+    p.error('--render_mesh rasterises the mesh: it needs --mesh')
   flags = train_driver.parse_flags(rest)
   for k, v in vars(own).items():
     setattr(flags, k, v)
@@ -130,8 +148,9 @@ def print_component_table(name, comps, head=8):
   return len(nt)
 
 
-def animate(flags, model, target, warp_extra, datasource, mesh, alpha_app, exp_dir):
-  """--animate: the template `mesh` carried into every frame of flags.animate; {item id: its PLY}."""
+def animate(flags, model, target, warp_extra, datasource, mesh, alpha_app, exp_dir, carried=None):
+  """--animate: the template `mesh` carried into every frame of flags.animate; {item id: its PLY}.  `carried`, when given, receives
+  {item id: (vertices, normals)} on the device."""
   if not model.use_warp or model.warp_metadata_encoder_type == 'time':
     raise SystemExit('--animate: needs a model with a warp field driven by warp ids (not the time encoder)')
   known = list(datasource.train_ids) + list(datasource.val_ids)
@@ -156,7 +175,45 @@ def animate(flags, model, target, warp_extra, datasource, mesh, alpha_app, exp_d
     print(f'mesh_canonical_at_{item}: {nv} vertices, {nv - left - stopped} converged, {left} out of steps, {stopped} stopped at a singular '
           f'step, largest residual {worst:.3g} -> {path}', flush=True)
     written[item] = path
+    if carried is not None:
+      carried[item] = (verts, normals)
   return written
+
+
+def render_mesh(flags, model, state, datasource, mesh, carried, exp_dir):
+  """--render_mesh: the mesh rasterised into each item's camera and held against the field's own depth there;
+  {item id: {'png', 'depth_npy', 'covered', 'median_abs_depth_difference'}}."""
+  known = list(datasource.train_ids) + list(datasource.val_ids)
+  device = mesh['faces'].device
+  model_fn = lambda key_0, key_1, params, rays, warp_extra: model.apply({'params': params}, rays, warp_extra)
+  out = {}
+  for item in flags.render_mesh:
+    if item not in known:
+      raise SystemExit(f'--render_mesh {item}: not an item of the capture')
+    vertices, normals = carried.get(item, (mesh['vertices'], mesh['normals']))
+    cam = datasource.load_camera(item)
+    W, H = int(cam.image_size[0]), int(cam.image_size[1])
+    table = camera_lib.pack_cameras([cam], device)
+    shade = mesh['rgb'] if flags.render_shading == 'rgb' else normals * 0.5 + 0.5
+    raster = evaluation.rasterize_mesh(vertices, mesh['faces'], table, (W, H), near=datasource.near,
+                                       attributes={'shade': shade.float().contiguous(), 'points': vertices}, background={'shade': 1.0, 'points': 0.0},
+                                       lib=model.lib)
+    mask = raster['mask']
+    position = table[0, 9:12]
+    distance = torch.where(mask, (raster['points'] - position).norm(dim=-1), torch.zeros((), device=device))
+    png = os.path.join(exp_dir, f'mesh_render_{item}.png')
+    viz.save_image(png, viz.image_to_uint8(raster['shade'].cpu().numpy()))
+    depth_npy = os.path.join(exp_dir, f'mesh_depth_{item}.npy')
+    np.save(depth_npy, distance.cpu().numpy())
+    rays = datasource.item_rays(item, device)
+    rays = {k: rays[k] for k in ('origins', 'directions', 'viewdirs', 'metadata') if k in rays}
+    field = evaluation.render_image(state, rays, model_fn, chunk=8192)['depth'].reshape(H, W)
+    covered = float(mask.float().mean())
+    median = float((distance - field).abs()[mask].median()) if bool(mask.any()) else float('nan')
+    print(f'mesh_render_{item}: {W} x {H}, {covered:.2%} of the pixels covered, median |mesh ray distance - NeRF depth| {median:.4g} over '
+          f'them -> {png}, {depth_npy}', flush=True)
+    out[item] = {'png': png, 'depth_npy': depth_npy, 'covered': covered, 'median_abs_depth_difference': median}
+  return out
 
 
 def main(argv=None):
@@ -248,8 +305,11 @@ def main(argv=None):
     print(f'mesh_{name}: {mesh["vertices"].shape[0]} vertices, {mesh["faces"].shape[0]} faces at sigma = {flags.threshold:g}, '
           f'{flags.mesh_refine} refine steps -> {mesh_ply}', flush=True)
     ret.update(mesh_ply=mesh_ply, num_mesh_vertices=int(mesh['vertices'].shape[0]), num_mesh_faces=int(mesh['faces'].shape[0]))
+    carried = {}
     if flags.animate is not None:
-      ret['animated'] = animate(flags, model, target, state.warp_extra, datasource, mesh, alpha_app, exp_dir)
+      ret['animated'] = animate(flags, model, target, state.warp_extra, datasource, mesh, alpha_app, exp_dir, carried)
+    if flags.render_mesh is not None:
+      ret['rendered'] = render_mesh(flags, model, state, datasource, mesh, carried, exp_dir)
   return ret
 
 
