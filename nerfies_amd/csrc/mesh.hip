@@ -1,16 +1,15 @@
 // Surface nets on a device density grid (nrf_mesh_count / nrf_mesh_emit / nrf_mesh_snap; the definition is in
 // include/nerfies_amd.h): an indexed, deterministic triangle mesh of the level set sigma = threshold.
 //
-// Cells are walked in their linear order, i fastest: a workgroup of 256 threads owns MESH_BLOCK_CELLS = 1024 consecutive cells as
-// four rounds of 256, so the 64 lanes of a wave read consecutive x (the eight corner reads of a wave are eight runs of 65 floats,
-// but for the rows that end inside the wave) and the neighbours' re-reads hit the cache.  Every output slot is a rank: the number of
-// active cells (quads) before this one in that order = scanned workgroup total + the totals of the (round, wave) pairs before this
-// wave + the popcount of the wave's ballot below this lane.  No atomic, no flag another workgroup waits on: classify stores
-// per-workgroup totals, a one-workgroup kernel scans them, the emit kernels read the scan.
+// Cells are walked in their linear order, i fastest: a workgroup of 256 threads owns Cells::BLOCK = 1024 consecutive cells as four
+// rounds of 256, so the 64 lanes of a wave read consecutive x (the eight corner reads of a wave are eight runs of 65 floats, but for
+// the rows that end inside the wave) and the neighbours' re-reads hit the cache.  Every output slot is a rank, by the rule of
+// mesh_rank.h: the number of active cells (quads) before this one in that order.  The kernels here say what is voted on (a cell is
+// active; the up to three quads it owns) and what is written at the slot; the host half is built from mesh_host.h.
 //
 // Every float operation below is a single rounding in the order the header states: contraction is off for the whole file.
-#include "mesh_scan.h"
-#include "nrf_handle.h"
+#include "mesh_host.h"
+#include "mesh_rank.h"
 
 #include <cmath>
 
@@ -21,19 +20,14 @@ using namespace nrf::api;
 
 namespace {
 
-constexpr int MESH_THREADS = 256;
-constexpr int MESH_WAVES = MESH_THREADS / 64;
-constexpr int MESH_ROUNDS = 4;
-constexpr int MESH_BLOCK_CELLS = MESH_THREADS * MESH_ROUNDS;
-constexpr int MESH_SLOTS = MESH_ROUNDS * MESH_WAVES;   // (round, wave) pairs of a workgroup, in cell order
-constexpr size_t MESH_HEADER_BYTES = 256;              // nrf_mesh_status, padded
-constexpr size_t MESH_ALIGN = 256;
+constexpr int ROUNDS = 4;
+using Cells = MeshRank<ROUNDS>;
 
 struct MeshDims {
   int X, Y, Z;      // samples
   int cx, cy, cz;   // cells
   int ncells;
-  int nblocks;      // workgroups of MESH_BLOCK_CELLS cells
+  int nblocks;      // workgroups of Cells::BLOCK cells
 };
 
 // byte offsets of the workspace's regions
@@ -46,18 +40,18 @@ MeshDims mesh_dims(const nrf_grid* g) {
   d.X = g->dims[0]; d.Y = g->dims[1]; d.Z = g->dims[2];
   d.cx = d.X - 1; d.cy = d.Y - 1; d.cz = d.Z - 1;
   d.ncells = d.cx * d.cy * d.cz;
-  d.nblocks = (d.ncells + MESH_BLOCK_CELLS - 1) / MESH_BLOCK_CELLS;
+  d.nblocks = (int)blocks_of(d.ncells, Cells::BLOCK);
   return d;
 }
 
 MeshPlan mesh_plan(const MeshDims& d) {
   MeshPlan p;
-  size_t o = MESH_HEADER_BYTES;
-  p.block_v = o; o = align_up(o + sizeof(int) * (size_t)d.nblocks, MESH_ALIGN);
-  p.block_q = o; o = align_up(o + sizeof(int) * (size_t)d.nblocks, MESH_ALIGN);
-  p.mask = o;    o = align_up(o + (size_t)d.ncells, MESH_ALIGN);
-  p.map = o;     o = align_up(o + sizeof(int) * (size_t)d.ncells, MESH_ALIGN);
-  p.total = o;
+  MeshCarve c;
+  p.block_v = c.take(sizeof(int) * (size_t)d.nblocks);
+  p.block_q = c.take(sizeof(int) * (size_t)d.nblocks);
+  p.mask = c.take((size_t)d.ncells);
+  p.map = c.take(sizeof(int) * (size_t)d.ncells);
+  p.total = c.total;
   return p;
 }
 
@@ -68,7 +62,8 @@ __device__ __forceinline__ void cell_coords(int cell, const MeshDims& d, int& i,
   k = r / d.cy;
 }
 
-__device__ __forceinline__ unsigned long long lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
+// a thread's cell of round r: an int, as everything derived from it is (at most NRF_MESH_MAX_CELLS cells, rounded up to a workgroup)
+__device__ __forceinline__ int owned_cell(const int r) { return (int)Cells::owned(r); }
 
 // the three quads a cell may own, from its corner mask and its position: bit ax set iff the samples at c and c + e_ax differ in
 // insideness and c[u] >= 1, c[v] >= 1 (u = ax + 1, v = ax + 2 mod 3)
@@ -85,12 +80,11 @@ __device__ __forceinline__ unsigned owned_quads(unsigned m, int i, int j, int k)
 __global__ __launch_bounds__(MESH_THREADS) void mesh_classify_kernel(const float* __restrict__ sigma, const MeshDims d, const float thr,
                                                                      unsigned char* __restrict__ mask, int* __restrict__ block_v,
                                                                      int* __restrict__ block_q) {
-  __shared__ int sv[MESH_SLOTS], sq[MESH_SLOTS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ int sv[Cells::SLOTS], sq[Cells::SLOTS];
   const size_t sy = (size_t)d.X, sz = (size_t)d.X * (size_t)d.Y;
 #pragma unroll
-  for (int r = 0; r < MESH_ROUNDS; ++r) {
-    const int cell = blockIdx.x * MESH_BLOCK_CELLS + r * MESH_THREADS + threadIdx.x;
+  for (int r = 0; r < ROUNDS; ++r) {
+    const int cell = owned_cell(r);
     bool active = false;
     unsigned q = 0;
     if (cell < d.ncells) {
@@ -107,20 +101,13 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_classify_kernel(const float
       active = m != 0u && m != 255u;
       q = owned_quads(m, i, j, k);
     }
-    const unsigned long long bv = __ballot(active);
-    const unsigned long long bx = __ballot((q & 1u) != 0u), by = __ballot((q & 2u) != 0u), bz = __ballot((q & 4u) != 0u);
-    if (lane == 0) {
-      sv[r * MESH_WAVES + wave] = __popcll(bv);
-      sq[r * MESH_WAVES + wave] = __popcll(bx) + __popcll(by) + __popcll(bz);
-    }
+    Cells::vote(sv, r, active);
+    Cells::vote<3>(sq, r, q);
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    int tv = 0, tq = 0;
-#pragma unroll
-    for (int e = 0; e < MESH_SLOTS; ++e) { tv += sv[e]; tq += sq[e]; }
-    block_v[blockIdx.x] = tv;
-    block_q[blockIdx.x] = tq;
+    block_v[blockIdx.x] = Cells::block_total(sv);
+    block_q[blockIdx.x] = Cells::block_total(sq);
   }
 }
 
@@ -186,54 +173,40 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_vertices_kernel(const float
                                                                      const int max_vertices, const int max_triangles,
                                                                      float* __restrict__ vertices, int* __restrict__ vertex_cell,
                                                                      int* __restrict__ map) {
-  __shared__ int sv[MESH_SLOTS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ int sv[Cells::SLOTS];
   const bool fits = status[0] <= max_vertices && status[1] <= max_triangles;
-  int rank[MESH_ROUNDS];
-  unsigned ms[MESH_ROUNDS];
+  int rank[ROUNDS];
+  unsigned ms[ROUNDS];
 #pragma unroll
-  for (int r = 0; r < MESH_ROUNDS; ++r) {
-    const int cell = blockIdx.x * MESH_BLOCK_CELLS + r * MESH_THREADS + threadIdx.x;
-    const unsigned m = cell < d.ncells ? (unsigned)mask[cell] : 0u;
-    const unsigned long long bv = __ballot(m != 0u && m != 255u);
-    ms[r] = m;
-    rank[r] = __popcll(bv & lanes_below());
-    if (lane == 0) sv[r * MESH_WAVES + wave] = __popcll(bv);
+  for (int r = 0; r < ROUNDS; ++r) {
+    const int cell = owned_cell(r);
+    ms[r] = cell < d.ncells ? (unsigned)mask[cell] : 0u;
+    rank[r] = Cells::vote(sv, r, ms[r] != 0u && ms[r] != 255u);
   }
   __syncthreads();
   if (blockIdx.x == 0 && threadIdx.x == 0) {   // what the caller reads back: all of the mesh, or none of it
     status[2] = fits ? status[0] : 0;
     status[3] = fits ? status[1] : 0;
   }
-  int before = block_v[blockIdx.x];
   const size_t sy = (size_t)d.X, sz = (size_t)d.X * (size_t)d.Y;
-#pragma unroll
-  for (int r = 0; r < MESH_ROUNDS; ++r) {
-#pragma unroll
-    for (int w = 0; w < MESH_WAVES; ++w) {
-      const int e = r * MESH_WAVES + w;
-      if (w == wave) {
-        const int cell = blockIdx.x * MESH_BLOCK_CELLS + r * MESH_THREADS + threadIdx.x;
-        const unsigned m = ms[r];
-        if (cell < d.ncells) {
-          const bool active = m != 0u && m != 255u;
-          const int vid = before + rank[r];
-          map[cell] = active ? vid : -1;
-          if (active && fits && vid < max_vertices) {
-            int i, j, k;
-            cell_coords(cell, d, i, j, k);
-            float p[3];
-            cell_vertex(sigma + ((size_t)i + sy * (size_t)j + sz * (size_t)k), sy, sz, m, thr, i, j, k, g, p);
-            vertices[3 * (size_t)vid + 0] = p[0];
-            vertices[3 * (size_t)vid + 1] = p[1];
-            vertices[3 * (size_t)vid + 2] = p[2];
-            vertex_cell[vid] = cell;
-          }
-        }
-      }
-      before += sv[e];
+  Cells::walk(sv, block_v[blockIdx.x], [&](const int r, const int before) {
+    const int cell = owned_cell(r);
+    const unsigned m = ms[r];
+    if (cell >= d.ncells) return;
+    const bool active = m != 0u && m != 255u;
+    const int vid = before + rank[r];
+    map[cell] = active ? vid : -1;
+    if (active && fits && vid < max_vertices) {
+      int i, j, k;
+      cell_coords(cell, d, i, j, k);
+      float p[3];
+      cell_vertex(sigma + ((size_t)i + sy * (size_t)j + sz * (size_t)k), sy, sz, m, thr, i, j, k, g, p);
+      vertices[3 * (size_t)vid + 0] = p[0];
+      vertices[3 * (size_t)vid + 1] = p[1];
+      vertices[3 * (size_t)vid + 2] = p[2];
+      vertex_cell[vid] = cell;
     }
-  }
+  });
 }
 
 // Stage 3b: two triangles per owned quad, from the map.
@@ -241,14 +214,13 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_faces_kernel(const MeshDims
                                                                   const int* __restrict__ map, const int* __restrict__ block_q,
                                                                   const int* __restrict__ status, const int max_vertices,
                                                                   const int max_triangles, int* __restrict__ triangles) {
-  __shared__ int sq[MESH_SLOTS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ int sq[Cells::SLOTS];
   if (!(status[0] <= max_vertices && status[1] <= max_triangles)) return;   // uniform over the grid
-  int rank[MESH_ROUNDS];
-  unsigned qs[MESH_ROUNDS];
+  int rank[ROUNDS];
+  unsigned qs[ROUNDS];
 #pragma unroll
-  for (int r = 0; r < MESH_ROUNDS; ++r) {
-    const int cell = blockIdx.x * MESH_BLOCK_CELLS + r * MESH_THREADS + threadIdx.x;
+  for (int r = 0; r < ROUNDS; ++r) {
+    const int cell = owned_cell(r);
     unsigned q = 0;
     if (cell < d.ncells) {
       int i, j, k;
@@ -256,45 +228,34 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_faces_kernel(const MeshDims
       const unsigned m = (unsigned)mask[cell];
       q = owned_quads(m, i, j, k) | ((m & 1u) << 3);   // bit 3: the sample at c is inside
     }
-    const unsigned long long bx = __ballot((q & 1u) != 0u), by = __ballot((q & 2u) != 0u), bz = __ballot((q & 4u) != 0u);
-    const unsigned long long lt = lanes_below();
     qs[r] = q;
-    rank[r] = __popcll(bx & lt) + __popcll(by & lt) + __popcll(bz & lt);
-    if (lane == 0) sq[r * MESH_WAVES + wave] = __popcll(bx) + __popcll(by) + __popcll(bz);
+    rank[r] = Cells::vote<3>(sq, r, q);   // a lane's quads are consecutive, in axis order
   }
   __syncthreads();
-  int before = block_q[blockIdx.x];
   const int ey = d.cx, ez = d.cx * d.cy;   // cell strides
+  Cells::walk(sq, block_q[blockIdx.x], [&](const int r, const int before) {
+    if ((qs[r] & 7u) == 0u) return;
+    const int cell = owned_cell(r);
+    const bool inside = (qs[r] & 8u) != 0u;
+    int quad = before + rank[r];
 #pragma unroll
-  for (int r = 0; r < MESH_ROUNDS; ++r) {
-#pragma unroll
-    for (int w = 0; w < MESH_WAVES; ++w) {
-      const int e = r * MESH_WAVES + w;
-      if (w == wave && (qs[r] & 7u) != 0u) {
-        const int cell = blockIdx.x * MESH_BLOCK_CELLS + r * MESH_THREADS + threadIdx.x;
-        const bool inside = (qs[r] & 8u) != 0u;
-        int quad = before + rank[r];
-#pragma unroll
-        for (int ax = 0; ax < 3; ++ax) {
-          if (((qs[r] >> ax) & 1u) == 0u) continue;
-          const int eu = ax == 0 ? ey : (ax == 1 ? ez : 1), ev = ax == 0 ? ez : (ax == 1 ? 1 : ey);
-          int q0 = map[cell - eu - ev], q1 = map[cell - ev], q2 = map[cell], q3 = map[cell - eu];
-          if (!inside) {
-            int t = q0; q0 = q3; q3 = t;
-            t = q1; q1 = q2; q2 = t;
-          }
-          const long long tri = 2ll * quad;
-          if (tri + 1 < (long long)max_triangles) {
-            int* o = triangles + 3 * (size_t)tri;
-            o[0] = q0; o[1] = q1; o[2] = q2;
-            o[3] = q0; o[4] = q2; o[5] = q3;
-          }
-          ++quad;
-        }
+    for (int ax = 0; ax < 3; ++ax) {
+      if (((qs[r] >> ax) & 1u) == 0u) continue;
+      const int eu = ax == 0 ? ey : (ax == 1 ? ez : 1), ev = ax == 0 ? ez : (ax == 1 ? 1 : ey);
+      int q0 = map[cell - eu - ev], q1 = map[cell - ev], q2 = map[cell], q3 = map[cell - eu];
+      if (!inside) {
+        int t = q0; q0 = q3; q3 = t;
+        t = q1; q1 = q2; q2 = t;
       }
-      before += sq[e];
+      const long long tri = 2ll * quad;
+      if (tri + 1 < (long long)max_triangles) {
+        int* o = triangles + 3 * (size_t)tri;
+        o[0] = q0; o[1] = q1; o[2] = q2;
+        o[3] = q0; o[4] = q2; o[5] = q3;
+      }
+      ++quad;
     }
-  }
+  });
 }
 
 // One Newton step onto the level set per vertex, then the clamp to the vertex's own cell.
@@ -327,48 +288,24 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_snap_kernel(float* __restri
 
 // what every entry checks of its grid and threshold before any HIP call
 int mesh_args(const char* entry, const nrf_grid* grid, float threshold, bool with_threshold) {
-  char msg[200];
-  if (!grid) {
-    snprintf(msg, sizeof(msg), "%s: grid is null", entry);
-    return fail(NRF_E_NULL, msg);
-  }
+  if (!grid) return mesh_null(entry, "grid");
   long long cells = 1;
   for (int c = 0; c < 3; ++c) {
     if (grid->dims[c] < 2) {
+      char msg[200];
       snprintf(msg, sizeof(msg), "%s: grid->dims[%d] = %d: a mesh needs at least 2 samples per axis", entry, c, grid->dims[c]);
       return fail(NRF_E_SHAPE, msg);
     }
     cells *= (long long)(grid->dims[c] - 1);
-    if (cells > NRF_MESH_MAX_CELLS) {
-      snprintf(msg, sizeof(msg), "%s: more than NRF_MESH_MAX_CELLS = 1 << 28 cells", entry);
-      return fail(NRF_E_SHAPE, msg);
-    }
+    if (cells > NRF_MESH_MAX_CELLS) return mesh_shape(entry, "more than NRF_MESH_MAX_CELLS = 1 << 28 cells");
   }
-  if (with_threshold && !std::isfinite(threshold)) {
-    snprintf(msg, sizeof(msg), "%s: threshold must be finite", entry);
-    return fail(NRF_E_SHAPE, msg);
-  }
+  if (with_threshold && !std::isfinite(threshold)) return mesh_shape(entry, "threshold must be finite");
   return NRF_OK;
 }
 
-int mesh_null(const char* entry, const char* name) {
-  char msg[200];
-  snprintf(msg, sizeof(msg), "%s: %s is null", entry, name);
-  return fail(NRF_E_NULL, msg);
-}
-
-int mesh_workspace(const char* entry, const MeshPlan& p, const void* workspace, size_t bytes) {
-  char msg[200];
-  if (!workspace) return mesh_null(entry, "workspace");
-  if (((uintptr_t)workspace & 15u) != 0) {
-    snprintf(msg, sizeof(msg), "%s: workspace must be 16-byte aligned", entry);
-    return fail(NRF_E_SHAPE, msg);
-  }
-  if (bytes < p.total) {
-    snprintf(msg, sizeof(msg), "%s: workspace too small (see nrf_mesh_workspace_bytes)", entry);
-    return fail(NRF_E_WORKSPACE, msg);
-  }
-  return NRF_OK;
+// the workspace rule of count and emit; a misaligned pointer is NRF_E_SHAPE to these two (mesh_host.h)
+int grid_workspace(const char* entry, const MeshPlan& p, const void* workspace, size_t bytes) {
+  return mesh_workspace(entry, "nrf_mesh_workspace_bytes", NRF_E_SHAPE, p.total, workspace, bytes);
 }
 
 }  // namespace
@@ -390,57 +327,48 @@ int nrf_mesh_count(const float* sigma, const nrf_grid* grid, float threshold, in
   if (!counts) return mesh_null(entry, "counts");
   const MeshDims d = mesh_dims(grid);
   const MeshPlan p = mesh_plan(d);
-  CK(mesh_workspace(entry, p, workspace, workspace_bytes));
+  CK(grid_workspace(entry, p, workspace, workspace_bytes));
   char* ws = (char*)workspace;
-  hipLaunchKernelGGL(mesh_classify_kernel, dim3(d.nblocks), dim3(MESH_THREADS), 0, (hipStream_t)stream, sigma, d, threshold,
-                     (unsigned char*)(ws + p.mask), (int*)(ws + p.block_v), (int*)(ws + p.block_q));
-  hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, (int*)(ws + p.block_v), (int*)(ws + p.block_q),
-                     d.nblocks, (int*)ws, counts);
+  MESH_LAUNCH(mesh_classify_kernel, d.nblocks, MESH_THREADS, sigma, d, threshold, (unsigned char*)(ws + p.mask), (int*)(ws + p.block_v),
+              (int*)(ws + p.block_q));
+  MESH_LAUNCH(mesh_scan_kernel, 1, SCAN_THREADS, (int*)(ws + p.block_v), (int*)(ws + p.block_q), d.nblocks, (int*)ws, counts);
   return check_launch(entry);
 }
 
 int nrf_mesh_emit(const float* sigma, const nrf_grid* grid, float threshold, int32_t max_vertices, int32_t max_triangles, float* vertices,
                   int32_t* vertex_cell, int32_t* triangles, void* workspace, size_t workspace_bytes, void* stream) {
   const char* entry = "nrf_mesh_emit";
-  char msg[200];
   if (!sigma) return mesh_null(entry, "sigma");
   CK(mesh_args(entry, grid, threshold, true));
-  if (max_vertices < 0 || max_triangles < 0) {
-    snprintf(msg, sizeof(msg), "%s: %s must not be negative", entry, max_vertices < 0 ? "max_vertices" : "max_triangles");
-    return fail(NRF_E_SHAPE, msg);
-  }
+  if (max_vertices < 0) return mesh_shape(entry, "max_vertices must not be negative");
+  if (max_triangles < 0) return mesh_shape(entry, "max_triangles must not be negative");
   if (max_vertices > 0 && !vertices) return mesh_null(entry, "vertices");
   if (max_vertices > 0 && !vertex_cell) return mesh_null(entry, "vertex_cell");
   if (max_triangles > 0 && !triangles) return mesh_null(entry, "triangles");
   const MeshDims d = mesh_dims(grid);
   const MeshPlan p = mesh_plan(d);
-  CK(mesh_workspace(entry, p, workspace, workspace_bytes));
+  CK(grid_workspace(entry, p, workspace, workspace_bytes));
   char* ws = (char*)workspace;
-  hipLaunchKernelGGL(mesh_vertices_kernel, dim3(d.nblocks), dim3(MESH_THREADS), 0, (hipStream_t)stream, sigma, d, *grid, threshold,
-                     (const unsigned char*)(ws + p.mask), (const int*)(ws + p.block_v), (int*)ws, max_vertices, max_triangles, vertices,
-                     vertex_cell, (int*)(ws + p.map));
-  hipLaunchKernelGGL(mesh_faces_kernel, dim3(d.nblocks), dim3(MESH_THREADS), 0, (hipStream_t)stream, d, (const unsigned char*)(ws + p.mask),
-                     (const int*)(ws + p.map), (const int*)(ws + p.block_q), (const int*)ws, max_vertices, max_triangles, triangles);
+  MESH_LAUNCH(mesh_vertices_kernel, d.nblocks, MESH_THREADS, sigma, d, *grid, threshold, (const unsigned char*)(ws + p.mask),
+              (const int*)(ws + p.block_v), (int*)ws, max_vertices, max_triangles, vertices, vertex_cell, (int*)(ws + p.map));
+  MESH_LAUNCH(mesh_faces_kernel, d.nblocks, MESH_THREADS, d, (const unsigned char*)(ws + p.mask), (const int*)(ws + p.map),
+              (const int*)(ws + p.block_q), (const int*)ws, max_vertices, max_triangles, triangles);
   return check_launch(entry);
 }
 
 int nrf_mesh_snap(float* vertices, const int32_t* vertex_cell, const float* sigma_at, const float* grad_at, const nrf_grid* grid,
                   float threshold, int32_t num_vertices, void* stream) {
   const char* entry = "nrf_mesh_snap";
-  char msg[200];
   CK(mesh_args(entry, grid, threshold, true));
-  if (num_vertices < 0) {
-    snprintf(msg, sizeof(msg), "%s: num_vertices must not be negative", entry);
-    return fail(NRF_E_SHAPE, msg);
-  }
+  if (num_vertices < 0) return mesh_shape(entry, "num_vertices must not be negative");
   if (num_vertices == 0) return NRF_OK;   // an empty mesh: the buffers may be NULL
   if (!vertices) return mesh_null(entry, "vertices");
   if (!vertex_cell) return mesh_null(entry, "vertex_cell");
   if (!sigma_at) return mesh_null(entry, "sigma_at");
   if (!grad_at) return mesh_null(entry, "grad_at");
   const MeshDims d = mesh_dims(grid);
-  hipLaunchKernelGGL(mesh_snap_kernel, dim3((num_vertices + MESH_THREADS - 1) / MESH_THREADS), dim3(MESH_THREADS), 0, (hipStream_t)stream,
-                     vertices, vertex_cell, sigma_at, grad_at, *grid, d, threshold, num_vertices);
+  MESH_LAUNCH(mesh_snap_kernel, blocks_of(num_vertices, MESH_THREADS), MESH_THREADS, vertices, vertex_cell, sigma_at, grad_at, *grid, d,
+              threshold, num_vertices);
   return check_launch(entry);
 }
 

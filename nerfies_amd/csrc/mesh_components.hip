@@ -9,26 +9,19 @@
 // returned with a strictly smaller pair of vertices.  No thread waits for another: every loop is bounded by V, holds a hard cap on
 // top of that, and on overrun sets the status block's error word and leaves.
 //
-// Every output slot is a rank, as in mesh.hip: scanned workgroup total + the totals of the (round, wave) pairs before this wave +
-// the popcount of the wave's ballot below this lane.  The only atomics on outputs are the table's integer adds and integer min /
-// max, which do not depend on the order they arrive in.
-#include "mesh_scan.h"
-#include "nrf_handle.h"
+// Every output slot is a rank, by the rule of mesh_rank.h; the ranking kernels here say what is voted on (a vertex is a root, a vertex
+// or triangle is kept) and what is written at the slot.  The only atomics on outputs are the table's integer adds and integer min /
+// max, which do not depend on the order they arrive in.  The host half is built from mesh_host.h.
+#include "mesh_host.h"
+#include "mesh_rank.h"
 
 using namespace nrf;
 using namespace nrf::api;
 
 namespace {
 
-constexpr int MC_THREADS = 256;
-constexpr int MC_WAVES = MC_THREADS / 64;
-constexpr int MC_ROUNDS = 4;
-constexpr int MC_BLOCK = MC_THREADS * MC_ROUNDS;   // vertices (triangles) of one workgroup of the ranking kernels
-constexpr int MC_SLOTS = MC_ROUNDS * MC_WAVES;
-constexpr size_t MC_HEADER_BYTES = 256;            // the status block, padded
-constexpr size_t MC_ALIGN = 256;
-
-inline int blocks_of(int n, int per) { return (int)(((long long)n + per - 1) / per); }
+constexpr int ROUNDS = 4;
+using Elems = MeshRank<ROUNDS>;   // the vertices (triangles) of the ranking kernels
 
 // byte offsets of the components workspace
 struct ComponentsPlan {
@@ -38,11 +31,11 @@ struct ComponentsPlan {
 
 ComponentsPlan components_plan(int V) {
   ComponentsPlan p;
-  p.nbv = blocks_of(V, MC_BLOCK);
-  size_t o = MC_HEADER_BYTES;
-  p.parent = o;      o = align_up(o + sizeof(int) * (size_t)V, MC_ALIGN);
-  p.block_roots = o; o = align_up(o + sizeof(int) * (size_t)p.nbv, MC_ALIGN);
-  p.total = o;
+  MeshCarve c;
+  p.nbv = (int)blocks_of(V, Elems::BLOCK);
+  p.parent = c.take(sizeof(int) * (size_t)V);
+  p.block_roots = c.take(sizeof(int) * (size_t)p.nbv);
+  p.total = c.total;
   return p;
 }
 
@@ -53,19 +46,14 @@ struct SubmeshPlan {
 
 SubmeshPlan submesh_plan(int V, int F) {
   SubmeshPlan p;
-  p.nbv = blocks_of(V, MC_BLOCK);
-  p.nbt = blocks_of(F, MC_BLOCK);
-  size_t o = MC_HEADER_BYTES;
-  p.block_v = o; o = align_up(o + sizeof(int) * (size_t)p.nbv, MC_ALIGN);
-  p.block_t = o; o = align_up(o + sizeof(int) * (size_t)p.nbt, MC_ALIGN);
-  p.total = o;
+  MeshCarve c;
+  p.nbv = (int)blocks_of(V, Elems::BLOCK);
+  p.nbt = (int)blocks_of(F, Elems::BLOCK);
+  p.block_v = c.take(sizeof(int) * (size_t)p.nbv);
+  p.block_t = c.take(sizeof(int) * (size_t)p.nbt);
+  p.total = c.total;
   return p;
 }
-
-__device__ __forceinline__ unsigned long long lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
-
-// the element a thread of a ranking kernel owns in round r; 64-bit, since the last workgroup's may pass 2^31
-__device__ __forceinline__ long long owned(int r) { return (long long)blockIdx.x * MC_BLOCK + r * MC_THREADS + threadIdx.x; }
 
 // an entry of `parent` another workgroup may have rewritten: served by L2, never by this CU's L1
 __device__ __forceinline__ int load_parent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -110,8 +98,8 @@ __device__ void join(int* __restrict__ parent, int a, int b, const int cap, int*
   }
 }
 
-__global__ __launch_bounds__(MC_THREADS) void cc_init_kernel(int* __restrict__ parent, const int V, int* __restrict__ status) {
-  const long long v = (long long)blockIdx.x * MC_THREADS + threadIdx.x;
+__global__ __launch_bounds__(MESH_THREADS) void cc_init_kernel(int* __restrict__ parent, const int V, int* __restrict__ status) {
+  const long long v = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (v < V) parent[v] = (int)v;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     status[2] = 0;
@@ -119,9 +107,9 @@ __global__ __launch_bounds__(MC_THREADS) void cc_init_kernel(int* __restrict__ p
   }
 }
 
-__global__ __launch_bounds__(MC_THREADS) void cc_hook_kernel(const int* __restrict__ triangles, const int F, const int V,
-                                                             int* __restrict__ parent, int* __restrict__ status) {
-  const long long t = (long long)blockIdx.x * MC_THREADS + threadIdx.x;
+__global__ __launch_bounds__(MESH_THREADS) void cc_hook_kernel(const int* __restrict__ triangles, const int F, const int V,
+                                                               int* __restrict__ parent, int* __restrict__ status) {
+  const long long t = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (t >= F) return;
   const int a = triangles[3 * (size_t)t + 0], b = triangles[3 * (size_t)t + 1], c = triangles[3 * (size_t)t + 2];
   if (!valid_triangle(a, b, c, V)) return;
@@ -130,29 +118,22 @@ __global__ __launch_bounds__(MC_THREADS) void cc_hook_kernel(const int* __restri
 }
 
 // every vertex points at its root; per-workgroup totals of the roots
-__global__ __launch_bounds__(MC_THREADS) void cc_flatten_kernel(int* __restrict__ parent, const int V, int* __restrict__ block_roots,
-                                                                int* __restrict__ status) {
-  __shared__ int sr[MC_SLOTS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+__global__ __launch_bounds__(MESH_THREADS) void cc_flatten_kernel(int* __restrict__ parent, const int V, int* __restrict__ block_roots,
+                                                                  int* __restrict__ status) {
+  __shared__ int sr[Elems::SLOTS];
 #pragma unroll
-  for (int r = 0; r < MC_ROUNDS; ++r) {
-    const long long v = owned(r);
+  for (int r = 0; r < ROUNDS; ++r) {
+    const long long v = Elems::owned(r);
     bool root = false;
     if (v < V) {
       const int top = find_root(parent, (int)v, V, status);
       root = top == (int)v;
       if (top >= 0 && !root) __hip_atomic_store(parent + v, top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    const unsigned long long br = __ballot(root);
-    if (lane == 0) sr[r * MC_WAVES + wave] = __popcll(br);
+    Elems::vote(sr, r, root);
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int total = 0;
-#pragma unroll
-    for (int e = 0; e < MC_SLOTS; ++e) total += sr[e];
-    block_roots[blockIdx.x] = total;
-  }
+  if (threadIdx.x == 0) block_roots[blockIdx.x] = Elems::block_total(sr);
 }
 
 __global__ __launch_bounds__(SCAN_THREADS) void cc_scan_kernel(int* __restrict__ block_roots, const int nblocks, int* __restrict__ status,
@@ -167,35 +148,25 @@ __global__ __launch_bounds__(SCAN_THREADS) void cc_scan_kernel(int* __restrict__
 }
 
 // a root's id is its rank among the roots
-__global__ __launch_bounds__(MC_THREADS) void cc_label_roots_kernel(const int* __restrict__ parent, const int V,
-                                                                    const int* __restrict__ block_roots, int* __restrict__ vertex_component) {
-  __shared__ int sr[MC_SLOTS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int rank[MC_ROUNDS];
-  bool roots[MC_ROUNDS];
+__global__ __launch_bounds__(MESH_THREADS) void cc_label_roots_kernel(const int* __restrict__ parent, const int V,
+                                                                      const int* __restrict__ block_roots, int* __restrict__ vertex_component) {
+  __shared__ int sr[Elems::SLOTS];
+  int rank[ROUNDS];
+  bool roots[ROUNDS];
 #pragma unroll
-  for (int r = 0; r < MC_ROUNDS; ++r) {
-    const long long v = owned(r);
-    const bool root = v < V && parent[v] == (int)v;
-    const unsigned long long br = __ballot(root);
-    roots[r] = root;
-    rank[r] = __popcll(br & lanes_below());
-    if (lane == 0) sr[r * MC_WAVES + wave] = __popcll(br);
+  for (int r = 0; r < ROUNDS; ++r) {
+    const long long v = Elems::owned(r);
+    roots[r] = v < V && parent[v] == (int)v;
+    rank[r] = Elems::vote(sr, r, roots[r]);
   }
   __syncthreads();
-  int before = block_roots[blockIdx.x];
-#pragma unroll
-  for (int r = 0; r < MC_ROUNDS; ++r) {
-#pragma unroll
-    for (int w = 0; w < MC_WAVES; ++w) {
-      if (w == wave && roots[r]) vertex_component[owned(r)] = before + rank[r];
-      before += sr[r * MC_WAVES + w];
-    }
-  }
+  Elems::walk(sr, block_roots[blockIdx.x], [&](const int r, const int before) {
+    if (roots[r]) vertex_component[Elems::owned(r)] = before + rank[r];
+  });
 }
 
-__global__ __launch_bounds__(MC_THREADS) void cc_label_rest_kernel(const int* __restrict__ parent, const int V, int* vertex_component) {
-  const long long v = (long long)blockIdx.x * MC_THREADS + threadIdx.x;
+__global__ __launch_bounds__(MESH_THREADS) void cc_label_rest_kernel(const int* __restrict__ parent, const int V, int* vertex_component) {
+  const long long v = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (v >= V) return;
   const int top = parent[v];
   if (top != (int)v && top >= 0 && top < V) vertex_component[v] = vertex_component[top];   // a root's entry is not written here
@@ -212,11 +183,11 @@ constexpr unsigned KEY_PLUS_INF = 0xff800000u;    // float_key(+inf)
 constexpr unsigned KEY_MINUS_INF = 0x007fffffu;   // float_key(-inf)
 
 // zeroes the table's rows and seeds the boxes with (+inf, -inf) as keys; says what this table call writes
-__global__ __launch_bounds__(MC_THREADS) void table_init_kernel(int* __restrict__ status, const int max_components, int* __restrict__ comp_counts,
-                                                                unsigned* __restrict__ comp_bbox) {
+__global__ __launch_bounds__(MESH_THREADS) void table_init_kernel(int* __restrict__ status, const int max_components, int* __restrict__ comp_counts,
+                                                                  unsigned* __restrict__ comp_bbox) {
   const int C = status[0];
   const bool fits = C <= max_components;
-  const long long c = (long long)blockIdx.x * MC_THREADS + threadIdx.x;
+  const long long c = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (fits && c < C) {
     comp_counts[2 * c + 0] = 0;
     comp_counts[2 * c + 1] = 0;
@@ -294,20 +265,20 @@ __device__ __forceinline__ void row_merge(RowAcc& held, const RowAcc& part, cons
 // walks groups of 64 consecutive elements; in a group the lanes of one component are reduced in the wave (the first TABLE_PEEL
 // components of the group; a mesh in surface-nets order has one or two), and the component the wave mostly sees is held in registers
 // across groups, then merged over the workgroup: a large component costs a handful of atomics per workgroup, not one per vertex.
-__global__ __launch_bounds__(MC_THREADS) void table_accumulate_kernel(const int* __restrict__ triangles, const int F,
-                                                                      const float* __restrict__ vertices, const int V,
-                                                                      const int* __restrict__ vertex_component, const int* __restrict__ status,
-                                                                      const int max_components, int* __restrict__ comp_counts,
-                                                                      unsigned* __restrict__ comp_bbox) {
-  __shared__ RowAcc shared[MC_WAVES];
+__global__ __launch_bounds__(MESH_THREADS) void table_accumulate_kernel(const int* __restrict__ triangles, const int F,
+                                                                        const float* __restrict__ vertices, const int V,
+                                                                        const int* __restrict__ vertex_component, const int* __restrict__ status,
+                                                                        const int max_components, int* __restrict__ comp_counts,
+                                                                        unsigned* __restrict__ comp_bbox) {
+  __shared__ RowAcc shared[MESH_WAVES];
   const int C = status[0];
   if (C > max_components) return;   // uniform over the grid
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long n = V > F ? V : F;
-  const long long stride = (long long)gridDim.x * MC_THREADS;
+  const long long stride = (long long)gridDim.x * MESH_THREADS;
   RowAcc held;
   row_clear(held, -1);
-  for (long long base = (long long)blockIdx.x * MC_THREADS + wave * 64; base < n; base += stride) {   // uniform over the wave
+  for (long long base = (long long)blockIdx.x * MESH_THREADS + wave * 64; base < n; base += stride) {   // uniform over the wave
     const long long i = base + lane;
     RowAcc own;
     row_clear(own, -1);
@@ -377,7 +348,7 @@ __global__ __launch_bounds__(MC_THREADS) void table_accumulate_kernel(const int*
   __syncthreads();
   if (threadIdx.x == 0) {   // the waves' held rows, merged where they are one component's
     RowAcc run = shared[0];
-    for (int w = 1; w < MC_WAVES; ++w) {
+    for (int w = 1; w < MESH_WAVES; ++w) {
       const RowAcc next = shared[w];
       if (next.lab == run.lab) {
         row_add(run, next);
@@ -391,33 +362,24 @@ __global__ __launch_bounds__(MC_THREADS) void table_accumulate_kernel(const int*
 }
 
 // the boxes' keys back to floats, in place
-__global__ __launch_bounds__(MC_THREADS) void table_decode_kernel(const int* __restrict__ status, const int max_components,
-                                                                  unsigned* __restrict__ comp_bbox) {
+__global__ __launch_bounds__(MESH_THREADS) void table_decode_kernel(const int* __restrict__ status, const int max_components,
+                                                                    unsigned* __restrict__ comp_bbox) {
   const int C = status[0];
-  const long long w = (long long)blockIdx.x * MC_THREADS + threadIdx.x;
+  const long long w = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (C > max_components || w >= 6ll * C) return;
   comp_bbox[w] = __float_as_uint(key_float(comp_bbox[w]));
 }
 
-__device__ __forceinline__ void store_block_total(const int* s, int* __restrict__ block_total) {
-  int total = 0;
+__global__ __launch_bounds__(MESH_THREADS) void submesh_count_vertices_kernel(const unsigned char* __restrict__ keep, const int V,
+                                                                              int* __restrict__ block_v) {
+  __shared__ int s[Elems::SLOTS];
 #pragma unroll
-  for (int e = 0; e < MC_SLOTS; ++e) total += s[e];
-  block_total[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(MC_THREADS) void submesh_count_vertices_kernel(const unsigned char* __restrict__ keep, const int V,
-                                                                            int* __restrict__ block_v) {
-  __shared__ int s[MC_SLOTS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int r = 0; r < MC_ROUNDS; ++r) {
-    const long long v = owned(r);
-    const unsigned long long bk = __ballot(v < V && keep[v] != 0);
-    if (lane == 0) s[r * MC_WAVES + wave] = __popcll(bk);
+  for (int r = 0; r < ROUNDS; ++r) {
+    const long long v = Elems::owned(r);
+    Elems::vote(s, r, v < V && keep[v] != 0);
   }
   __syncthreads();
-  if (threadIdx.x == 0) store_block_total(s, block_v);
+  if (threadIdx.x == 0) block_v[blockIdx.x] = Elems::block_total(s);
 }
 
 __device__ __forceinline__ bool kept_triangle(const unsigned char* __restrict__ keep, const int* __restrict__ triangles, const long long t,
@@ -427,18 +389,14 @@ __device__ __forceinline__ bool kept_triangle(const unsigned char* __restrict__ 
   return valid_triangle(a, b, c, V) && keep[a] != 0 && keep[b] != 0 && keep[c] != 0;
 }
 
-__global__ __launch_bounds__(MC_THREADS) void submesh_count_triangles_kernel(const unsigned char* __restrict__ keep, const int V,
-                                                                             const int* __restrict__ triangles, const int F,
-                                                                             int* __restrict__ block_t) {
-  __shared__ int s[MC_SLOTS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+__global__ __launch_bounds__(MESH_THREADS) void submesh_count_triangles_kernel(const unsigned char* __restrict__ keep, const int V,
+                                                                               const int* __restrict__ triangles, const int F,
+                                                                               int* __restrict__ block_t) {
+  __shared__ int s[Elems::SLOTS];
 #pragma unroll
-  for (int r = 0; r < MC_ROUNDS; ++r) {
-    const unsigned long long bk = __ballot(kept_triangle(keep, triangles, owned(r), F, V));
-    if (lane == 0) s[r * MC_WAVES + wave] = __popcll(bk);
-  }
+  for (int r = 0; r < ROUNDS; ++r) Elems::vote(s, r, kept_triangle(keep, triangles, Elems::owned(r), F, V));
   __syncthreads();
-  if (threadIdx.x == 0) store_block_total(s, block_t);
+  if (threadIdx.x == 0) block_t[blockIdx.x] = Elems::block_total(s);
 }
 
 __global__ __launch_bounds__(SCAN_THREADS) void submesh_scan_kernel(int* __restrict__ block_v, const int nbv, int* __restrict__ block_t,
@@ -456,22 +414,18 @@ __global__ __launch_bounds__(SCAN_THREADS) void submesh_scan_kernel(int* __restr
 }
 
 // vertex_map, when both capacities hold the scanned totals
-__global__ __launch_bounds__(MC_THREADS) void submesh_map_kernel(const unsigned char* __restrict__ keep, const int V,
-                                                                 const int* __restrict__ block_v, int* __restrict__ status,
-                                                                 const int max_vertices, const int max_triangles, int* __restrict__ vertex_map) {
-  __shared__ int s[MC_SLOTS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+__global__ __launch_bounds__(MESH_THREADS) void submesh_map_kernel(const unsigned char* __restrict__ keep, const int V,
+                                                                   const int* __restrict__ block_v, int* __restrict__ status,
+                                                                   const int max_vertices, const int max_triangles, int* __restrict__ vertex_map) {
+  __shared__ int s[Elems::SLOTS];
   const bool fits = status[0] <= max_vertices && status[1] <= max_triangles;
-  int rank[MC_ROUNDS];
-  bool kept[MC_ROUNDS];
+  int rank[ROUNDS];
+  bool kept[ROUNDS];
 #pragma unroll
-  for (int r = 0; r < MC_ROUNDS; ++r) {
-    const long long v = owned(r);
-    const bool k = v < V && keep[v] != 0;
-    const unsigned long long bk = __ballot(k);
-    kept[r] = k;
-    rank[r] = __popcll(bk & lanes_below());
-    if (lane == 0) s[r * MC_WAVES + wave] = __popcll(bk);
+  for (int r = 0; r < ROUNDS; ++r) {
+    const long long v = Elems::owned(r);
+    kept[r] = v < V && keep[v] != 0;
+    rank[r] = Elems::vote(s, r, kept[r]);
   }
   __syncthreads();
   if (blockIdx.x == 0 && threadIdx.x == 0) {   // what the caller reads back: all of the submesh, or none of it
@@ -479,105 +433,57 @@ __global__ __launch_bounds__(MC_THREADS) void submesh_map_kernel(const unsigned 
     status[3] = fits ? status[1] : 0;
   }
   if (!fits || V == 0) return;
-  int before = block_v[blockIdx.x];
-#pragma unroll
-  for (int r = 0; r < MC_ROUNDS; ++r) {
-#pragma unroll
-    for (int w = 0; w < MC_WAVES; ++w) {
-      const long long v = owned(r);
-      if (w == wave && v < V) vertex_map[v] = kept[r] ? before + rank[r] : -1;
-      before += s[r * MC_WAVES + w];
-    }
-  }
+  Elems::walk(s, block_v[blockIdx.x], [&](const int r, const int before) {
+    const long long v = Elems::owned(r);
+    if (v < V) vertex_map[v] = kept[r] ? before + rank[r] : -1;
+  });
 }
 
 // the kept triangles, in their order, with mapped indices
-__global__ __launch_bounds__(MC_THREADS) void submesh_triangles_kernel(const unsigned char* __restrict__ keep, const int V,
-                                                                       const int* __restrict__ triangles, const int F,
-                                                                       const int* __restrict__ block_t, const int* __restrict__ status,
-                                                                       const int max_vertices, const int max_triangles,
-                                                                       const int* __restrict__ vertex_map, int* __restrict__ triangles_out) {
-  __shared__ int s[MC_SLOTS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+__global__ __launch_bounds__(MESH_THREADS) void submesh_triangles_kernel(const unsigned char* __restrict__ keep, const int V,
+                                                                         const int* __restrict__ triangles, const int F,
+                                                                         const int* __restrict__ block_t, const int* __restrict__ status,
+                                                                         const int max_vertices, const int max_triangles,
+                                                                         const int* __restrict__ vertex_map, int* __restrict__ triangles_out) {
+  __shared__ int s[Elems::SLOTS];
   if (!(status[0] <= max_vertices && status[1] <= max_triangles)) return;   // uniform over the grid
-  int rank[MC_ROUNDS];
-  bool kept[MC_ROUNDS];
+  int rank[ROUNDS];
+  bool kept[ROUNDS];
 #pragma unroll
-  for (int r = 0; r < MC_ROUNDS; ++r) {
-    const bool k = kept_triangle(keep, triangles, owned(r), F, V);
-    const unsigned long long bk = __ballot(k);
-    kept[r] = k;
-    rank[r] = __popcll(bk & lanes_below());
-    if (lane == 0) s[r * MC_WAVES + wave] = __popcll(bk);
+  for (int r = 0; r < ROUNDS; ++r) {
+    kept[r] = kept_triangle(keep, triangles, Elems::owned(r), F, V);
+    rank[r] = Elems::vote(s, r, kept[r]);
   }
   __syncthreads();
-  int before = block_t[blockIdx.x];
-#pragma unroll
-  for (int r = 0; r < MC_ROUNDS; ++r) {
-#pragma unroll
-    for (int w = 0; w < MC_WAVES; ++w) {
-      if (w == wave && kept[r]) {
-        const int slot = before + rank[r];
-        if (slot < max_triangles) {
-          const int* in = triangles + 3 * (size_t)owned(r);
-          int* o = triangles_out + 3 * (size_t)slot;
-          o[0] = vertex_map[in[0]];
-          o[1] = vertex_map[in[1]];
-          o[2] = vertex_map[in[2]];
-        }
-      }
-      before += s[r * MC_WAVES + w];
-    }
-  }
+  Elems::walk(s, block_t[blockIdx.x], [&](const int r, const int before) {
+    const int slot = before + rank[r];
+    if (!kept[r] || slot >= max_triangles) return;
+    const int* in = triangles + 3 * (size_t)Elems::owned(r);
+    int* o = triangles_out + 3 * (size_t)slot;
+    o[0] = vertex_map[in[0]];
+    o[1] = vertex_map[in[1]];
+    o[2] = vertex_map[in[2]];
+  });
 }
 
 // one thread per 4-byte word of src
-__global__ __launch_bounds__(MC_THREADS) void gather_rows_kernel(const unsigned* __restrict__ src, const int width,
-                                                                 const int* __restrict__ vertex_map, const long long words,
-                                                                 unsigned* __restrict__ dst, const int max_rows) {
-  const long long i = (long long)blockIdx.x * MC_THREADS + threadIdx.x;
+__global__ __launch_bounds__(MESH_THREADS) void gather_rows_kernel(const unsigned* __restrict__ src, const int width,
+                                                                   const int* __restrict__ vertex_map, const long long words,
+                                                                   unsigned* __restrict__ dst, const int max_rows) {
+  const long long i = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (i >= words) return;
   const long long v = i / width;
   const int m = vertex_map[v];
   if (m >= 0 && m < max_rows) dst[(size_t)m * width + (size_t)(i - v * width)] = src[i];
 }
 
-int mc_null(const char* entry, const char* name) {
-  char msg[200];
-  snprintf(msg, sizeof(msg), "%s: %s is null", entry, name);
-  return fail(NRF_E_NULL, msg);
-}
-
-int mc_negative(const char* entry, const char* name) {
-  char msg[200];
-  snprintf(msg, sizeof(msg), "%s: %s must not be negative", entry, name);
-  return fail(NRF_E_SHAPE, msg);
-}
-
-int mc_workspace(const char* entry, const char* sizer, size_t need, const void* workspace, size_t bytes) {
-  char msg[200];
-  if (!workspace) return mc_null(entry, "workspace");
-  if (((uintptr_t)workspace & 15u) != 0) {
-    snprintf(msg, sizeof(msg), "%s: workspace must be 16-byte aligned", entry);
-    return fail(NRF_E_WORKSPACE, msg);
-  }
-  if (bytes < need) {
-    snprintf(msg, sizeof(msg), "%s: workspace too small (see %s)", entry, sizer);
-    return fail(NRF_E_WORKSPACE, msg);
-  }
-  return NRF_OK;
-}
-
 // the mesh every entry is handed: counts and the pointers they make necessary
 int mc_mesh(const char* entry, const int32_t* triangles, int32_t num_triangles, int32_t num_vertices) {
-  if (num_vertices < 0) return mc_negative(entry, "num_vertices");
-  if (num_triangles < 0) return mc_negative(entry, "num_triangles");
-  if (num_triangles > 0 && !triangles) return mc_null(entry, "triangles");
+  if (num_vertices < 0) return mesh_shape(entry, "num_vertices must not be negative");
+  if (num_triangles < 0) return mesh_shape(entry, "num_triangles must not be negative");
+  if (num_triangles > 0 && !triangles) return mesh_null(entry, "triangles");
   return NRF_OK;
 }
-
-#define MC_LAUNCH(kernel, blocks, threads, ...) \
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks)), dim3(threads), 0, (hipStream_t)stream, __VA_ARGS__)
 
 }  // namespace
 
@@ -585,9 +491,9 @@ extern "C" {
 
 int nrf_mesh_components_workspace_bytes(int32_t num_vertices, int32_t num_triangles, size_t* bytes) {
   const char* entry = "nrf_mesh_components_workspace_bytes";
-  if (num_vertices < 0) return mc_negative(entry, "num_vertices");
-  if (num_triangles < 0) return mc_negative(entry, "num_triangles");
-  if (!bytes) return mc_null(entry, "bytes");
+  if (num_vertices < 0) return mesh_shape(entry, "num_vertices must not be negative");
+  if (num_triangles < 0) return mesh_shape(entry, "num_triangles must not be negative");
+  if (!bytes) return mesh_null(entry, "bytes");
   *bytes = components_plan(num_vertices).total;
   return NRF_OK;
 }
@@ -596,23 +502,23 @@ int nrf_mesh_components(const int32_t* triangles, int32_t num_triangles, int32_t
                         void* workspace, size_t workspace_bytes, void* stream) {
   const char* entry = "nrf_mesh_components";
   CK(mc_mesh(entry, triangles, num_triangles, num_vertices));
-  if (num_vertices > 0 && !vertex_component) return mc_null(entry, "vertex_component");
-  if (!counts) return mc_null(entry, "counts");
+  if (num_vertices > 0 && !vertex_component) return mesh_null(entry, "vertex_component");
+  if (!counts) return mesh_null(entry, "counts");
   const int V = num_vertices, F = num_triangles;
   const ComponentsPlan p = components_plan(V);
-  CK(mc_workspace(entry, "nrf_mesh_components_workspace_bytes", p.total, workspace, workspace_bytes));
+  CK(mesh_workspace(entry, "nrf_mesh_components_workspace_bytes", NRF_E_WORKSPACE, p.total, workspace, workspace_bytes));
   char* ws = (char*)workspace;
   int* status = (int*)ws;
   int* parent = (int*)(ws + p.parent);
   int* block_roots = (int*)(ws + p.block_roots);
-  const int per_thread = blocks_of(V, MC_THREADS);
-  MC_LAUNCH(cc_init_kernel, per_thread > 0 ? per_thread : 1, MC_THREADS, parent, V, status);
-  if (V > 0 && F > 0) MC_LAUNCH(cc_hook_kernel, blocks_of(F, MC_THREADS), MC_THREADS, triangles, F, V, parent, status);
-  if (V > 0) MC_LAUNCH(cc_flatten_kernel, p.nbv, MC_THREADS, parent, V, block_roots, status);
-  MC_LAUNCH(cc_scan_kernel, 1, SCAN_THREADS, block_roots, p.nbv, status, counts);
+  const int per_thread = (int)blocks_of(V, MESH_THREADS);
+  MESH_LAUNCH(cc_init_kernel, per_thread > 0 ? per_thread : 1, MESH_THREADS, parent, V, status);
+  if (V > 0 && F > 0) MESH_LAUNCH(cc_hook_kernel, blocks_of(F, MESH_THREADS), MESH_THREADS, triangles, F, V, parent, status);
+  if (V > 0) MESH_LAUNCH(cc_flatten_kernel, p.nbv, MESH_THREADS, parent, V, block_roots, status);
+  MESH_LAUNCH(cc_scan_kernel, 1, SCAN_THREADS, block_roots, p.nbv, status, counts);
   if (V > 0) {
-    MC_LAUNCH(cc_label_roots_kernel, p.nbv, MC_THREADS, (const int*)parent, V, (const int*)block_roots, vertex_component);
-    MC_LAUNCH(cc_label_rest_kernel, per_thread, MC_THREADS, (const int*)parent, V, vertex_component);
+    MESH_LAUNCH(cc_label_roots_kernel, p.nbv, MESH_THREADS, (const int*)parent, V, (const int*)block_roots, vertex_component);
+    MESH_LAUNCH(cc_label_rest_kernel, per_thread, MESH_THREADS, (const int*)parent, V, vertex_component);
   }
   return check_launch(entry);
 }
@@ -622,32 +528,32 @@ int nrf_mesh_component_table(const int32_t* triangles, int32_t num_triangles, co
                              void* workspace, size_t workspace_bytes, void* stream) {
   const char* entry = "nrf_mesh_component_table";
   CK(mc_mesh(entry, triangles, num_triangles, num_vertices));
-  if (max_components < 0) return mc_negative(entry, "max_components");
-  if (num_vertices > 0 && !vertex_component) return mc_null(entry, "vertex_component");
-  if (max_components > 0 && !comp_counts) return mc_null(entry, "comp_counts");
-  if (comp_bbox && num_vertices > 0 && !vertices) return mc_null(entry, "vertices (comp_bbox is given)");
-  if (vertices && max_components > 0 && !comp_bbox) return mc_null(entry, "comp_bbox (vertices are given)");
+  if (max_components < 0) return mesh_shape(entry, "max_components must not be negative");
+  if (num_vertices > 0 && !vertex_component) return mesh_null(entry, "vertex_component");
+  if (max_components > 0 && !comp_counts) return mesh_null(entry, "comp_counts");
+  if (comp_bbox && num_vertices > 0 && !vertices) return mesh_null(entry, "vertices (comp_bbox is given)");
+  if (vertices && max_components > 0 && !comp_bbox) return mesh_null(entry, "comp_bbox (vertices are given)");
   const int V = num_vertices, F = num_triangles;
   const ComponentsPlan p = components_plan(V);
-  CK(mc_workspace(entry, "nrf_mesh_components_workspace_bytes", p.total, workspace, workspace_bytes));
+  CK(mesh_workspace(entry, "nrf_mesh_components_workspace_bytes", NRF_E_WORKSPACE, p.total, workspace, workspace_bytes));
   int* status = (int*)workspace;
   unsigned* box = vertices ? (unsigned*)comp_bbox : nullptr;
-  const int cblocks = blocks_of(max_components, MC_THREADS);
-  MC_LAUNCH(table_init_kernel, cblocks > 0 ? cblocks : 1, MC_THREADS, status, max_components, comp_counts, box);
-  const int n = V > F ? V : F;
-  if (n > 0 && max_components > 0)
-    MC_LAUNCH(table_accumulate_kernel, blocks_of(n, MC_THREADS) < TABLE_MAX_BLOCKS ? blocks_of(n, MC_THREADS) : TABLE_MAX_BLOCKS, MC_THREADS, triangles, F, vertices, V, vertex_component, (const int*)status,
-              max_components, comp_counts, box);
+  const int cblocks = (int)blocks_of(max_components, MESH_THREADS);
+  MESH_LAUNCH(table_init_kernel, cblocks > 0 ? cblocks : 1, MESH_THREADS, status, max_components, comp_counts, box);
+  const long long nblocks = blocks_of(V > F ? V : F, MESH_THREADS);
+  if (nblocks > 0 && max_components > 0)
+    MESH_LAUNCH(table_accumulate_kernel, nblocks < TABLE_MAX_BLOCKS ? nblocks : TABLE_MAX_BLOCKS, MESH_THREADS, triangles, F, vertices, V,
+                vertex_component, (const int*)status, max_components, comp_counts, box);
   if (box && max_components > 0)
-    MC_LAUNCH(table_decode_kernel, (6ll * max_components + MC_THREADS - 1) / MC_THREADS, MC_THREADS, (const int*)status, max_components, box);
+    MESH_LAUNCH(table_decode_kernel, blocks_of(6ll * max_components, MESH_THREADS), MESH_THREADS, (const int*)status, max_components, box);
   return check_launch(entry);
 }
 
 int nrf_mesh_submesh_workspace_bytes(int32_t num_vertices, int32_t num_triangles, size_t* bytes) {
   const char* entry = "nrf_mesh_submesh_workspace_bytes";
-  if (num_vertices < 0) return mc_negative(entry, "num_vertices");
-  if (num_triangles < 0) return mc_negative(entry, "num_triangles");
-  if (!bytes) return mc_null(entry, "bytes");
+  if (num_vertices < 0) return mesh_shape(entry, "num_vertices must not be negative");
+  if (num_triangles < 0) return mesh_shape(entry, "num_triangles must not be negative");
+  if (!bytes) return mesh_null(entry, "bytes");
   *bytes = submesh_plan(num_vertices, num_triangles).total;
   return NRF_OK;
 }
@@ -656,17 +562,17 @@ int nrf_mesh_submesh_count(const uint8_t* keep, int32_t num_vertices, const int3
                            void* workspace, size_t workspace_bytes, void* stream) {
   const char* entry = "nrf_mesh_submesh_count";
   CK(mc_mesh(entry, triangles, num_triangles, num_vertices));
-  if (num_vertices > 0 && !keep) return mc_null(entry, "keep");
-  if (!counts) return mc_null(entry, "counts");
+  if (num_vertices > 0 && !keep) return mesh_null(entry, "keep");
+  if (!counts) return mesh_null(entry, "counts");
   const int V = num_vertices, F = num_triangles;
   const SubmeshPlan p = submesh_plan(V, F);
-  CK(mc_workspace(entry, "nrf_mesh_submesh_workspace_bytes", p.total, workspace, workspace_bytes));
+  CK(mesh_workspace(entry, "nrf_mesh_submesh_workspace_bytes", NRF_E_WORKSPACE, p.total, workspace, workspace_bytes));
   char* ws = (char*)workspace;
   int* block_v = (int*)(ws + p.block_v);
   int* block_t = (int*)(ws + p.block_t);
-  if (V > 0) MC_LAUNCH(submesh_count_vertices_kernel, p.nbv, MC_THREADS, keep, V, block_v);
-  if (F > 0) MC_LAUNCH(submesh_count_triangles_kernel, p.nbt, MC_THREADS, keep, V, triangles, F, block_t);
-  MC_LAUNCH(submesh_scan_kernel, 1, SCAN_THREADS, block_v, p.nbv, block_t, p.nbt, (int*)ws, counts);
+  if (V > 0) MESH_LAUNCH(submesh_count_vertices_kernel, p.nbv, MESH_THREADS, keep, V, block_v);
+  if (F > 0) MESH_LAUNCH(submesh_count_triangles_kernel, p.nbt, MESH_THREADS, keep, V, triangles, F, block_t);
+  MESH_LAUNCH(submesh_scan_kernel, 1, SCAN_THREADS, block_v, p.nbv, block_t, p.nbt, (int*)ws, counts);
   return check_launch(entry);
 }
 
@@ -675,19 +581,19 @@ int nrf_mesh_submesh_emit(const uint8_t* keep, int32_t num_vertices, const int32
                           void* stream) {
   const char* entry = "nrf_mesh_submesh_emit";
   CK(mc_mesh(entry, triangles, num_triangles, num_vertices));
-  if (max_vertices < 0) return mc_negative(entry, "max_vertices");
-  if (max_triangles < 0) return mc_negative(entry, "max_triangles");
-  if (num_vertices > 0 && !keep) return mc_null(entry, "keep");
-  if (num_vertices > 0 && !vertex_map) return mc_null(entry, "vertex_map");
-  if (max_triangles > 0 && !triangles_out) return mc_null(entry, "triangles_out");
+  if (max_vertices < 0) return mesh_shape(entry, "max_vertices must not be negative");
+  if (max_triangles < 0) return mesh_shape(entry, "max_triangles must not be negative");
+  if (num_vertices > 0 && !keep) return mesh_null(entry, "keep");
+  if (num_vertices > 0 && !vertex_map) return mesh_null(entry, "vertex_map");
+  if (max_triangles > 0 && !triangles_out) return mesh_null(entry, "triangles_out");
   const int V = num_vertices, F = num_triangles;
   const SubmeshPlan p = submesh_plan(V, F);
-  CK(mc_workspace(entry, "nrf_mesh_submesh_workspace_bytes", p.total, workspace, workspace_bytes));
+  CK(mesh_workspace(entry, "nrf_mesh_submesh_workspace_bytes", NRF_E_WORKSPACE, p.total, workspace, workspace_bytes));
   char* ws = (char*)workspace;
-  MC_LAUNCH(submesh_map_kernel, p.nbv > 0 ? p.nbv : 1, MC_THREADS, keep, V, (const int*)(ws + p.block_v), (int*)ws, max_vertices,
+  MESH_LAUNCH(submesh_map_kernel, p.nbv > 0 ? p.nbv : 1, MESH_THREADS, keep, V, (const int*)(ws + p.block_v), (int*)ws, max_vertices,
             max_triangles, vertex_map);
   if (F > 0 && V > 0 && max_triangles > 0)
-    MC_LAUNCH(submesh_triangles_kernel, p.nbt, MC_THREADS, keep, V, triangles, F, (const int*)(ws + p.block_t), (const int*)ws, max_vertices,
+    MESH_LAUNCH(submesh_triangles_kernel, p.nbt, MESH_THREADS, keep, V, triangles, F, (const int*)(ws + p.block_t), (const int*)ws, max_vertices,
               max_triangles, (const int*)vertex_map, triangles_out);
   return check_launch(entry);
 }
@@ -696,23 +602,23 @@ int nrf_mesh_gather_rows(const void* src, int32_t width, const int32_t* vertex_m
                          void* stream) {
   const char* entry = "nrf_mesh_gather_rows";
   char msg[200];
-  if (num_vertices < 0) return mc_negative(entry, "num_vertices");
-  if (max_rows < 0) return mc_negative(entry, "max_rows");
+  if (num_vertices < 0) return mesh_shape(entry, "num_vertices must not be negative");
+  if (max_rows < 0) return mesh_shape(entry, "max_rows must not be negative");
   if (width < 1) {
     snprintf(msg, sizeof(msg), "%s: width = %d: a row has at least one 4-byte word", entry, width);
     return fail(NRF_E_SHAPE, msg);
   }
   const long long words = (long long)num_vertices * width;
-  const long long blocks = (words + MC_THREADS - 1) / MC_THREADS;
+  const long long blocks = blocks_of(words, MESH_THREADS);
   if (blocks > 0x7fffffffll) {
-    snprintf(msg, sizeof(msg), "%s: num_vertices * width is more than 2^31 - 1 workgroups of %d words", entry, MC_THREADS);
+    snprintf(msg, sizeof(msg), "%s: num_vertices * width is more than 2^31 - 1 workgroups of %d words", entry, MESH_THREADS);
     return fail(NRF_E_SHAPE, msg);
   }
   if (num_vertices == 0 || max_rows == 0) return NRF_OK;   // nothing to copy: the buffers may be NULL
-  if (!src) return mc_null(entry, "src");
-  if (!vertex_map) return mc_null(entry, "vertex_map");
-  if (!dst) return mc_null(entry, "dst");
-  MC_LAUNCH(gather_rows_kernel, blocks, MC_THREADS, (const unsigned*)src, width, vertex_map, words, (unsigned*)dst, max_rows);
+  if (!src) return mesh_null(entry, "src");
+  if (!vertex_map) return mesh_null(entry, "vertex_map");
+  if (!dst) return mesh_null(entry, "dst");
+  MESH_LAUNCH(gather_rows_kernel, blocks, MESH_THREADS, (const unsigned*)src, width, vertex_map, words, (unsigned*)dst, max_rows);
   return check_launch(entry);
 }
 

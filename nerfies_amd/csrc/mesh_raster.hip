@@ -10,11 +10,12 @@
 // draw pass used (raster_shade).
 //
 // No thread waits on another.  A triangle whose pixel box has more than RASTER_SMALL pixels is not drawn by its thread: it is ranked
-// (ballot, then the waves' totals) into its workgroup's RS_THREADS slots of a list, the workgroups' totals are scanned by
-// mesh_scan_totals, and a fixed grid of workgroups strides over the ranks 0 .. total-1, finding each rank's workgroup by bisection of
-// the scan.  Every loop is bounded by a clamped pixel box, by F, or by log2 of the number of workgroups.
-#include "mesh_scan.h"
-#include "nrf_handle.h"
+// within its workgroup (the rule of mesh_rank.h, one round) into the workgroup's Faces::BLOCK slots of a list, the workgroups' totals
+// are scanned, and a fixed grid of workgroups strides over the ranks 0 .. total-1, finding each rank's workgroup by bisection of the
+// scan.  Every loop is bounded by a clamped pixel box, by F, or by log2 of the number of workgroups.  The host half is built from
+// mesh_host.h.
+#include "mesh_host.h"
+#include "mesh_rank.h"
 
 #include <cmath>
 
@@ -25,15 +26,10 @@ using namespace nrf::api;
 
 namespace {
 
-constexpr int RS_THREADS = 256;
-constexpr int RS_WAVES = RS_THREADS / 64;
+using Faces = MeshRank<1>;                   // one triangle per thread of the faces kernel
 constexpr int RASTER_SMALL = 256;            // pixels of a pixel box a single thread still draws
 constexpr int RASTER_LARGE_BLOCKS = 1024;    // at most this many workgroups stride over the list of large triangles
-constexpr size_t RS_HEADER_BYTES = 256;      // the status block, padded
-constexpr size_t RS_ALIGN = 256;
 constexpr unsigned long long KEY_EMPTY = ~0ull;
-
-inline long long blocks_of(long long n, int per) { return (n + per - 1) / per; }
 
 // byte offsets of the workspace
 struct RasterPlan {
@@ -43,12 +39,12 @@ struct RasterPlan {
 
 RasterPlan raster_plan(int F, int W, int H) {
   RasterPlan p;
-  p.nbt = (int)blocks_of(F, RS_THREADS);
-  size_t o = RS_HEADER_BYTES;
-  p.keys = o;        o = align_up(o + sizeof(unsigned long long) * (size_t)W * (size_t)H, RS_ALIGN);
-  p.block_large = o; o = align_up(o + sizeof(int) * (size_t)p.nbt, RS_ALIGN);
-  p.list = o;        o = align_up(o + sizeof(int) * (size_t)p.nbt * RS_THREADS, RS_ALIGN);
-  p.total = o;
+  MeshCarve c;
+  p.nbt = (int)blocks_of(F, Faces::BLOCK);
+  p.keys = c.take(sizeof(unsigned long long) * (size_t)W * (size_t)H);
+  p.block_large = c.take(sizeof(int) * (size_t)p.nbt);
+  p.list = c.take(sizeof(int) * (size_t)p.nbt * Faces::BLOCK);
+  p.total = c.total;
   return p;
 }
 
@@ -119,22 +115,21 @@ __device__ __forceinline__ void raster_offer(unsigned long long* __restrict__ ke
   if (key < __hip_atomic_load(keys + pixel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(keys + pixel, key);
 }
 
-__global__ __launch_bounds__(RS_THREADS) void raster_clear_kernel(unsigned long long* __restrict__ keys, const long long pixels,
-                                                                  int* __restrict__ status) {
-  const long long p = (long long)blockIdx.x * RS_THREADS + threadIdx.x;
+__global__ __launch_bounds__(MESH_THREADS) void raster_clear_kernel(unsigned long long* __restrict__ keys, const long long pixels,
+                                                                    int* __restrict__ status) {
+  const long long p = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (p < pixels) keys[p] = KEY_EMPTY;
   if (p < 4) status[p] = 0;
 }
 
-// One thread per triangle: small ones are drawn here, large ones are ranked into list[blockIdx.x * RS_THREADS ..].
-__global__ __launch_bounds__(RS_THREADS) void raster_faces_kernel(const float* __restrict__ screen, const int V,
-                                                                  const int* __restrict__ triangles, const int F, const int W, const int H,
-                                                                  const float near, unsigned long long* __restrict__ keys,
-                                                                  int* __restrict__ block_large, int* __restrict__ list,
-                                                                  int* __restrict__ status) {
-  __shared__ int wave_large[RS_WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long t = (long long)blockIdx.x * RS_THREADS + threadIdx.x;
+// One thread per triangle: small ones are drawn here, large ones are ranked into list[blockIdx.x * Faces::BLOCK ..].
+__global__ __launch_bounds__(MESH_THREADS) void raster_faces_kernel(const float* __restrict__ screen, const int V,
+                                                                    const int* __restrict__ triangles, const int F, const int W, const int H,
+                                                                    const float near, unsigned long long* __restrict__ keys,
+                                                                    int* __restrict__ block_large, int* __restrict__ list,
+                                                                    int* __restrict__ status) {
+  __shared__ int wave_large[Faces::SLOTS];
+  const long long t = Faces::owned(0);
   RasterTri T;
   const bool drawn = t < F && raster_setup(screen, V, triangles, t, W, H, near, T);
   bool large = false;
@@ -150,20 +145,14 @@ __global__ __launch_bounds__(RS_THREADS) void raster_faces_kernel(const float* _
       }
     }
   }
-  const unsigned long long bd = __ballot(drawn), bl = __ballot(large);
-  if (lane == 0) {
-    wave_large[wave] = __popcll(bl);
-    if (bd != 0ull) atomicAdd(status + 0, __popcll(bd));   // an integer add per wave
-  }
+  const unsigned long long bd = __ballot(drawn);
+  if ((threadIdx.x & 63) == 0 && bd != 0ull) atomicAdd(status + 0, __popcll(bd));   // a count, not a rank: an integer add per wave
+  const int rank = Faces::vote(wave_large, 0, large);
   __syncthreads();
-  int before = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < RS_WAVES; ++w) {
-    before += w < wave ? wave_large[w] : 0;
-    total += wave_large[w];
-  }
-  if (large) list[(size_t)blockIdx.x * RS_THREADS + before + __popcll(bl & ((1ull << lane) - 1ull))] = (int)t;
-  if (threadIdx.x == 0) block_large[blockIdx.x] = total;
+  Faces::walk(wave_large, 0, [&](const int, const int before) {
+    if (large) list[(size_t)blockIdx.x * Faces::BLOCK + before + rank] = (int)t;
+  });
+  if (threadIdx.x == 0) block_large[blockIdx.x] = Faces::block_total(wave_large);
 }
 
 __global__ __launch_bounds__(SCAN_THREADS) void raster_scan_kernel(int* __restrict__ block_large, const int nblocks, int* __restrict__ status) {
@@ -174,11 +163,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void raster_scan_kernel(int* __restri
 
 // Rank r of the large triangles belongs to the faces workgroup g with block_large[g] <= r < block_large[g + 1] (the scan is
 // exclusive); one workgroup draws it, its threads striding over the pixel box.
-__global__ __launch_bounds__(RS_THREADS) void raster_large_kernel(const float* __restrict__ screen, const int V,
-                                                                  const int* __restrict__ triangles, const int F, const int W, const int H,
-                                                                  const float near, unsigned long long* __restrict__ keys,
-                                                                  const int* __restrict__ block_large, const int nblocks,
-                                                                  const int* __restrict__ list, const int* __restrict__ status) {
+__global__ __launch_bounds__(MESH_THREADS) void raster_large_kernel(const float* __restrict__ screen, const int V,
+                                                                    const int* __restrict__ triangles, const int F, const int W, const int H,
+                                                                    const float near, unsigned long long* __restrict__ keys,
+                                                                    const int* __restrict__ block_large, const int nblocks,
+                                                                    const int* __restrict__ list, const int* __restrict__ status) {
   int total = status[1];
   total = total < F ? total : F;
   for (int r = blockIdx.x; r < total; r += gridDim.x) {   // uniform over the workgroup
@@ -188,14 +177,14 @@ __global__ __launch_bounds__(RS_THREADS) void raster_large_kernel(const float* _
       if (block_large[mid] <= r) lo = mid; else hi = mid - 1;
     }
     const int local = r - block_large[lo];
-    if (local < 0 || local >= RS_THREADS) continue;
-    const int t = list[(size_t)lo * RS_THREADS + local];
+    if (local < 0 || local >= Faces::BLOCK) continue;
+    const int t = list[(size_t)lo * Faces::BLOCK + local];
     if (t < 0 || t >= F) continue;
     RasterTri T;
     if (!raster_setup(screen, V, triangles, t, W, H, near, T)) continue;
     const int bw = T.i1 - T.i0 + 1;
     const long long n = (long long)bw * (T.j1 - T.j0 + 1);
-    for (long long p = threadIdx.x; p < n; p += RS_THREADS) {
+    for (long long p = threadIdx.x; p < n; p += MESH_THREADS) {
       const int row = (int)(p / bw);
       const int i = T.i0 + (int)(p - (long long)row * bw), j = T.j0 + row;
       float depth, b[3];
@@ -204,13 +193,13 @@ __global__ __launch_bounds__(RS_THREADS) void raster_large_kernel(const float* _
   }
 }
 
-__global__ __launch_bounds__(RS_THREADS) void raster_resolve_kernel(const float* __restrict__ screen, const int V,
-                                                                    const int* __restrict__ triangles, const int F, const int W, const int H,
-                                                                    const float near, const unsigned long long* __restrict__ keys,
-                                                                    int* __restrict__ face_id, float* __restrict__ depth_out,
-                                                                    float* __restrict__ bary, int* __restrict__ status) {
+__global__ __launch_bounds__(MESH_THREADS) void raster_resolve_kernel(const float* __restrict__ screen, const int V,
+                                                                      const int* __restrict__ triangles, const int F, const int W, const int H,
+                                                                      const float near, const unsigned long long* __restrict__ keys,
+                                                                      int* __restrict__ face_id, float* __restrict__ depth_out,
+                                                                      float* __restrict__ bary, int* __restrict__ status) {
   const long long pixels = (long long)W * H;
-  const long long p = (long long)blockIdx.x * RS_THREADS + threadIdx.x;
+  const long long p = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
   bool covered = false;
   if (p < pixels) {
     const unsigned long long key = keys[p];
@@ -242,12 +231,12 @@ __global__ __launch_bounds__(RS_THREADS) void raster_resolve_kernel(const float*
 }
 
 // one thread per output element
-__global__ __launch_bounds__(RS_THREADS) void raster_interpolate_kernel(const int* __restrict__ face_id, const float* __restrict__ bary,
-                                                                        const long long elements, const int* __restrict__ triangles,
-                                                                        const int F, const float* __restrict__ attributes, const int V,
-                                                                        const int A, const float* __restrict__ background,
-                                                                        float* __restrict__ out) {
-  const long long e = (long long)blockIdx.x * RS_THREADS + threadIdx.x;
+__global__ __launch_bounds__(MESH_THREADS) void raster_interpolate_kernel(const int* __restrict__ face_id, const float* __restrict__ bary,
+                                                                          const long long elements, const int* __restrict__ triangles,
+                                                                          const int F, const float* __restrict__ attributes, const int V,
+                                                                          const int A, const float* __restrict__ background,
+                                                                          float* __restrict__ out) {
+  const long long e = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (e >= elements) return;
   const long long p = e / A;
   const int c = (int)(e - p * A);
@@ -263,16 +252,16 @@ __global__ __launch_bounds__(RS_THREADS) void raster_interpolate_kernel(const in
   out[e] = r;
 }
 
-__global__ __launch_bounds__(RS_THREADS) void raster_visibility_clear_kernel(unsigned char* __restrict__ visible, const int V) {
-  const long long v = (long long)blockIdx.x * RS_THREADS + threadIdx.x;
+__global__ __launch_bounds__(MESH_THREADS) void raster_visibility_clear_kernel(unsigned char* __restrict__ visible, const int V) {
+  const long long v = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (v < V) visible[v] = 0;
 }
 
 // every store writes the same byte value: the order plays no part
-__global__ __launch_bounds__(RS_THREADS) void raster_visibility_kernel(const int* __restrict__ face_id, const long long pixels,
-                                                                       const int* __restrict__ triangles, const int F, const int V,
-                                                                       unsigned char* __restrict__ visible) {
-  const long long p = (long long)blockIdx.x * RS_THREADS + threadIdx.x;
+__global__ __launch_bounds__(MESH_THREADS) void raster_visibility_kernel(const int* __restrict__ face_id, const long long pixels,
+                                                                         const int* __restrict__ triangles, const int F, const int V,
+                                                                         unsigned char* __restrict__ visible) {
+  const long long p = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (p >= pixels) return;
   const int f = face_id[p];
   if (f < 0 || f >= F) return;
@@ -283,40 +272,25 @@ __global__ __launch_bounds__(RS_THREADS) void raster_visibility_kernel(const int
   }
 }
 
-int rs_null(const char* entry, const char* name) {
-  char msg[200];
-  snprintf(msg, sizeof(msg), "%s: %s is null", entry, name);
-  return fail(NRF_E_NULL, msg);
-}
-
-int rs_shape(const char* entry, const char* what) {
-  char msg[200];
-  snprintf(msg, sizeof(msg), "%s: %s", entry, what);
-  return fail(NRF_E_SHAPE, msg);
-}
-
 int rs_image(const char* entry, int32_t num_triangles, int32_t width, int32_t height) {
-  if (num_triangles < 0) return rs_shape(entry, "num_triangles must not be negative");
-  if (width < 1) return rs_shape(entry, "width must be at least 1");
-  if (height < 1) return rs_shape(entry, "height must be at least 1");
+  if (num_triangles < 0) return mesh_shape(entry, "num_triangles must not be negative");
+  if (width < 1) return mesh_shape(entry, "width must be at least 1");
+  if (height < 1) return mesh_shape(entry, "height must be at least 1");
   if ((long long)width * height > (long long)NRF_MESH_RASTER_MAX_PIXELS)
-    return rs_shape(entry, "width * height is more than NRF_MESH_RASTER_MAX_PIXELS");
+    return mesh_shape(entry, "width * height is more than NRF_MESH_RASTER_MAX_PIXELS");
   return NRF_OK;
 }
 
 // the pixels and the mesh interpolate and visibility are handed
 int rs_pixels_mesh(const char* entry, const int32_t* face_id, int64_t num_pixels, const int32_t* triangles, int32_t num_triangles,
                    int32_t num_vertices) {
-  if (num_pixels < 0) return rs_shape(entry, "num_pixels must not be negative");
-  if (num_triangles < 0) return rs_shape(entry, "num_triangles must not be negative");
-  if (num_vertices < 0) return rs_shape(entry, "num_vertices must not be negative");
-  if (num_pixels > 0 && !face_id) return rs_null(entry, "face_id");
-  if (num_triangles > 0 && !triangles) return rs_null(entry, "triangles");
+  if (num_pixels < 0) return mesh_shape(entry, "num_pixels must not be negative");
+  if (num_triangles < 0) return mesh_shape(entry, "num_triangles must not be negative");
+  if (num_vertices < 0) return mesh_shape(entry, "num_vertices must not be negative");
+  if (num_pixels > 0 && !face_id) return mesh_null(entry, "face_id");
+  if (num_triangles > 0 && !triangles) return mesh_null(entry, "triangles");
   return NRF_OK;
 }
-
-#define RS_LAUNCH(kernel, blocks, threads, ...) \
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks)), dim3(threads), 0, (hipStream_t)stream, __VA_ARGS__)
 
 }  // namespace
 
@@ -325,7 +299,7 @@ extern "C" {
 int nrf_mesh_raster_workspace_bytes(int32_t num_triangles, int32_t width, int32_t height, size_t* bytes) {
   const char* entry = "nrf_mesh_raster_workspace_bytes";
   CK(rs_image(entry, num_triangles, width, height));
-  if (!bytes) return rs_null(entry, "bytes");
+  if (!bytes) return mesh_null(entry, "bytes");
   *bytes = raster_plan(num_triangles, width, height).total;
   return NRF_OK;
 }
@@ -334,40 +308,31 @@ int nrf_mesh_raster_draw(const float* screen, int32_t num_vertices, const int32_
                          int32_t height, float near, int32_t* face_id, float* depth, float* bary, void* workspace,
                          size_t workspace_bytes, void* stream) {
   const char* entry = "nrf_mesh_raster_draw";
-  char msg[200];
-  if (num_vertices < 0) return rs_shape(entry, "num_vertices must not be negative");
+  if (num_vertices < 0) return mesh_shape(entry, "num_vertices must not be negative");
   CK(rs_image(entry, num_triangles, width, height));
-  if (!(near >= 0.0f) || !std::isfinite(near)) return rs_shape(entry, "near must be finite and not negative");
-  if (num_vertices > 0 && !screen) return rs_null(entry, "screen");
-  if (num_triangles > 0 && !triangles) return rs_null(entry, "triangles");
-  if (!face_id) return rs_null(entry, "face_id");
-  if (!depth) return rs_null(entry, "depth");
-  if (!workspace) return rs_null(entry, "workspace");
+  if (!(near >= 0.0f) || !std::isfinite(near)) return mesh_shape(entry, "near must be finite and not negative");
+  if (num_vertices > 0 && !screen) return mesh_null(entry, "screen");
+  if (num_triangles > 0 && !triangles) return mesh_null(entry, "triangles");
+  if (!face_id) return mesh_null(entry, "face_id");
+  if (!depth) return mesh_null(entry, "depth");
   const int V = num_vertices, F = num_triangles, W = width, H = height;
   const RasterPlan p = raster_plan(F, W, H);
-  if (((uintptr_t)workspace & 15u) != 0) {
-    snprintf(msg, sizeof(msg), "%s: workspace must be 16-byte aligned", entry);
-    return fail(NRF_E_WORKSPACE, msg);
-  }
-  if (workspace_bytes < p.total) {
-    snprintf(msg, sizeof(msg), "%s: workspace too small (see nrf_mesh_raster_workspace_bytes)", entry);
-    return fail(NRF_E_WORKSPACE, msg);
-  }
+  CK(mesh_workspace(entry, "nrf_mesh_raster_workspace_bytes", NRF_E_WORKSPACE, p.total, workspace, workspace_bytes));
   char* ws = (char*)workspace;
   int* status = (int*)ws;
   unsigned long long* keys = (unsigned long long*)(ws + p.keys);
   int* block_large = (int*)(ws + p.block_large);
   int* list = (int*)(ws + p.list);
   const long long pixels = (long long)W * H;
-  const long long pblocks = blocks_of(pixels, RS_THREADS);
-  RS_LAUNCH(raster_clear_kernel, pblocks, RS_THREADS, keys, pixels, status);
+  const long long pblocks = blocks_of(pixels, MESH_THREADS);
+  MESH_LAUNCH(raster_clear_kernel, pblocks, MESH_THREADS, keys, pixels, status);
   if (F > 0) {
-    RS_LAUNCH(raster_faces_kernel, p.nbt, RS_THREADS, screen, V, triangles, F, W, H, near, keys, block_large, list, status);
-    RS_LAUNCH(raster_scan_kernel, 1, SCAN_THREADS, block_large, p.nbt, status);
-    RS_LAUNCH(raster_large_kernel, F < RASTER_LARGE_BLOCKS ? F : RASTER_LARGE_BLOCKS, RS_THREADS, screen, V, triangles, F, W, H, near, keys,
+    MESH_LAUNCH(raster_faces_kernel, p.nbt, MESH_THREADS, screen, V, triangles, F, W, H, near, keys, block_large, list, status);
+    MESH_LAUNCH(raster_scan_kernel, 1, SCAN_THREADS, block_large, p.nbt, status);
+    MESH_LAUNCH(raster_large_kernel, F < RASTER_LARGE_BLOCKS ? F : RASTER_LARGE_BLOCKS, MESH_THREADS, screen, V, triangles, F, W, H, near, keys,
               (const int*)block_large, p.nbt, (const int*)list, (const int*)status);
   }
-  RS_LAUNCH(raster_resolve_kernel, pblocks, RS_THREADS, screen, V, triangles, F, W, H, near, (const unsigned long long*)keys, face_id, depth,
+  MESH_LAUNCH(raster_resolve_kernel, pblocks, MESH_THREADS, screen, V, triangles, F, W, H, near, (const unsigned long long*)keys, face_id, depth,
             bary, status);
   return check_launch(entry);
 }
@@ -377,15 +342,15 @@ int nrf_mesh_raster_interpolate(const int32_t* face_id, const float* bary, int64
                                 const float* background, float* out, void* stream) {
   const char* entry = "nrf_mesh_raster_interpolate";
   CK(rs_pixels_mesh(entry, face_id, num_pixels, triangles, num_triangles, num_vertices));
-  if (width_a < 1) return rs_shape(entry, "width_a must be at least 1");
-  if (num_pixels > 0x7fffffffll * RS_THREADS / width_a)
-    return rs_shape(entry, "num_pixels * width_a is more than 2^31 - 1 workgroups of 256 elements");
-  if (num_pixels > 0 && !bary) return rs_null(entry, "bary");
-  if (num_vertices > 0 && !attributes) return rs_null(entry, "attributes");
-  if (num_pixels > 0 && !out) return rs_null(entry, "out");
+  if (width_a < 1) return mesh_shape(entry, "width_a must be at least 1");
+  if (num_pixels > 0x7fffffffll * MESH_THREADS / width_a)
+    return mesh_shape(entry, "num_pixels * width_a is more than 2^31 - 1 workgroups of 256 elements");
+  if (num_pixels > 0 && !bary) return mesh_null(entry, "bary");
+  if (num_vertices > 0 && !attributes) return mesh_null(entry, "attributes");
+  if (num_pixels > 0 && !out) return mesh_null(entry, "out");
   if (num_pixels == 0) return NRF_OK;
   const long long elements = (long long)num_pixels * width_a;
-  RS_LAUNCH(raster_interpolate_kernel, blocks_of(elements, RS_THREADS), RS_THREADS, face_id, bary, elements, triangles, num_triangles,
+  MESH_LAUNCH(raster_interpolate_kernel, blocks_of(elements, MESH_THREADS), MESH_THREADS, face_id, bary, elements, triangles, num_triangles,
             attributes, num_vertices, width_a, background, out);
   return check_launch(entry);
 }
@@ -394,12 +359,12 @@ int nrf_mesh_raster_visibility(const int32_t* face_id, int64_t num_pixels, const
                                int32_t num_vertices, uint8_t* visible, void* stream) {
   const char* entry = "nrf_mesh_raster_visibility";
   CK(rs_pixels_mesh(entry, face_id, num_pixels, triangles, num_triangles, num_vertices));
-  if (num_pixels > 0x7fffffffll * RS_THREADS) return rs_shape(entry, "num_pixels is more than 2^31 - 1 workgroups of 256 pixels");
-  if (num_vertices > 0 && !visible) return rs_null(entry, "visible");
+  if (num_pixels > 0x7fffffffll * MESH_THREADS) return mesh_shape(entry, "num_pixels is more than 2^31 - 1 workgroups of 256 pixels");
+  if (num_vertices > 0 && !visible) return mesh_null(entry, "visible");
   if (num_vertices == 0) return NRF_OK;
-  RS_LAUNCH(raster_visibility_clear_kernel, blocks_of(num_vertices, RS_THREADS), RS_THREADS, visible, num_vertices);
+  MESH_LAUNCH(raster_visibility_clear_kernel, blocks_of(num_vertices, MESH_THREADS), MESH_THREADS, visible, num_vertices);
   if (num_pixels > 0 && num_triangles > 0)
-    RS_LAUNCH(raster_visibility_kernel, blocks_of(num_pixels, RS_THREADS), RS_THREADS, face_id, (long long)num_pixels, triangles,
+    MESH_LAUNCH(raster_visibility_kernel, blocks_of(num_pixels, MESH_THREADS), MESH_THREADS, face_id, (long long)num_pixels, triangles,
               num_triangles, num_vertices, visible);
   return check_launch(entry);
 }

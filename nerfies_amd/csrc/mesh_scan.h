@@ -1,6 +1,7 @@
-// The one scan of the mesh entries (mesh.hip, mesh_components.hip): exclusive scans of two arrays of per-workgroup totals, in place,
-// by ONE workgroup of SCAN_THREADS threads, each thread a contiguous run.  No workgroup ever waits on another's flag, so nothing can
-// stall: the kernels before it store the totals, the kernels after it read the scan.
+// The scan of the mesh entries' placement rule (mesh_rank.h; mesh.hip, mesh_components.hip, mesh_raster.hip): exclusive scans of two
+// arrays of per-workgroup totals, in place, by ONE workgroup of SCAN_THREADS threads, each thread a contiguous run.  No workgroup ever
+// waits on another's flag, so nothing can stall: the kernels before it store the totals, the kernels after it read the scan.  Each
+// entry wraps it in a kernel of its own that writes that entry's status words.
 #pragma once
 
 #include <hip/hip_runtime.h>

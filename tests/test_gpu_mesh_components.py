@@ -169,6 +169,40 @@ def test_entries_match_the_reference(name):
       assert torch.equal(_bits(rows[:nv].cpu()), _bits(torch.from_numpy(R.gather_rows(v, vmap)))) and _intact(_bits(rows[nv:]))
 
 
+# The ranking rule by itself (no triangle: a slot is the cumsum of the mask): one lane, the sides of a wave (64), of a round (256), of a
+# workgroup (1024), several workgroups, and 1026 workgroup totals: the one-workgroup scan's threads then own runs of 2, the last cut.
+RULE_V = (1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4097, 1024 * 1024 + 1025)
+NO_FACES = np.zeros((0, 3), np.int32)
+
+
+def _rule_mask(kind, V):
+  if kind == 'random':
+    return (np.random.RandomState(V % 9973).rand(V) < 0.5).astype(np.uint8)
+  return {'all': np.ones(V, np.uint8), 'none': np.zeros(V, np.uint8), 'alternate': (np.arange(V) % 2 == 0).astype(np.uint8)}[kind]
+
+
+@pytest.mark.parametrize('kind', ['all', 'none', 'alternate', 'random'])
+@pytest.mark.parametrize('V', RULE_V)
+def test_the_ranking_rule_alone(V, kind):
+  keep = _rule_mask(kind, V)
+  vmap, faces = R.submesh(keep, NO_FACES, V)
+  nv = int(keep.sum())
+  assert len(faces) == 0 and int((vmap >= 0).sum()) == nv and (nv == 0 or vmap.max() == nv - 1)
+  raw = _Raw(np.zeros((V, 0), np.float32), NO_FACES)
+  assert raw.count(keep) == (nv, 0), (V, kind)
+  gm, gt, status = raw.emit(0, nv, 0)
+  assert status == (nv, 0, nv, 0), (V, kind, status)
+  assert torch.equal(gm[:V].cpu(), torch.from_numpy(vmap)), (V, kind)
+  assert _intact(gm[V:]) and _intact(gt)
+
+
+def test_components_without_triangles_across_1026_workgroups():
+  V = RULE_V[-1]
+  got, gc, status = _Raw(np.zeros((V, 0), np.float32), NO_FACES).components()
+  assert gc == V and status[0] == V and status[2] == 0
+  assert torch.equal(got, torch.arange(V, dtype=torch.int32, device=H.DEV))                 # every vertex is its own component's root
+
+
 def test_scene_components_are_the_balls_alone():
   from nerfies_amd import evaluation
   v, cells, f = R.mesh('scene')

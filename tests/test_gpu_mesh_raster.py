@@ -101,6 +101,31 @@ def _whole_image_with_small():
   return np.array(screen, np.float32), np.array(faces, np.int32)[order], 64, 48, 0.0
 
 
+LARGE_AT = (0, 1, 63, 64, 65, 255, 256, 300, 599)   # first lanes, the sides of a wave and of a workgroup, a third workgroup's last lane
+
+
+def _many_large():
+  """600 triangles (three workgroups of the faces kernel) on 64 x 48: those at LARGE_AT have pixel boxes of more than 256 pixels, the
+  others of at most 16; every triangle has its own constant depth, so no pixel is a tie and the picture has one owner per pixel
+  whatever the order."""
+  rs = np.random.RandomState(12)
+  screen, faces = [], []
+  for t in range(600):
+    if t in LARGE_AT:
+      a = rs.uniform([1, 1], [20, 15])
+      corners = [a, a + [rs.uniform(30, 40), rs.uniform(0, 5)], a + [rs.uniform(0, 5), rs.uniform(25, 30)]]
+      z = 2.0 + 0.05 * LARGE_AT.index(t)
+    else:
+      c = rs.uniform([3, 3], [61, 45])
+      corners = [c + d for d in rs.uniform(-1.5, 1.5, (3, 2))]
+      z = (1.0 if t % 2 == 0 else 3.0) + 0.001 * t                     # in front of the large ones, and behind them
+    if rs.rand() < 0.5:
+      corners = corners[::-1]                                          # either orientation
+    faces.append([len(screen), len(screen) + 1, len(screen) + 2])
+    screen += [[p[0], p[1], z] for p in corners]
+  return np.array(screen, np.float32), np.array(faces, np.int32), 64, 48, 0.0
+
+
 def _cases():
   nan, inf = np.nan, np.inf
   front = _tri([4.2, 3.1, 1.0], [25.7, 5.3, 1.5], [9.4, 20.8, 2.0])
@@ -126,6 +151,7 @@ def _cases():
       'split_256': (_tri([-5.5, 2.5, 1.0], [15.5, 2.5, 1.0], [-5.5, 17.5, 1.0], [-5.5, 2.5, 2.0], [16.5, 2.5, 2.0], [-5.5, 17.5, 2.0]),
                     [[0, 1, 2], [3, 4, 5]], 32, 24, 0.0),
       'whole_image_with_small': _whole_image_with_small(),
+      'many_large': _many_large(),
       'no_faces': (front, np.zeros((0, 3), np.int32), 32, 24, 0.0),
       'no_vertices': (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32), 32, 24, 0.0),
   })
@@ -182,6 +208,31 @@ def test_draw_is_the_reference_bit_for_bit(name):
     assert status[0] >= 20 and status[1] == 1 and covered.all() and len(np.unique(want_id)) > 10
     large = int(np.nonzero((np.asarray(f) == 0).any(1))[0][0])
     assert (want_id == large).sum() > 0.5 * W * H_ and (want_id != large).sum() > 20
+  elif name == 'many_large':
+    assert _large_faces(s, f, W, H_) == list(LARGE_AT) and status[1] == 9 == want_status[1] and status[0] > 500
+    assert not R.tie_pixels(s, f, W, H_).any()
+    assert set(LARGE_AT) <= set(np.unique(want_id)) and len(np.unique(want_id)) > 100   # every large one and many small ones own pixels
+
+
+def _large_faces(s, f, W, H_):
+  """The faces the reference counts as large, from its own pixel boxes."""
+  return [t for t, _, _, _, _, _, i0, i1, j0, j1 in R.triangles(s, f, W, H_) if (i1 - i0 + 1) * (j1 - j0 + 1) > R.SMALL_BOX]
+
+
+def test_many_large_triangles_in_another_order():
+  """The large triangles land on other lanes, waves and workgroups of the faces kernel; the picture is the reference's for that order,
+  and the same picture as before under the permutation (no pixel of this case is a tie)."""
+  s, f, W, H_, near = CASES['many_large']
+  perm = np.random.RandomState(13).permutation(len(f))
+  want_id, want_depth, want_bary, want_status = R.draw(s, f[perm], W, H_, near)
+  assert want_status[1] == 9 and sorted(perm[_large_faces(s, f[perm], W, H_)]) == list(LARGE_AT)
+  face_id, depth, bary, status = _Raw().draw(s, f[perm], W, H_, near)
+  assert status == want_status and status[1] == 9
+  assert np.array_equal(face_id, want_id)
+  assert np.array_equal(_bits(depth), _bits(want_depth)) and np.array_equal(_bits(bary), _bits(want_bary))
+  first_id, first_depth = reference('many_large')[:2]
+  assert np.array_equal(np.where(face_id >= 0, perm[np.maximum(face_id, 0)], -1), first_id)
+  assert np.array_equal(_bits(depth), _bits(first_depth))
 
 
 def test_draw_without_barycentrics_and_with_any_workspace_contents():

@@ -155,6 +155,11 @@ def test_workspace_size_and_short_workspaces(lib):
   assert rc == 0 and base > 0 and c.size() == (0, base)          # equal grids, equal sizes
   assert c.count(nbytes=base - 1) == NRF_E_WORKSPACE and b'nrf_mesh_count' in c.err() and b'nrf_mesh_workspace_bytes' in c.err()
   assert c.emit(nbytes=base - 1) == NRF_E_WORKSPACE and b'nrf_mesh_emit' in c.err() and b'nrf_mesh_workspace_bytes' in c.err()
+  # a workspace that is not 16-byte aligned is NRF_E_SHAPE here; the components and raster entries answer NRF_E_WORKSPACE to the same
+  # thing (their host tests pin that).  The codes are part of the ABI as they stand.
+  off = C.c_void_p(((c.p.value + 15) & ~15) + 4)
+  assert c.count(ws=off) == NRF_E_SHAPE and b'nrf_mesh_count' in c.err() and b'16-byte aligned' in c.err()
+  assert c.emit(ws=off) == NRF_E_SHAPE and b'nrf_mesh_emit' in c.err() and b'16-byte aligned' in c.err()
   # origin, step and threshold play no part
   g = c.grid()
   g.origin[0], g.step[2] = 3.0, 0.25
